@@ -14,12 +14,15 @@ Launch forms:
                                                  CHILD process before anything touches the GPU, relays its output and exit code
   python -m torch.distributed.run ... bench.py   one rank per GPU (RANK / LOCAL_RANK / WORLD_SIZE from the environment)
 
-Prints ONE JSON line on rank 0 (contract in the task description), including
+Prints ONE JSON line on rank 0 (contract in the task description). A plain run sets up, warms up, times EXACTLY --steps
+steps and prints the headline (value, ms_per_step, ...); --dump-outputs DIR also writes what the last timed step computed.
+With --full the line further holds
   roofline     — live HIP-event timing of the dominant kernel (fused ConvLSTM cell), algorithmic FLOPs / duration
   cpu_baseline — the oracle's PyTorch-CPU restatement of the same forward, timed on the host cores (rank 0, N=1 only)
   extras       — further configurations (small batch, training step, exact fp32, predrnn-pp, 128x128x3 10->20), each timed
                  for >= --extras-seconds with its own roofline (N=1: 8 entries; N>1: the training / C4-shaped entries that
                  carry the gradient all-reduce)
+and the full record goes to bench_extras.json.
 """
 import argparse
 import json
@@ -71,7 +74,16 @@ def parse():
     ap.add_argument("--stub", action="store_true",
                     help="(tests/test_host_logic.py) a CPU stand-in for the model on the gloo backend: the launcher, the rank plumbing, the "
                          "barrier + MAX-over-ranks timing brackets and the one JSON line of rank 0 run without a GPU; measures nothing")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: its roofline (HIP events around every fused-cell call of the timed steps), the CPU "
+                         "baseline, the `extras` configurations and the full record in bench_extras.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at "
+                         "most 64 MB in all: a fixed seeded sample of larger outputs); inputs are identical from run to run")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def free_port():
@@ -162,18 +174,52 @@ class Runner:
                               "forward + MSE + backward (BPTT) + flat-bucket all-reduce + fused Adam")
 
     def step(self):
+        """One step of the timed path; returns what its caller receives."""
         import torch
         if self.spec.cell:
             from vp_suite_amd import ops
             with torch.no_grad():
-                ops.convlstm_seq(self.x, None, None, self.cell_w, self.cell_b, *self.cell_peep, seq_len=self.spec.context,
-                                 in_channels=self.spec.cell[0], precision=self.spec.precision)
-            return
+                return ops.convlstm_seq(self.x, None, None, self.cell_w, self.cell_b, *self.cell_peep, seq_len=self.spec.context,
+                                        in_channels=self.spec.cell[0], precision=self.spec.precision)
         if self.spec.mode == "train":
-            self.trainer.step(self.x, self.target, self.spec.pred)
-        else:
-            with torch.no_grad():
-                self.model(self.x, pred_frames=self.spec.pred)
+            return self.trainer.step(self.x, self.target, self.spec.pred)
+        with torch.no_grad():
+            return self.model(self.x, pred_frames=self.spec.pred)
+
+    def outputs(self, res):
+        """{name: tensor} of one step's result `res` (--dump-outputs): the cell's (output, h_T, c_T); the model's predictions and
+        model losses; in train mode the loss and the parameters the step left behind."""
+        import torch
+        if self.spec.cell:
+            return dict(zip(("output", "h_last", "c_last"), res))
+        if self.spec.mode == "train":
+            params = self.trainer.flat_param if self.trainer.fused else torch.cat([p.detach().reshape(-1) for p in self.trainer.params])
+            return {"loss": res, "parameters": params}
+        pred, model_losses = res
+        out = {"predictions": pred}
+        out.update({f"model_loss_{k}": v for k, v in (model_losses or {}).items() if torch.is_tensor(v)})
+        return out
+
+    def train_state(self):
+        """What a training step reads besides its inputs: parameters and buffers, optimizer state, plain counters of the model's
+        modules (PredRNN-V2: training_iteration, sampling_eta) and the RNG streams (its sampling masks)."""
+        import copy
+        import torch
+        return {"model": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
+                "optimizer": copy.deepcopy(self.trainer.optimizer.state_dict()),
+                "attrs": [{k: v for k, v in vars(m).items() if type(v) in (bool, int, float)} for m in self.model.modules()],
+                "rng": (torch.get_rng_state(), torch.cuda.get_rng_state(self.dev))}
+
+    def load_train_state(self, s):
+        import torch
+        with torch.no_grad():
+            self.model.load_state_dict(s["model"])
+        self.trainer.optimizer.load_state_dict(s["optimizer"])
+        for m, attrs in zip(self.model.modules(), s["attrs"]):
+            for k, v in attrs.items():
+                setattr(m, k, v)
+        torch.set_rng_state(s["rng"][0])
+        torch.cuda.set_rng_state(s["rng"][1], self.dev)
 
     def barrier(self):
         import torch
@@ -183,19 +229,22 @@ class Runner:
         if self.dev.type == "cuda":
             torch.cuda.synchronize()
 
-    def timed(self, steps, warmup):
-        """W untimed steps, then EXACTLY `steps` steps between barrier + synchronize brackets; MAX over ranks."""
+    def timed(self, steps, warmup, profile=True):
+        """W untimed steps, then EXACTLY `steps` steps between barrier + synchronize brackets; MAX over ranks. `profile`: HIP events
+        around every fused-cell call of the timed steps (the roofline's kernel time), else no summary. The last step's result is
+        kept in `self.last`."""
         import torch
         import torch.distributed as dist
         from vp_suite_amd import ops
         for _ in range(warmup):
             self.step()
-        prof = ops.KernelProfile()
+        prof = ops.KernelProfile() if profile else None
         ops.PROFILE = prof
         self.barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
-            self.step()
+            self.last = None   # a step's result is freed before the next one runs, as if it were discarded
+            self.last = self.step()
         self.barrier()
         elapsed = time.perf_counter() - t0
         ops.PROFILE = None
@@ -203,7 +252,7 @@ class Runner:
             t = torch.tensor([elapsed], device=self.dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        return elapsed, prof.summary()
+        return elapsed, (prof.summary() if profile else None)
 
     def prewarm(self, seconds):
         """Untimed steps for about `seconds` of wall time BEFORE the W warmup steps: an idle MI355X sits in a low-power state
@@ -285,6 +334,37 @@ class StubRunner(Runner):
         time.sleep(self.sleep_s)
         if self.spec.mode == "train" and self.use_dist:
             dist.all_reduce(self.bucket)
+
+    def outputs(self, res):
+        return {}
+
+
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(arrays, out_dir):
+    """--dump-outputs: writes `arrays` ({name: tensor}) as out_dir/<name>.npy, float64 as float64 and every other dtype as float32.
+    At most DUMP_BUDGET_BYTES in all: an array larger than its share of what is left (smallest arrays first) is written as a fixed
+    1-D sample of its flat elements (sorted indices drawn from a generator seeded by the array's name), so that runs with the same
+    arguments write the same elements; every other array keeps its shape."""
+    import re
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    named = {re.sub(r"[^A-Za-z0-9_.-]+", "_", k): v.detach() for k, v in arrays.items()}
+    width = {k: 8 if t.dtype == torch.float64 else 4 for k, t in named.items()}
+    left = DUMP_BUDGET_BYTES - 4096 * len(named)   # room for the .npy headers
+    for i, name in enumerate(sorted(named, key=lambda k: named[k].numel() * width[k])):
+        t = named[name]
+        keep = min(t.numel(), left // (len(named) - i) // width[name])
+        left -= keep * width[name]
+        if keep < t.numel():
+            gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(t.numel(), (keep,), generator=gen).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        dtype = torch.float64 if width[name] == 8 else torch.float32
+        np.save(os.path.join(out_dir, name + ".npy"), t.to("cpu", dtype).numpy())
 
 
 def measured_traffic(spec):
@@ -503,7 +583,8 @@ def compact_line(full):
     if isinstance(cfg.get("prewarm"), dict):
         cfg["prewarm"] = {k: cfg["prewarm"][k] for k in ("seconds", "steps") if k in cfg["prewarm"]}
     out["config"] = cfg
-    out["roofline"] = compact_roofline(full["roofline"])
+    if "roofline" in full:
+        out["roofline"] = compact_roofline(full["roofline"])
     if "cpu_baseline" in full:
         cb = full["cpu_baseline"]
         out["cpu_baseline"] = {k: cb[k] for k in ("value", "unit", "cores", "kind", "points", "all_cores", "sample") if k in cb}
@@ -608,8 +689,17 @@ def main():
                 channels=args.channels, context=args.context, pred=args.pred, layers=args.layers,
                 cell=tuple(int(v) for v in args.cell.split(",")) if args.cell else None)
     runner = (StubRunner if args.stub else Runner)(spec, dev, rank, world, use_dist)
+    # a training step's result depends on the steps before it, and the prewarm's step count on the clock: when outputs are dumped,
+    # the warmup and timed steps start from the state before the prewarm
+    snapshot = runner.train_state() if (args.dump_outputs and spec.mode == "train" and not args.stub) else None
     prewarm_steps = runner.prewarm(args.prewarm)
-    elapsed, ps = runner.timed(args.steps, args.warmup)
+    if snapshot is not None:
+        runner.load_train_state(snapshot)
+        del snapshot
+    elapsed, ps = runner.timed(args.steps, args.warmup, profile=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(runner.outputs(runner.last), args.dump_outputs)
+    runner.last = None
 
     out = None
     if rank == 0:
@@ -632,16 +722,17 @@ def main():
                        "ranks": world, "backend": (("gloo (stub)" if args.stub else "nccl (RCCL)") if use_dist else "single process"),
                        "prewarm": {"seconds": args.prewarm, "steps": prewarm_steps,
                                    "what": "untimed steps before the W warmup steps: clock ramp out of the idle power state"}},
-            "roofline": roofline(spec, ps),
         }
-    cpu_model = runner.model if (world == 1 and not args.no_cpu_baseline and spec.model == "convlstm-shi") else None
+        if args.full:
+            out["roofline"] = roofline(spec, ps)
+    cpu_model = runner.model if (args.full and world == 1 and not args.no_cpu_baseline and spec.model == "convlstm-shi") else None
     if cpu_model is None:
         del runner
         if not args.stub:
             torch.cuda.empty_cache()
 
     extras = []
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         for es in extras_for(world):
             try:
                 extras.append(run_extra(es, dev, rank, world, use_dist, args.extras_seconds))
@@ -649,7 +740,9 @@ def main():
                 if use_dist:
                     raise
                 extras.append({"name": es.name, "error": f"{type(exc).__name__}: {exc}"})
-    if rank == 0:
+    if rank == 0 and not args.full:   # a plain run: the headline line, no sidecar
+        print(compact_line(out), flush=True)
+    elif rank == 0:
         if extras:
             out["extras"] = extras
         if cpu_model is not None:

@@ -107,7 +107,7 @@ def test_bench_launcher_path_runs_rccl_world1():
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(bench.free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--batch", "8", "--mode", "train", "--no-extras", "--no-cpu-baseline"]
+           "--batch", "8", "--mode", "train", "--full", "--no-extras", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=500)
     assert out.returncode == 0, out.stderr[-2000:]
     last = out.stdout.splitlines()[-1]

@@ -4,7 +4,7 @@
 #   tools/ab_round5.sh defer     deferred ST-LSTM weight gradients vs per-step            (VPX_BENCH_DEFER_WGRAD)
 #   tools/ab_round5.sh glue      stage-glue data gradients on convq vs first generation   (VPX_BENCH_EXPERIMENT=16384)
 #   tools/ab_round5.sh predrnn   the five PredRNN workloads of the extras, as they are
-b() { python3 bench.py "$@" --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "
+b() { python3 bench.py "$@" --full --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('   ', d['ms_per_step'], 'ms  frac', d['roofline']['frac'])"; }
 SHARD="--model predrnn-pp --batch 2 --img 128 --channels 3 --context 10 --pred 30 --layers 4"
