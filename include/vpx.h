@@ -21,6 +21,10 @@
  * vpx_conv2d_ex_fwd / _bwd         Conv2d / ConvTranspose2d + LeakyReLU     vp_suite/models/precipitation_nowcasting/ef_blocks.py:15-49
  * vpx_mse_loss                     MSE measure + loss provider              vp_suite/base/base_measure.py:55-57, measure/loss_provider.py:48-51
  * vpx_adam_step                    torch.optim.Adam(model.parameters(), lr)  vp_suite/vpsuite.py:353, base/base_model.py:174-176
+ * vpx_groupnorm_fwd / _bwd         GroupNorm + LeakyReLU (DCGAN layers)     vp_suite/model_blocks/conv.py, model_blocks/phydnet.py
+ * vpx_phycell_correct_fwd / _bwd   PhyCell_Cell prediction-correction       vp_suite/model_blocks/phydnet.py (PhyCell_Cell.forward)
+ * vpx_moment_loss_fwd / _bwd       K2M + moment regularisation loss         vp_suite/models/phydnet.py (PhyDNet.forward)
+ * vpx_sigmoid_head_fwd / _bwd      sigmoid output + stack of frames         vp_suite/models/phydnet.py (encoder_fwd, forward)
  * vpx_nchw_to_nhwc / nhwc_to_nchw  (layout adaptors at the boundary; the reference is NCHW throughout)
  *
  * Layouts. VPX_LAYOUT_NHWC ("channels last", the library's native layout):
@@ -389,6 +393,37 @@ int vpx_layernorm_fwd(const float* x, const float* gamma, const float* beta, flo
                       void* workspace, size_t workspace_bytes, void* stream);
 int vpx_layernorm_bwd(const float* dy, const float* xhat, const float* stats, const float* gamma, float* dx, float* dgamma, float* dbeta,
                       int B, int HW, int C, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- GroupNorm(G, C) + optional LeakyReLU + optional residual on NHWC tensors (conv.py DCGANConv / DCGANConvTranspose,
+ *      phydnet.py PhyCell_Cell.F; eps = 1e-5, biased variance) ----------------------------------------------------------------- *
+ * x, y, r: [N][HW][C]; gamma, beta: [C]; stats [N][G][2] = (mean, 1/std) written by the forward for the backward.
+ * y = act(x̂ * gamma + beta) + r, act = LeakyReLU(slope) when `act` != 0 else the identity, r optional (NULL: no residual; its gradient
+ * is dy itself). One launch forward (one workgroup per (sample, group), exact two-pass variance in fp32 with fixed-order sums).
+ * The backward recomputes x̂ from x and stats and takes the activation's derivative from the sign of the recomputed pre-activation;
+ * dgamma / dbeta (OVERWRITTEN, optional: both or neither) are reduced through per-sample partials in the workspace in a fixed order
+ * (no atomics: bit-reproducible in every mode). Two launches. */
+int vpx_groupnorm_fwd(const float* x, const float* gamma, const float* beta, const float* r, float* y, float* stats, int N, int HW, int C,
+                      int G, int act, float slope, void* stream);
+size_t vpx_groupnorm_bwd_workspace_bytes(int N, int C);
+int vpx_groupnorm_bwd(const float* x, const float* stats, const float* gamma, const float* beta, const float* dy, float* dx, float* dgamma,
+                      float* dbeta, int N, int HW, int C, int G, int act, float slope, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- PhyDNet (models/phydnet.py, model_blocks/phydnet.py) ------------------------------------------------------------------------ *
+ * PhyCell correction, n elements of one layout: next = (h + Fh) + sigmoid(G) * (E - (h + Fh)). The backward writes dG, dh (the direct
+ * part; the convolution paths add to it), dFh and dE; any of the four may be NULL. */
+int vpx_phycell_correct_fwd(const float* G, const float* Fh, const float* h, const float* E, float* next, long long n, void* stream);
+int vpx_phycell_correct_bwd(const float* G, const float* Fh, const float* h, const float* E, const float* dnext, float* dG, float* dh,
+                            float* dFh, float* dE, long long n, void* stream);
+/* Moment loss of the PhyCell's first filter bank W [hidden][Cin][kh][kw] (kh, kw <= 8): for every input channel b,
+ * moment[o] = M0 · W[o, b] · M1^T with M[i][u] = (u - (k-1)/2)^i / i! (K2M), loss = scale * sum_b mean((moment - C)^2) with
+ * C[o][i][j] = (o == i*kw + j). Computed in fp64, written as fp32 to *loss (one launch). The backward reads dloss from device memory
+ * and OVERWRITES dW = dloss * scale * 2/(hidden*kh*kw) * M0^T (moment - C) M1. */
+int vpx_moment_loss_fwd(const float* W, float* loss, int hidden, int Cin, int kh, int kw, float scale, void* stream);
+int vpx_moment_loss_bwd(const float* W, const float* dloss, float* dW, int hidden, int Cin, int kh, int kw, float scale, void* stream);
+/* Sigmoid output head: x holds nT frames time-major NHWC [nT][B][H*W][C]; frame k lands in slot t0 + k of out [B][T][C][H][W].
+ * The backward reads that slot of out (the saved sigmoid) and of dout and writes dx in x's layout. */
+int vpx_sigmoid_head_fwd(const float* x, float* out, int B, int T, int t0, int nT, int C, int H, int W, void* stream);
+int vpx_sigmoid_head_bwd(const float* out, const float* dout, float* dx, int B, int T, int t0, int nT, int C, int H, int W, void* stream);
 
 /* ---- layout adaptors: src [N,C,H,W] <-> dst [N,H,W,C] -------------------------------------------------------- */
 int vpx_nchw_to_nhwc(const float* src, float* dst, int N, int C, int H, int W, void* stream);

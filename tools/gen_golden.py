@@ -432,8 +432,107 @@ def gen_predrnn():
           chk_w=checksum(model.cell_list[0].conv_x[0].weight), **_sd_meta(model))
 
 
+# --------------------------------------------------------------------------------------------------------------
+# PhyDNet ("phy"): the PhyCell block, tiny / action-conditional / default models (cases: tests/test_phydnet_host.py)
+# --------------------------------------------------------------------------------------------------------------
+def _phy_reference_models():
+    """The reference's MODEL_CLASSES with its decoder's Resize replaced by a size-asserting identity (torchvision is a stub here; at
+    sizes divisible by 4 Resize is the identity)."""
+    import vp_suite.model_blocks.enc as ref_enc
+    from vp_suite.models import MODEL_CLASSES
+
+    class _SameSize(torch.nn.Module):
+        def __init__(self, size):
+            super().__init__()
+            self.size = tuple(size)
+
+        def forward(self, x):
+            assert tuple(x.shape[-2:]) == self.size, (tuple(x.shape), self.size)
+            return x
+    ref_enc.Resize = _SameSize
+    return MODEL_CLASSES
+
+
+def _phy_model_arrays(MC, tag, kw, B):
+    """eval 4 -> 3, pred_1, and training forwards (teacher forcing off / on) with moment loss, total loss and gradient summaries."""
+    from test_phydnet_host import (PHY_TINY_CTX, PHY_TINY_PRED, PHY_TRAIN_CTX, PHY_TRAIN_PRED, grad_summary, phy_fill_)
+    model = MC["phy"]("cpu", **kw)
+    phy_fill_(model, name_seed(f"phydnet.{tag}"))
+    c, h, w = kw["img_shape"]
+    a = kw.get("action_size", 0) if kw.get("action_conditional") else 0
+    arrays = {}
+    x = seeded_rand((B, PHY_TINY_CTX, c, h, w), name_seed(f"phydnet.{tag}.x"))
+    fkw = {}
+    if a:
+        fkw["actions"] = seeded_randn((B, PHY_TINY_CTX + PHY_TINY_PRED - 1, a), name_seed(f"phydnet.{tag}.actions"))
+    with torch.no_grad():
+        arrays["eval"] = _np(model(x, pred_frames=PHY_TINY_PRED, **fkw)[0])
+        if not a:
+            arrays["pred1"] = _np(model.pred_1(x))
+    xt = seeded_rand((B, PHY_TRAIN_CTX + PHY_TRAIN_PRED, c, h, w), name_seed(f"phydnet.{tag}.xt"))
+    tkw = {}
+    if a:
+        tkw["actions"] = seeded_randn((B, PHY_TRAIN_CTX + PHY_TRAIN_PRED - 1, a), name_seed(f"phydnet.{tag}.actions_t"))
+    lp = _loss_provider(c)
+    for tf in ((False, True) if not a else (False,)):
+        model.zero_grad()
+        out, ml = model(xt, pred_frames=PHY_TRAIN_PRED, train=True, teacher_forcing=tf, **tkw)
+        _, total = lp.get_losses(out, xt[:, 1:])
+        moment = ml["moment regularization loss"]
+        total = total + moment
+        total.backward()
+        k = f"tf{int(tf)}"
+        arrays[f"{k}.frames"] = _np(out)
+        arrays[f"{k}.moment"] = np.float64(moment.item())
+        arrays[f"{k}.total"] = np.float64(total.item())
+        for name, (gs, gq, gmax, gkept) in grad_summary({n: p.grad for n, p in model.named_parameters()}).items():
+            arrays[f"{k}.gsum.{name}"] = np.float64(gs)
+            arrays[f"{k}.gsq.{name}"] = np.float64(gq)
+            arrays[f"{k}.gmax.{name}"] = np.float64(gmax)
+            arrays[f"{k}.gkept.{name}"] = gkept.astype(np.float32)
+    arrays.update(chk_x=checksum(x), chk_xt=checksum(xt))
+    return arrays
+
+
+def gen_phydnet():
+    from test_phydnet_host import (PHY_CELL_CASES, PHY_DEFAULT_B, PHY_DEFAULT_CTX, PHY_DEFAULT_KW, PHY_DEFAULT_PRED, PHY_TINY_AC_KW,
+                                   PHY_TINY_B, PHY_TINY_KW, phy_fill_)
+    from vp_suite.model_blocks.phydnet import PhyCell
+    MC = _phy_reference_models()
+    # PhyCell block: outputs per step, final H, all gradients
+    for tag, (idim, hid, k, H, W, asz, B, steps) in PHY_CELL_CASES.items():
+        blk = PhyCell((H, W), idim, [hid], 1, (k, k), asz > 0, asz, "cpu")
+        phy_fill_(blk, name_seed("phydnet_cell." + tag))
+        frames = seeded_randn((B, steps, idim, H, W), name_seed(f"phydnet_cell.{tag}.frames")).requires_grad_(True)
+        actions = seeded_randn((B, steps, max(asz, 1)), name_seed(f"phydnet_cell.{tag}.actions"))[:, :, :asz]
+        loss, arrays = 0.0, {}
+        for t in range(steps):
+            Hs, out = blk(frames[:, t], actions[:, t], first_timestep=(t == 0))
+            gt = seeded_randn(out[-1].shape, name_seed(f"phydnet_cell.{tag}.g{t}"))
+            loss = loss + (out[-1] * gt).sum()
+            arrays[f"out{t}"] = _np(out[-1])
+        arrays["H0"] = _np(Hs[0])
+        loss.backward()
+        arrays["dframes"] = _np(frames.grad)
+        for key, prm in blk.named_parameters():
+            arrays["grad." + key] = _np(prm.grad)
+        arrays.update(_sd_meta(blk))
+        _save(f"phydnet_cell_{tag}", **arrays)
+    _save("phydnet_tiny", **_phy_model_arrays(MC, "tiny", PHY_TINY_KW, PHY_TINY_B))
+    _save("phydnet_tiny_ac", **_phy_model_arrays(MC, "tiny_ac", PHY_TINY_AC_KW, PHY_TINY_B))
+    # default model, 10 -> 10 eval at B = 1: prediction slice + checksum, n_params, state_dict table
+    model = MC["phy"]("cpu", **PHY_DEFAULT_KW)
+    phy_fill_(model, name_seed("phydnet.default"))
+    x = seeded_rand((PHY_DEFAULT_B, PHY_DEFAULT_CTX, 1, 64, 64), name_seed("phydnet.default.x"))
+    with torch.no_grad():
+        pred, _ = model(x, pred_frames=PHY_DEFAULT_PRED)
+    _save("phydnet_default", pred_slice=_np(pred[:, :, :, ::4, ::4]), pred_chk=np.float64(checksum(pred)), chk_x=checksum(x),
+          n_params=np.array(sum(p.numel() for p in model.parameters())), **_sd_meta(model))
+
+
 GENERATORS = {"hzzone": gen_hzzone, "ndrplz": gen_ndrplz, "stlstm": gen_stlstm, "decouple": gen_decouple,
-              "ef": gen_ef, "predrnn": gen_predrnn, "phy_ssc": gen_phydnet_ssc, "acstlstm": gen_acstlstm, "trajgru": gen_trajgru, "ef_trajgru": gen_ef_trajgru, "predrnn_action": gen_predrnn_action}
+              "ef": gen_ef, "predrnn": gen_predrnn, "phy_ssc": gen_phydnet_ssc, "acstlstm": gen_acstlstm, "trajgru": gen_trajgru, "ef_trajgru": gen_ef_trajgru, "predrnn_action": gen_predrnn_action,
+              "phydnet": gen_phydnet}
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()

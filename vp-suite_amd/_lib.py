@@ -43,6 +43,9 @@ EXPORTED_SYMBOLS = [
     "vpx_nchw_to_nhwc", "vpx_nhwc_to_nchw",
     "vpx_layernorm_workspace_bytes", "vpx_layernorm_fwd", "vpx_layernorm_bwd",
     "vpx_mse_loss_workspace_bytes", "vpx_mse_loss", "vpx_adam_step",
+    "vpx_groupnorm_fwd", "vpx_groupnorm_bwd_workspace_bytes", "vpx_groupnorm_bwd",
+    "vpx_phycell_correct_fwd", "vpx_phycell_correct_bwd", "vpx_moment_loss_fwd", "vpx_moment_loss_bwd",
+    "vpx_sigmoid_head_fwd", "vpx_sigmoid_head_bwd",
 ]
 
 
@@ -207,6 +210,24 @@ def lib():
         L.vpx_mse_loss.argtypes = [vp, vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_float, vp, vp, vp, sz, vp]
         L.vpx_adam_step.restype = ctypes.c_int
         L.vpx_adam_step.argtypes = [vp] * 4 + [ctypes.c_longlong] + [ctypes.c_double] * 5 + [ctypes.c_int, ctypes.c_double, vp]
+        L.vpx_groupnorm_fwd.restype = ci
+        L.vpx_groupnorm_fwd.argtypes = [vp] * 6 + [ci] * 5 + [fl, vp]
+        L.vpx_groupnorm_bwd_workspace_bytes.restype = sz
+        L.vpx_groupnorm_bwd_workspace_bytes.argtypes = [ci, ci]
+        L.vpx_groupnorm_bwd.restype = ci
+        L.vpx_groupnorm_bwd.argtypes = [vp] * 8 + [ci] * 5 + [fl, vp, sz, vp]
+        L.vpx_phycell_correct_fwd.restype = ci
+        L.vpx_phycell_correct_fwd.argtypes = [vp] * 5 + [ll, vp]
+        L.vpx_phycell_correct_bwd.restype = ci
+        L.vpx_phycell_correct_bwd.argtypes = [vp] * 9 + [ll, vp]
+        L.vpx_moment_loss_fwd.restype = ci
+        L.vpx_moment_loss_fwd.argtypes = [vp, vp] + [ci] * 4 + [fl, vp]
+        L.vpx_moment_loss_bwd.restype = ci
+        L.vpx_moment_loss_bwd.argtypes = [vp, vp, vp] + [ci] * 4 + [fl, vp]
+        for name in ("vpx_sigmoid_head_fwd", "vpx_sigmoid_head_bwd"):
+            getattr(L, name).restype = ci
+        L.vpx_sigmoid_head_fwd.argtypes = [vp, vp] + [ci] * 7 + [vp]
+        L.vpx_sigmoid_head_bwd.argtypes = [vp, vp, vp] + [ci] * 7 + [vp]
         for name in ("vpx_nchw_to_nhwc", "vpx_nhwc_to_nchw"):
             getattr(L, name).restype = ctypes.c_int
             getattr(L, name).argtypes = [vp, vp] + [ctypes.c_int] * 4 + [vp]
