@@ -425,6 +425,35 @@ int vpx_moment_loss_bwd(const float* W, const float* dloss, float* dW, int hidde
 int vpx_sigmoid_head_fwd(const float* x, float* out, int B, int T, int t0, int nT, int C, int H, int W, void* stream);
 int vpx_sigmoid_head_bwd(const float* out, const float* dout, float* dx, int B, int T, int t0, int nT, int C, int H, int W, void* stream);
 
+/* ---- ST-Phy (models/st_phy.py, model_blocks/enc.py Autoencoder) ------------------------------------------------------------------- *
+ * The layers of vpx_conv2d_ex_fwd / _bwd with an activation code beside the descriptor (whose leaky_slope == 0 means "none", so ReLU
+ * cannot be said there). VPX_ACT_RELU needs leaky_slope == 0 and is applied in the epilogue of the implicit-GEMM launch(es) that run
+ * the layer; VPX_ACT_NONE is exactly vpx_conv2d_ex_fwd / _bwd (y may be NULL in the backward). The backward reads ReLU' off the saved
+ * output y (y > 0; zero at y == 0) in the pass that sums the bias gradient; that pass MULTIPLIES dy by the 0 / 1 derivative, so a
+ * non-finite dy at a dead unit yields NaN (torch selects 0 there). Workspaces: the *_act_* queries (same sizes as the plain layer's). */
+enum { VPX_ACT_NONE = 0, VPX_ACT_RELU = 1 };
+size_t vpx_conv2d_act_workspace_bytes(const vpx_conv_desc* d, int act);
+int vpx_conv2d_act_fwd(const vpx_conv_desc* d, int act, const float* x, const float* w, const float* bias, float* y, void* workspace,
+                       size_t workspace_bytes, void* stream);
+size_t vpx_conv2d_act_bwd_workspace_bytes(const vpx_conv_desc* d, int act);
+int vpx_conv2d_act_bwd(const vpx_conv_desc* d, int act, const float* x, const float* w, const float* y, const float* dy, float* dx,
+                       float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream);
+/* Encoder tail: y = r / max(||r||_2 over W, eps), r = relu(x), per (sample, row, channel) of x [N][H][W][C] (F.normalize(relu(x),
+ * p=2, dim=-1, eps) on the reference's NCHW tensor). norm [N][H][C] (nullable in the forward) receives ||r||_2 for the backward, which
+ * writes dx = relu'(x) * (dy - y <dy, y>) / norm where norm >= eps and relu'(x) * dy / eps below it. One launch each. */
+int vpx_relu_rownorm_fwd(const float* x, float* y, float* norm, int N, int H, int W, int C, float eps, void* stream);
+int vpx_relu_rownorm_bwd(const float* x, const float* norm, const float* dy, float* dx, int N, int H, int W, int C, float eps, void* stream);
+/* Merge: y [N,H,W,Co] = w[:, :Cs] a + w[:, Cs:] b + bias for a [N,H,W,Cs], b [N,H,W,Cp], w [Co, Cs+Cp] (the 1x1 Conv2d over
+ * cat([a, b], dim=1), never materialised); bias nullable. precision: VPX_PREC_F32 | VPX_PREC_BF16X3. The backward OVERWRITES
+ * da, db, dw [Co, Cs+Cp], dbias [Co] (each nullable); parameter gradients are fixed-order sums (bit-reproducible). y, da and db come
+ * from K-split launches with float atomics on small maps unless vpx_set_deterministic(1). */
+size_t vpx_merge1x1_workspace_bytes(int Cs, int Cp, int Co);
+int vpx_merge1x1_fwd(const float* a, const float* b, const float* w, const float* bias, float* y, int N, int H, int W, int Cs, int Cp,
+                     int Co, int precision, void* workspace, size_t workspace_bytes, void* stream);
+size_t vpx_merge1x1_bwd_workspace_bytes(int N, int H, int W, int Cs, int Cp, int Co);
+int vpx_merge1x1_bwd(const float* a, const float* b, const float* w, const float* dy, float* da, float* db, float* dw, float* dbias, int N,
+                     int H, int W, int Cs, int Cp, int Co, int precision, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- layout adaptors: src [N,C,H,W] <-> dst [N,H,W,C] -------------------------------------------------------- */
 int vpx_nchw_to_nhwc(const float* src, float* dst, int N, int C, int H, int W, void* stream);
 int vpx_nhwc_to_nchw(const float* src, float* dst, int N, int C, int H, int W, void* stream);

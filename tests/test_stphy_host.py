@@ -1,0 +1,335 @@
+"""ST-Phy ("st-phy") on the host, no GPU: registry, constructor contract (state_dict keys / shapes / n_params against the reference's,
+pinned in tests/golden/stphy_default.npz), pickling, the errors the port raises, the Decoder's size rule, and the dry-run workspace
+contract (VPX_OPT_DRY_RUN, see test_workspace_contract.py) of the new library entry points over the autoencoder's layer shapes.
+
+Also the case table of the ST-Phy fixtures, shared with test_gpu_stphy.py and tools/gen_golden_stphy.py."""
+import ctypes
+import itertools
+import json
+import pickle
+
+import numpy as np
+import pytest
+import torch
+
+from golden_util import fill_state_dict_, load_golden
+
+# ---- fixture cases (tools/gen_golden_stphy.py) --------------------------------------------------------------------------------------
+STPHY_AE_SHAPE, STPHY_AE_ENC_C, STPHY_AE_B = (1, 32, 40), 16, 2
+STPHY_TINY_KW = dict(img_shape=(1, 32, 40), action_size=0, tensor_value_range=[0.0, 1.0], num_layers=2, st_cell_channels=16,
+                     moment_loss_scale=0.5)
+STPHY_TINY3_KW = dict(img_shape=(3, 40, 32), action_size=0, tensor_value_range=[0.0, 1.0], num_layers=3, st_cell_channels=16)
+STPHY_DEFAULT_KW = dict(img_shape=(1, 64, 64), action_size=0, tensor_value_range=[0.0, 1.0])
+STPHY_TINY_B, STPHY_TINY_CTX, STPHY_TINY_PRED = 2, 4, 3     # eval: 4 -> 3
+STPHY_TRAIN_CTX, STPHY_TRAIN_PRED = 3, 3                    # train: 6 frames, 3 of them predicted
+STPHY_DEFAULT_B, STPHY_DEFAULT_CTX, STPHY_DEFAULT_PRED = 1, 10, 10
+STPHY_DEFAULT_SLICES = ((2, 2), (1, 3), (3, 1))              # offsets of the default fixture's extra [oy::4, ox::4] slices
+GRAD_SLICE = 97                                             # the gradient summaries keep every 97th element (at most 64 of them) ...
+GRAD_FULL_MAX = 64                                          # ... of tensors larger than this; smaller ones in full (fixtures <= 200 KB)
+
+
+def stphy_fill_(module, seed):
+    """fill_state_dict_ (which centres LayerNorm scales on 1) plus 1 on every GroupNorm scale."""
+    fill_state_dict_(module, seed)
+    with torch.no_grad():
+        for _, m in module.named_modules():
+            if isinstance(m, torch.nn.GroupNorm):
+                m.weight.add_(1.0)
+    return module
+
+
+def grad_kept(a):
+    return a if a.size <= GRAD_FULL_MAX else a[::GRAD_SLICE][:64]
+
+
+def grad_summary(named_grads):
+    """{name: (sum, sum of squares, max |g|, the elements kept)} of fp64 numpy copies."""
+    out = {}
+    for k, g in named_grads.items():
+        a = g.detach().cpu().double().numpy().reshape(-1)
+        out[k] = (a.sum(), (a * a).sum(), np.abs(a).max(), grad_kept(a))
+    return out
+
+
+def encoded_hw(n):
+    return ((((n - 5) // 2 + 1) - 3) // 2 + 1) - 2
+
+
+# ---- host tests -------------------------------------------------------------------------------------------------------------------
+def test_stphy_is_registered(vpx):
+    from vp_suite_amd.models import MODEL_CLASSES
+    assert "st-phy" in MODEL_CLASSES
+    assert MODEL_CLASSES["st-phy"].NAME == "ST-Phy"
+    assert not MODEL_CLASSES["st-phy"].CAN_HANDLE_ACTIONS
+
+
+def test_stphy_state_dict_matches_reference_on_cpu(vpx):
+    from vp_suite_amd.models import MODEL_CLASSES
+    g = load_golden("stphy_default")
+    model = MODEL_CLASSES["st-phy"]("cpu", **STPHY_DEFAULT_KW)
+    sd = model.state_dict()
+    assert sorted(sd.keys()) == [str(k) for k in g["sd_keys"]]
+    assert len(sd) == 83
+    shapes = json.loads(str(g["sd_shapes"]))
+    assert {k: list(v.shape) for k, v in sd.items()} == shapes
+    n_params = sum(p.numel() for p in model.parameters())
+    assert n_params == int(g["n_params"]) == 6772922
+    assert tuple(model.autoencoder.encoded_shape[1:]) == (64, 12, 12)
+    assert model.autoencoder.encoded_numel == 64 * 12 * 12
+
+
+@pytest.mark.parametrize("tag,kw", [("stphy_tiny", STPHY_TINY_KW), ("stphy_tiny3", STPHY_TINY3_KW)])
+def test_stphy_tiny_state_dicts(vpx, tag, kw):
+    from vp_suite_amd.models import MODEL_CLASSES
+    g = load_golden(tag)
+    sd = MODEL_CLASSES["st-phy"]("cpu", **kw).state_dict()
+    assert sorted(sd.keys()) == [str(k) for k in g["sd_keys"]]
+    assert {k: list(v.shape) for k, v in sd.items()} == json.loads(str(g["sd_shapes"]))
+
+
+def test_autoencoder_contract(vpx):
+    from vp_suite_amd.model_blocks import Autoencoder
+    g = load_golden("stphy_ae")
+    ae = Autoencoder(STPHY_AE_SHAPE, STPHY_AE_ENC_C, "cpu")
+    assert list(ae.encoded_shape) == [int(v) for v in g["encoded_shape"]] == [1, 16, 4, 6]
+    assert ae.encoded_numel == 16 * 4 * 6
+    sd = ae.state_dict()
+    assert sorted(sd.keys()) == [str(k) for k in g["sd_keys"]]
+    assert {k: list(v.shape) for k, v in sd.items()} == json.loads(str(g["sd_shapes"]))
+
+
+def test_stphy_pickles(vpx):
+    from vp_suite_amd.models import MODEL_CLASSES
+    model = MODEL_CLASSES["st-phy"]("cpu", **STPHY_TINY_KW)
+    stphy_fill_(model, 3)
+    clone = pickle.loads(pickle.dumps(model))
+    for (k, a), (k2, b) in zip(sorted(model.state_dict().items()), sorted(clone.state_dict().items())):
+        assert k == k2 and torch.equal(a, b)
+    assert clone.cell_precision == "f32" and clone.num_layers == 2
+
+
+def test_stphy_refuses_what_it_cannot_run(vpx):
+    from vp_suite_amd.models import MODEL_CLASSES
+    M = MODEL_CLASSES["st-phy"]
+    with pytest.raises(NotImplementedError):
+        M("cpu", img_shape=(1, 64, 64), action_size=3, action_conditional=True, tensor_value_range=[0.0, 1.0])
+    for shape in ((1, 62, 64), (1, 64, 34), (1, 16, 16), (3, 22, 22)):
+        with pytest.raises(ValueError):
+            M("cpu", img_shape=shape, action_size=0, tensor_value_range=[0.0, 1.0])
+    with pytest.raises(ValueError):
+        M("cpu", cell_precision="bf16", **STPHY_DEFAULT_KW)
+    with pytest.raises(ValueError):
+        M("cpu", phycell_kernel_size=(5, 3), **STPHY_DEFAULT_KW)
+
+
+def test_decoder_size_rule(vpx):
+    from vp_suite_amd.model_blocks import Decoder
+    for n in range(20, 129, 4):
+        assert 4 * encoded_hw(n) + 16 == n
+        Decoder(16, (1, n, 20))
+        Decoder(16, (3, 24, n))
+    for n in (22, 34, 62, 16, 19):
+        with pytest.raises(ValueError):
+            Decoder(16, (1, n, 64))
+        with pytest.raises(ValueError):
+            Decoder(16, (1, 64, n))
+
+
+def test_stphy_training_loss_argument_contract(vpx):
+    from vp_suite_amd.models import MODEL_CLASSES
+    model = MODEL_CLASSES["st-phy"]("cpu", **STPHY_TINY_KW)
+    inp = torch.rand(2, 3, 1, 32, 40)
+    with pytest.raises(ValueError):
+        model.training_loss(inp, None, 3, None)
+    with pytest.raises(ValueError):
+        model.training_loss(inp, torch.rand(2, 2, 1, 32, 40), 3, None)       # not pred_frames targets
+    with pytest.raises(ValueError):
+        model.training_loss(inp, torch.rand(1, 3, 1, 32, 40), 3, None)       # another batch
+    model.training_epoch = 0
+    assert bool(model._teacher_forcing_draw())          # epoch 0: probability 1
+    model.training_epoch = 10 ** 6
+    assert not model._teacher_forcing_draw()
+
+
+def test_stphy_ops_refuse_cpu_tensors(vpx):
+    """No CPU fallback: every op raises on host tensors before anything else."""
+    from vp_suite_amd import stphy_ops
+    from vp_suite_amd._lib import VpxError
+    with pytest.raises(VpxError):
+        stphy_ops.conv2d_act(torch.rand(2, 1, 32, 40), torch.rand(32, 1, 5, 5), torch.rand(32), 2, 0)
+    with pytest.raises(VpxError):
+        stphy_ops.relu_rownorm(torch.rand(2, 16, 4, 6))
+    with pytest.raises(VpxError):
+        stphy_ops.merge1x1(torch.rand(2, 16, 4, 6), torch.rand(2, 16, 4, 6), torch.rand(16, 32, 1, 1))
+    from vp_suite_amd.models import MODEL_CLASSES
+    model = MODEL_CLASSES["st-phy"]("cpu", **STPHY_TINY_KW)
+    with pytest.raises(VpxError):
+        model(torch.rand(1, 2, 1, 32, 40), pred_frames=1)
+
+
+# ---- dry-run workspace contract -----------------------------------------------------------------------------------------------------
+OK, E_ARG, E_WS, E_UNSUP = 0, -1, -2, -4
+WS_BASE = 0x7F0000000000
+WS_BASE_ODD = WS_BASE + 0x40
+ACT_NONE, ACT_RELU = 0, 1
+
+
+def _fake(i):
+    return ctypes.c_void_p(0x100000000000 + i * (1 << 36))
+
+
+@pytest.fixture(scope="module")
+def L():
+    from vp_suite_amd import _lib
+    lib = _lib.lib()
+    prev = lib.vpx_set_option(_lib.OPT_DRY_RUN, 1)
+    yield lib
+    lib.vpx_set_option(_lib.OPT_DRY_RUN, prev)
+    lib.vpx_set_deterministic(0)
+
+
+def autoencoder_layers(c, h, w, enc_c):
+    """(H, W, Ci, Co, k, stride, transposed, act) of the seven layers of Autoencoder(img_shape=(c, h, w), enc_c)."""
+    h1, w1 = (h - 5) // 2 + 1, (w - 5) // 2 + 1
+    h2, w2 = (h1 - 3) // 2 + 1, (w1 - 3) // 2 + 1
+    h3, w3 = h2 - 2, w2 - 2
+    return [(h, w, c, 32, 5, 2, 0, ACT_RELU), (h1, w1, 32, 64, 3, 2, 0, ACT_RELU), (h2, w2, 64, enc_c, 3, 1, 0, ACT_NONE),
+            (h3, w3, enc_c, enc_c, 1, 1, 0, ACT_RELU), (h3, w3, enc_c, 64, 6, 2, 1, ACT_RELU),
+            (2 * h3 + 4, 2 * w3 + 4, 64, 32, 6, 2, 1, ACT_RELU), (4 * h3 + 12, 4 * w3 + 12, 32, c, 5, 1, 1, ACT_NONE)]
+
+
+AE_GEOMETRIES = [(1, 32, 40, 16), (1, 64, 64, 64), (3, 128, 128, 64), (3, 40, 32, 16)]
+
+
+@pytest.mark.parametrize("det", [0, 1])
+@pytest.mark.parametrize("prec", [0, 1])
+def test_conv2d_act_entry_points(L, det, prec):
+    from vp_suite_amd._lib import ConvDesc
+    L.vpx_set_deterministic(det)
+    for (c, h, w, enc_c), N in itertools.product(AE_GEOMETRIES, (1, 2, 16, 160)):
+        layers = autoencoder_layers(c, h, w, enc_c)
+        for i, (H, W, Ci, Co, k, s, tr, act) in enumerate(layers):
+            d = ConvDesc(N, H, W, Ci, Co, k, k, s, 0, tr, 0.0, prec, 0, 0)
+            ho, wo = ctypes.c_int(0), ctypes.c_int(0)
+            assert L.vpx_conv2d_ex_out_shape(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)) == OK, L.vpx_last_error()
+            if i + 1 < len(layers):
+                assert (ho.value, wo.value) == layers[i + 1][:2]
+            else:
+                assert (ho.value, wo.value) == (h, w)
+            nb = L.vpx_conv2d_act_workspace_bytes(ctypes.byref(d), act)
+            assert nb > 0, L.vpx_last_error()
+            for base in (WS_BASE, WS_BASE_ODD):
+                rc = L.vpx_conv2d_act_fwd(ctypes.byref(d), act, _fake(1), _fake(2), _fake(3), _fake(4), ctypes.c_void_p(base), nb, None)
+                assert rc == OK, (H, W, Ci, Co, k, s, tr, L.vpx_last_error())
+            assert L.vpx_conv2d_act_fwd(ctypes.byref(d), act, _fake(1), _fake(2), _fake(3), _fake(4), ctypes.c_void_p(WS_BASE), nb - 256 - 4,
+                                        None) == E_WS
+            nbw = L.vpx_conv2d_act_bwd_workspace_bytes(ctypes.byref(d), act)
+            assert nbw > 0, L.vpx_last_error()
+            rc = L.vpx_conv2d_act_bwd(ctypes.byref(d), act, _fake(1), _fake(2), _fake(4), _fake(5), _fake(6), _fake(7), _fake(8),
+                                      ctypes.c_void_p(WS_BASE_ODD), nbw, None)
+            assert rc == OK, (H, W, Ci, Co, k, s, tr, L.vpx_last_error())
+            assert L.vpx_conv2d_act_bwd(ctypes.byref(d), act, _fake(1), _fake(2), _fake(4), _fake(5), _fake(6), _fake(7), _fake(8),
+                                        ctypes.c_void_p(WS_BASE), nbw - 256 - 4, None) == E_WS
+
+
+def test_conv2d_act_rejects_bad_arguments(L):
+    from vp_suite_amd._lib import ConvDesc
+    d = ConvDesc(2, 14, 18, 32, 64, 3, 3, 2, 0, 0, 0.0, 0, 0, 0)
+    nb = L.vpx_conv2d_act_workspace_bytes(ctypes.byref(d), ACT_RELU)
+    assert L.vpx_conv2d_act_workspace_bytes(ctypes.byref(d), 7) == 0
+    assert L.vpx_conv2d_act_fwd(ctypes.byref(d), 7, _fake(1), _fake(2), _fake(3), _fake(4), ctypes.c_void_p(WS_BASE), nb, None) == E_ARG
+    assert b"activation" in L.vpx_last_error()
+    assert L.vpx_conv2d_act_fwd(ctypes.byref(d), ACT_RELU, None, _fake(2), _fake(3), _fake(4), ctypes.c_void_p(WS_BASE), nb, None) == E_ARG
+    leaky = ConvDesc(2, 14, 18, 32, 64, 3, 3, 2, 0, 0, 0.2, 0, 0, 0)      # ReLU beside a LeakyReLU slope: refused, in both directions
+    assert L.vpx_conv2d_act_fwd(ctypes.byref(leaky), ACT_RELU, _fake(1), _fake(2), _fake(3), _fake(4), ctypes.c_void_p(WS_BASE), nb, None) == E_ARG
+    nbw = L.vpx_conv2d_act_bwd_workspace_bytes(ctypes.byref(d), ACT_RELU)
+    assert L.vpx_conv2d_act_bwd(ctypes.byref(leaky), ACT_RELU, _fake(1), _fake(2), _fake(4), _fake(5), _fake(6), _fake(7), _fake(8),
+                                ctypes.c_void_p(WS_BASE), nbw, None) == E_ARG
+    assert L.vpx_conv2d_act_bwd_workspace_bytes(ctypes.byref(leaky), ACT_RELU) == 0       # ... and by the size query, like the forward's
+    assert L.vpx_conv2d_act_workspace_bytes(ctypes.byref(leaky), ACT_RELU) == 0
+    assert L.vpx_conv2d_act_bwd_workspace_bytes(ctypes.byref(d), 7) == 0
+    # the saved output is what ReLU' is read from; the message names the entry point that was called
+    assert L.vpx_conv2d_act_bwd(ctypes.byref(d), ACT_RELU, _fake(1), _fake(2), None, _fake(5), _fake(6), _fake(7), _fake(8),
+                                ctypes.c_void_p(WS_BASE), nbw, None) == E_ARG
+    assert b"vpx_conv2d_act_bwd" in L.vpx_last_error() and b"forward output" in L.vpx_last_error()
+    # without an activation the output is not read: NULL is fine
+    assert L.vpx_conv2d_act_bwd(ctypes.byref(d), ACT_NONE, _fake(1), _fake(2), None, _fake(5), _fake(6), _fake(7), _fake(8),
+                                ctypes.c_void_p(WS_BASE), nbw, None) == OK
+
+
+def test_relu_rownorm_entry_points(L):
+    for (c, h, w, enc_c), N in itertools.product(AE_GEOMETRIES, (1, 2, 16, 640)):
+        h3, w3 = encoded_hw(h), encoded_hw(w)
+        assert L.vpx_relu_rownorm_fwd(_fake(1), _fake(2), _fake(3), N, h3, w3, enc_c, 1e-8, None) == OK, L.vpx_last_error()
+        assert L.vpx_relu_rownorm_fwd(_fake(1), _fake(2), None, N, h3, w3, enc_c, 1e-8, None) == OK       # inference: no norm kept
+        assert L.vpx_relu_rownorm_bwd(_fake(1), _fake(3), _fake(4), _fake(5), N, h3, w3, enc_c, 1e-8, None) == OK, L.vpx_last_error()
+    assert L.vpx_relu_rownorm_fwd(_fake(1), _fake(2), _fake(3), 2, 4, 6, 7, 1e-8, None) == OK              # odd channel count: scalar form
+    assert L.vpx_relu_rownorm_fwd(_fake(1), _fake(2), _fake(3), 2, 4, 0, 16, 1e-8, None) == E_ARG
+    assert L.vpx_relu_rownorm_fwd(_fake(1), _fake(2), _fake(3), 2, 4, 6, 16, 0.0, None) == E_ARG
+    assert L.vpx_relu_rownorm_fwd(None, _fake(2), _fake(3), 2, 4, 6, 16, 1e-8, None) == E_ARG
+    assert L.vpx_relu_rownorm_bwd(_fake(1), None, _fake(4), _fake(5), 2, 4, 6, 16, 1e-8, None) == E_ARG
+
+
+@pytest.mark.parametrize("det", [0, 1])
+@pytest.mark.parametrize("prec", [0, 1])
+def test_merge1x1_entry_points(L, det, prec):
+    L.vpx_set_deterministic(det)
+    for Cs, (H, W), N in itertools.product((16, 64), ((4, 6), (12, 12), (28, 28)), (1, 2, 16, 640)):
+        Cp, Co = Cs, Cs
+        nb = L.vpx_merge1x1_workspace_bytes(Cs, Cp, Co)
+        assert nb > 0
+        for base in (WS_BASE, WS_BASE_ODD):
+            rc = L.vpx_merge1x1_fwd(_fake(1), _fake(2), _fake(3), _fake(4), _fake(5), N, H, W, Cs, Cp, Co, prec, ctypes.c_void_p(base), nb, None)
+            assert rc == OK, L.vpx_last_error()
+        assert L.vpx_merge1x1_fwd(_fake(1), _fake(2), _fake(3), None, _fake(5), N, H, W, Cs, Cp, Co, prec, ctypes.c_void_p(WS_BASE), nb, None) == OK
+        assert L.vpx_merge1x1_fwd(_fake(1), _fake(2), _fake(3), None, _fake(5), N, H, W, Cs, Cp, Co, prec, ctypes.c_void_p(WS_BASE), nb - 256 - 4,
+                                  None) == E_WS
+        nbw = L.vpx_merge1x1_bwd_workspace_bytes(N, H, W, Cs, Cp, Co)
+        assert nbw > 0
+        for base in (WS_BASE, WS_BASE_ODD):
+            rc = L.vpx_merge1x1_bwd(_fake(1), _fake(2), _fake(3), _fake(6), _fake(7), _fake(8), _fake(9), _fake(10), N, H, W, Cs, Cp, Co, prec,
+                                    ctypes.c_void_p(base), nbw, None)
+            assert rc == OK, L.vpx_last_error()
+        assert L.vpx_merge1x1_bwd(_fake(1), _fake(2), _fake(3), _fake(6), _fake(7), _fake(8), _fake(9), _fake(10), N, H, W, Cs, Cp, Co, prec,
+                                  ctypes.c_void_p(WS_BASE), nbw - 256 - 4, None) == E_WS
+    # unequal halves, as a hidden_conv over another width would have them
+    nb = L.vpx_merge1x1_workspace_bytes(48, 16, 24)
+    assert L.vpx_merge1x1_fwd(_fake(1), _fake(2), _fake(3), _fake(4), _fake(5), 2, 5, 7, 48, 16, 24, prec, ctypes.c_void_p(WS_BASE), nb, None) == OK
+    nbw = L.vpx_merge1x1_bwd_workspace_bytes(2, 5, 7, 48, 16, 24)
+    assert L.vpx_merge1x1_bwd(_fake(1), _fake(2), _fake(3), _fake(6), _fake(7), _fake(8), _fake(9), _fake(10), 2, 5, 7, 48, 16, 24, prec,
+                              ctypes.c_void_p(WS_BASE), nbw, None) == OK
+
+
+def test_merge1x1_rejects_bad_arguments(L):
+    nb = L.vpx_merge1x1_workspace_bytes(16, 16, 16)
+    assert L.vpx_merge1x1_workspace_bytes(0, 16, 16) == 0
+    assert L.vpx_merge1x1_fwd(_fake(1), _fake(2), _fake(3), None, _fake(5), 2, 4, 6, 16, 0, 16, 0, ctypes.c_void_p(WS_BASE), nb, None) == E_ARG
+    assert L.vpx_merge1x1_fwd(_fake(1), None, _fake(3), None, _fake(5), 2, 4, 6, 16, 16, 16, 0, ctypes.c_void_p(WS_BASE), nb, None) == E_ARG
+    assert L.vpx_merge1x1_fwd(_fake(1), _fake(2), _fake(3), None, _fake(5), 2, 4, 6, 16, 16, 16, 2, ctypes.c_void_p(WS_BASE), nb, None) == E_UNSUP
+
+
+# ---- the plain-torch restatement (tests/stphy_ref.py) against the reference's fixture, on the CPU ------------------------------------
+def test_stphy_ref_matches_fixture_on_cpu(vpx):
+    """stphy_ref is what tools/bench_stphy.py times beside the library: it must compute the reference's model. f32 on the CPU against the
+    f32 CPU fixture: 1e-5 on frames (the block-level bar), 1e-5 relative on the two model losses."""
+    import stphy_ref
+    from golden_util import name_seed, seeded_rand
+    from vp_suite_amd.models import MODEL_CLASSES
+    g = load_golden("stphy_tiny")
+    model = MODEL_CLASSES["st-phy"]("cpu", **STPHY_TINY_KW)
+    stphy_fill_(model, name_seed("stphy.tiny"))
+    sd = {k: v.detach() for k, v in model.state_dict().items()}
+    c, h, w = STPHY_TINY_KW["img_shape"]
+    kw = dict(num_layers=STPHY_TINY_KW["num_layers"], moment_loss_scale=STPHY_TINY_KW["moment_loss_scale"])
+    x = seeded_rand((STPHY_TINY_B, STPHY_TINY_CTX, c, h, w), name_seed("stphy.tiny.x"))
+    with torch.no_grad():
+        pred, ml = stphy_ref.forward(sd, x, STPHY_TINY_PRED, **kw)
+        assert ml is None
+        assert float((pred - torch.from_numpy(g["eval"])).abs().max()) < 1e-5 * float(np.abs(g["eval"]).max())
+        xt = seeded_rand((STPHY_TINY_B, STPHY_TRAIN_CTX + STPHY_TRAIN_PRED, c, h, w), name_seed("stphy.tiny.xt"))
+        for tf in (False, True):
+            out, ml = stphy_ref.forward(sd, xt, STPHY_TRAIN_PRED, train=True, teacher_forcing=tf, **kw)
+            ref = g[f"tf{int(tf)}.frames"]
+            assert float((out - torch.from_numpy(ref)).abs().max()) < 1e-5 * float(np.abs(ref).max())
+            assert abs(float(ml["moment regularization loss"]) - float(g[f"tf{int(tf)}.moment"])) <= 1e-5 * abs(float(g[f"tf{int(tf)}.moment"]))
+            assert abs(float(ml["memory decoupling loss"]) - float(g[f"tf{int(tf)}.decouple"])) <= 1e-5 * abs(float(g[f"tf{int(tf)}.decouple"]))

@@ -14,6 +14,7 @@ CSRC_DIR = os.path.join(_HERE, "csrc")
 GATE_IFGO, GATE_IFOG = 0, 1
 LAYOUT_NHWC, LAYOUT_NCHW = 0, 1
 PREC_F32, PREC_BF16X3, PREC_BF16 = 0, 1, 2
+ACT_NONE, ACT_RELU = 0, 1
 FLAG_SAVE_FOR_BWD = 1
 FLAG_WEIGHTS_PACKED = 2
 FLAG_X_SPLIT = 4
@@ -46,6 +47,9 @@ EXPORTED_SYMBOLS = [
     "vpx_groupnorm_fwd", "vpx_groupnorm_bwd_workspace_bytes", "vpx_groupnorm_bwd",
     "vpx_phycell_correct_fwd", "vpx_phycell_correct_bwd", "vpx_moment_loss_fwd", "vpx_moment_loss_bwd",
     "vpx_sigmoid_head_fwd", "vpx_sigmoid_head_bwd",
+    "vpx_conv2d_act_workspace_bytes", "vpx_conv2d_act_fwd", "vpx_conv2d_act_bwd_workspace_bytes", "vpx_conv2d_act_bwd",
+    "vpx_relu_rownorm_fwd", "vpx_relu_rownorm_bwd",
+    "vpx_merge1x1_workspace_bytes", "vpx_merge1x1_fwd", "vpx_merge1x1_bwd_workspace_bytes", "vpx_merge1x1_bwd",
 ]
 
 
@@ -228,6 +232,25 @@ def lib():
             getattr(L, name).restype = ci
         L.vpx_sigmoid_head_fwd.argtypes = [vp, vp] + [ci] * 7 + [vp]
         L.vpx_sigmoid_head_bwd.argtypes = [vp, vp, vp] + [ci] * 7 + [vp]
+        for name in ("vpx_conv2d_act_workspace_bytes", "vpx_conv2d_act_bwd_workspace_bytes"):
+            getattr(L, name).restype = sz
+            getattr(L, name).argtypes = [ctypes.POINTER(ConvDesc), ci]
+        L.vpx_conv2d_act_fwd.restype = ci
+        L.vpx_conv2d_act_fwd.argtypes = [ctypes.POINTER(ConvDesc), ci] + [vp] * 4 + [vp, sz, vp]
+        L.vpx_conv2d_act_bwd.restype = ci
+        L.vpx_conv2d_act_bwd.argtypes = [ctypes.POINTER(ConvDesc), ci] + [vp] * 7 + [vp, sz, vp]
+        L.vpx_relu_rownorm_fwd.restype = ci
+        L.vpx_relu_rownorm_fwd.argtypes = [vp] * 3 + [ci] * 4 + [fl, vp]
+        L.vpx_relu_rownorm_bwd.restype = ci
+        L.vpx_relu_rownorm_bwd.argtypes = [vp] * 4 + [ci] * 4 + [fl, vp]
+        L.vpx_merge1x1_workspace_bytes.restype = sz
+        L.vpx_merge1x1_workspace_bytes.argtypes = [ci] * 3
+        L.vpx_merge1x1_fwd.restype = ci
+        L.vpx_merge1x1_fwd.argtypes = [vp] * 5 + [ci] * 7 + [vp, sz, vp]
+        L.vpx_merge1x1_bwd_workspace_bytes.restype = sz
+        L.vpx_merge1x1_bwd_workspace_bytes.argtypes = [ci] * 6
+        L.vpx_merge1x1_bwd.restype = ci
+        L.vpx_merge1x1_bwd.argtypes = [vp] * 8 + [ci] * 7 + [vp, sz, vp]
         for name in ("vpx_nchw_to_nhwc", "vpx_nhwc_to_nchw"):
             getattr(L, name).restype = ctypes.c_int
             getattr(L, name).argtypes = [vp, vp] + [ctypes.c_int] * 4 + [vp]

@@ -211,7 +211,8 @@ static int ex_mw(const vpx_conv_desc* d, int Ht, int Wt, int sd) {
 // one launch: tile space Ht x Wt, kernel taps th x tw, halo origin (oy, ox), input step `sd`
 int ex_launch(hipStream_t stream, const vpx_conv_desc* d, const float* x, const float* w, const float* bias, float* y,
               const ExGeo& g, int Ht, int Wt, int th, int tw, int sd, int oy, int ox, const int* tapmap, bool flip,
-              int omap, int oys, int oyo, int oxs, int oxo, float* wpk, char* y_split = nullptr, bool x_split = false, bool packed = false) {
+              int omap, int oys, int oyo, int oxs, int oxo, float* wpk, char* y_split = nullptr, bool x_split = false, bool packed = false,
+              int act = 0) {
     const int prec = d->precision;
     ConvPlan P{};
     int chunks = 0;
@@ -244,6 +245,7 @@ int ex_launch(hipStream_t stream, const vpx_conv_desc* d, const float* x, const 
     ea.bias = bias; ea.Co = d->Co; ea.split = d->Co; ea.ng = ng;
     ea.out0 = y; ea.bstride0 = (long long)g.Ho * g.Wo * d->Co; ea.ld0 = d->Co;
     ea.leaky = d->leaky_slope;
+    ea.relu = act == VPX_ACT_RELU ? 1 : 0;
     ea.omap = omap; ea.oys = oys; ea.oyo = oyo; ea.oxs = oxs; ea.oxo = oxo; ea.Wmem = g.Wo;
     ea.sp_out = y_split; ea.sp_bstride = (long long)g.Ho * g.Wo * d->Co * 4;
     VPX_CHECK_HIP(launch_conv_plain_f32(P, ea, pd.n_tiles, stream));
@@ -251,7 +253,7 @@ int ex_launch(hipStream_t stream, const vpx_conv_desc* d, const float* x, const 
 }
 
 int ex_forward(const vpx_conv_desc* d, const ExGeo& g, const float* x, const float* w, const float* bias, float* y, float* wpk,
-               hipStream_t stream, char* y_split = nullptr, bool x_split = false, bool packed = false);
+               hipStream_t stream, char* y_split = nullptr, bool x_split = false, bool packed = false, int act = 0);
 bool exq_problem(const vpx_conv_desc* d, const ExGeo& g, ConvQProblem& pr);
 int ex_forward_q(const vpx_conv_desc* d, const ExGeo& g, const char* x_sp, long long x_bstride, long long x_tstride, int x_nT,
                  const float* w, const float* bias, float* y, char* y_sp, char* wpk, bool weights_packed, hipStream_t stream);
@@ -302,6 +304,32 @@ int vpx_conv2d_ex_fwd(const vpx_conv_desc* d, const float* x, const float* w, co
     float* wpk = ws.take(ex_wpk_floats(d));
     VPX_CHECK_CARVE(ws, "vpx_conv2d_ex_fwd");
     return ex_forward(d, g, x, w, bias, y, wpk, (hipStream_t)stream_);
+}
+
+// activation codes beyond the descriptor's LeakyReLU: leaky_slope == 0 means "no activation" there, so ReLU travels beside it
+static int ex_act_check(const vpx_conv_desc* d, int act, const char* who) {
+    if (act != VPX_ACT_NONE && act != VPX_ACT_RELU) { set_error("%s: unknown activation code %d", who, act); return VPX_ERR_ARG; }
+    if (d && act == VPX_ACT_RELU && d->leaky_slope != 0.0f) { set_error("%s: VPX_ACT_RELU with a LeakyReLU slope in the descriptor", who); return VPX_ERR_ARG; }
+    return VPX_OK;
+}
+
+size_t vpx_conv2d_act_workspace_bytes(const vpx_conv_desc* d, int act) {
+    if (ex_act_check(d, act, "vpx_conv2d_act_workspace_bytes") != VPX_OK) return 0;
+    return vpx_conv2d_ex_workspace_bytes(d);
+}
+
+int vpx_conv2d_act_fwd(const vpx_conv_desc* d, int act, const float* x, const float* w, const float* bias, float* y, void* workspace,
+                       size_t workspace_bytes, void* stream_) {
+    ExGeo g;
+    int rc = ex_check(d, g);
+    if (rc != VPX_OK) return rc;
+    if ((rc = ex_act_check(d, act, "vpx_conv2d_act_fwd")) != VPX_OK) return rc;
+    if (!x || !w || !y) { set_error("vpx_conv2d_act_fwd: NULL tensor argument"); return VPX_ERR_ARG; }
+    if (!workspace || workspace_bytes < vpx_conv2d_ex_workspace_bytes(d)) { set_error("vpx_conv2d_act_fwd: workspace too small"); return VPX_ERR_WORKSPACE; }
+    Carver ws(workspace, workspace_bytes);
+    float* wpk = ws.take(ex_wpk_floats(d));
+    VPX_CHECK_CARVE(ws, "vpx_conv2d_act_fwd");
+    return ex_forward(d, g, x, w, bias, y, wpk, (hipStream_t)stream_, nullptr, false, false, act);
 }
 
 int vpx_conv2d_ex_fwd_split(const vpx_conv_desc* d, const float* x, const float* w, const float* bias, float* y, void* y_split,
@@ -392,9 +420,9 @@ namespace {
 // packed: the workspace still holds the layer's packed weights — honoured by the single-launch forms (the four phase launches of a
 // stride-2 transposed layer pack into the same space one after the other)
 int ex_forward(const vpx_conv_desc* d, const ExGeo& g, const float* x, const float* w, const float* bias, float* y, float* wpk,
-               hipStream_t stream, char* y_split, bool x_split, bool packed) {
+               hipStream_t stream, char* y_split, bool x_split, bool packed, int act) {
     int rc;
-    const int small_kind = x_split ? 0 : conv_small_kind(d);   // (the streaming kernels read fp32)
+    const int small_kind = (x_split || act) ? 0 : conv_small_kind(d);   // (the streaming kernels read fp32 and know LeakyReLU only)
     if (const int kind = small_kind) {   // few-channel layers: streaming kernels (conv_small.hip)
         if (kind != 2 || !y_split) {
             VPX_CHECK_HIP(launch_conv_small(d, kind, x, w, bias, y, y_split, stream));
@@ -403,10 +431,10 @@ int ex_forward(const vpx_conv_desc* d, const ExGeo& g, const float* x, const flo
     }
     if (!d->transposed)  // y[o] = sum_k x[o*s - pad + k] w[k]
         return ex_launch(stream, d, x, w, bias, y, g, g.Ho, g.Wo, d->kh, d->kw, d->stride, -d->pad, -d->pad, nullptr, false,
-                         0, 1, 0, 1, 0, wpk, y_split, x_split, packed);
+                         0, 1, 0, 1, 0, wpk, y_split, x_split, packed, act);
     if (d->stride == 1)  // y[o] = sum_k x[o + pad - k] w[k]  ==  correlation with the flipped kernel, origin -(k-1-pad)
         return ex_launch(stream, d, x, w, bias, y, g, g.Ho, g.Wo, d->kh, d->kw, 1, -(d->kh - 1 - d->pad), -(d->kw - 1 - d->pad),
-                         nullptr, true, 0, 1, 0, 1, 0, wpk, y_split, x_split, packed);
+                         nullptr, true, 0, 1, 0, 1, 0, wpk, y_split, x_split, packed, act);
     // stride 2: output phase (py, px) is a stride-1 correlation of x with the taps k == (p + pad) mod 2 of that axis
     for (int py = 0; py < 2; ++py)
         for (int px = 0; px < 2; ++px) {
@@ -425,7 +453,7 @@ int ex_forward(const vpx_conv_desc* d, const ExGeo& g, const float* x, const flo
                 for (int tx = 0; tx < ntx; ++tx)
                     tapmap[ty * ntx + tx] = (ky0 + 2 * (nty - 1 - ty)) * d->kw + (kx0 + 2 * (ntx - 1 - tx));
             rc = ex_launch(stream, d, x, w, bias, y, g, Ht, Wt, nty, ntx, 1, basey - (nty - 1), basex - (ntx - 1), tapmap, false,
-                           1, 2, py, 2, px, wpk, y_split, x_split);
+                           1, 2, py, 2, px, wpk, y_split, x_split, false, act);
             if (rc != VPX_OK) return rc;
         }
     return VPX_OK;
@@ -658,16 +686,38 @@ int vpx_conv2d_ex_bwd(const vpx_conv_desc* d, const float* x, const float* w, co
     return vpx_conv2d_ex_bwd_ex(d, x, nullptr, w, y, dy, dx, dw, db, workspace, workspace_bytes, stream_);
 }
 
+static int ex_bwd_impl(const char* who, const vpx_conv_desc* d, int act, const float* x, const void* x_split, const float* w, const float* y,
+                       const float* dy, float* dx, float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream_);
+
 int vpx_conv2d_ex_bwd_ex(const vpx_conv_desc* d, const float* x, const void* x_split, const float* w, const float* y, const float* dy, float* dx,
                          float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream_) {
+    return ex_bwd_impl("vpx_conv2d_ex_bwd", d, VPX_ACT_NONE, x, x_split, w, y, dy, dx, dw, db, workspace, workspace_bytes, stream_);
+}
+
+size_t vpx_conv2d_act_bwd_workspace_bytes(const vpx_conv_desc* d, int act) {
+    if (ex_act_check(d, act, "vpx_conv2d_act_bwd_workspace_bytes") != VPX_OK) return 0;
+    return vpx_conv2d_ex_bwd_workspace_bytes(d);
+}
+
+/* ReLU' is read off the saved output (y > 0: zero at y == 0, as torch's threshold backward for finite dy) in the pass that sums the bias
+ * gradient. That pass multiplies dy by the 0 / 1 derivative (launch_colsum, shared with LeakyReLU): a non-finite dy at a dead unit
+ * gives NaN where torch's select gives 0. */
+int vpx_conv2d_act_bwd(const vpx_conv_desc* d, int act, const float* x, const float* w, const float* y, const float* dy, float* dx, float* dw,
+                       float* db, void* workspace, size_t workspace_bytes, void* stream_) {
+    if (int rc = ex_act_check(d, act, "vpx_conv2d_act_bwd")) return rc;
+    return ex_bwd_impl("vpx_conv2d_act_bwd", d, act, x, nullptr, w, y, dy, dx, dw, db, workspace, workspace_bytes, stream_);
+}
+
+static int ex_bwd_impl(const char* who, const vpx_conv_desc* d, int act, const float* x, const void* x_split, const float* w, const float* y,
+                       const float* dy, float* dx, float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream_) {
     ExGeo g;
     int rc = ex_check(d, g);
     if (rc != VPX_OK) return rc;
     vpx_conv_desc a;
     if ((rc = ex_adjoint(d, g, a)) != VPX_OK) return rc;
-    if (d->kh < d->stride || d->kw < d->stride) { set_error("vpx_conv2d_ex_bwd: kernel smaller than the stride"); return VPX_ERR_UNSUPPORTED; }
-    if (!x || !w || !dy) { set_error("vpx_conv2d_ex_bwd: NULL tensor argument"); return VPX_ERR_ARG; }
-    if (!workspace || workspace_bytes < vpx_conv2d_ex_bwd_workspace_bytes(d)) { set_error("vpx_conv2d_ex_bwd: workspace too small"); return VPX_ERR_WORKSPACE; }
+    if (d->kh < d->stride || d->kw < d->stride) { set_error("%s: kernel smaller than the stride", who); return VPX_ERR_UNSUPPORTED; }
+    if (!x || !w || !dy) { set_error("%s: NULL tensor argument", who); return VPX_ERR_ARG; }
+    if (!workspace || workspace_bytes < vpx_conv2d_ex_bwd_workspace_bytes(d)) { set_error("%s: workspace too small", who); return VPX_ERR_WORKSPACE; }
     hipStream_t stream = (hipStream_t)stream_;
     Carver ws(workspace, workspace_bytes);
     float* wpk = ws.take(ex_wpk_floats(&a));
@@ -682,14 +732,14 @@ int vpx_conv2d_ex_bwd_ex(const vpx_conv_desc* d, const float* x, const void* x_s
     const bool wsp = dw && ex_wgrad_split(d);
     char* x_sp = nullptr;
     if (wsp) { if (!dy_sp) dy_sp = (char*)ws.take(n_dy); x_sp = (char*)ws.take((size_t)d->N * d->H * d->W * d->Ci); }
-    VPX_CHECK_CARVE(ws, "vpx_conv2d_ex_bwd");
+    VPX_CHECK_CARVE(ws, who);
     const bool v4 = (d->Co & 3) == 0 && (((uintptr_t)dy | (uintptr_t)y) & 15) == 0;   // (launch_colsum's vector form: the split copy needs it)
     bool have_sp = false;
-    if (d->leaky_slope != 0.0f) {
+    if (d->leaky_slope != 0.0f || act == VPX_ACT_RELU) {
         // d(pre-activation) = dy * LeakyReLU'(.), the derivative read off the sign of the forward OUTPUT (same sign as the
         // pre-activation for a positive slope) — one pass that also yields the bias gradient
-        if (!y) { set_error("vpx_conv2d_ex_bwd: y (forward output) is required when leaky_slope != 0"); return VPX_ERR_ARG; }
-        if (d->leaky_slope < 0.0f) { set_error("vpx_conv2d_ex_bwd: negative leaky_slope is not implemented"); return VPX_ERR_UNSUPPORTED; }
+        if (!y) { set_error("%s: y (forward output) is required when the layer has an activation", who); return VPX_ERR_ARG; }
+        if (d->leaky_slope < 0.0f) { set_error("%s: negative leaky_slope is not implemented", who); return VPX_ERR_UNSUPPORTED; }
         have_sp = (dq || wsp) && v4;
         VPX_CHECK_HIP(launch_colsum(dy, y, d->leaky_slope, dys, db, db_part, (long long)d->N * g.Ho * g.Wo, d->Co, stream, have_sp ? dy_sp : nullptr));
         dy = dys;

@@ -271,6 +271,7 @@ struct EpiPlain {
                 }
                 if (a.accumulate) v += *p;   // the activation applies to the completed sum (two convolutions into one output)
                 if (a.leaky != 0.0f) v = v > 0.0f ? v : v * a.leaky;
+                if (a.relu) v = v > 0.0f ? v : 0.0f;
                 if (p) *p = v;
                 if (a.sp_out) {
                     unsigned short h16, l16;
@@ -743,7 +744,7 @@ hipError_t launch_conv_plain_f32(const ConvPlan& plan_in, const PlainEpiArgs& ea
     ConvPlan plan = plan_in;
     PlainEpiArgs ea = ea_in;
     plan.ksplit = ea.ksplit = (plan.ksplit > 1 && plan.ksplit <= plan.nstage) ? plan.ksplit : 0;
-    if (plan.ksplit > 1 && ea.leaky != 0.0f) return hipErrorInvalidValue;  // partial sums cannot be activated
+    if (plan.ksplit > 1 && (ea.leaky != 0.0f || ea.relu)) return hipErrorInvalidValue;  // partial sums cannot be activated
     switch (ea.ng) {
         case 1: return launch_conv(plan, EpiPlain<1>{ea}, n_tiles, s);
         case 2: return launch_conv(plan, EpiPlain<2>{ea}, n_tiles, s);

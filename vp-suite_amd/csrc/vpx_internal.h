@@ -336,6 +336,7 @@ struct PlainEpiArgs {
     int oys, oyo, oxs, oxo, Wmem;
     char* sp_out;             // optional: the output AGAIN in split-bf16 operand format (cell2.hip; [pixel][Co/8][hi 8 | lo 8]) —
     long long sp_bstride;     //   BYTES between batch items; out0 may then be null (inference: the fp32 copy is never read)
+    int relu;                 // 1: ReLU after the bias (vpx_conv2d_act_fwd; `leaky` is 0 then: a slope of 0 means "no activation" there)
 };
 hipError_t launch_conv_plain_f32(const ConvPlan& plan, const PlainEpiArgs& ea, int n_tiles, hipStream_t s);
 // N tiling of a plain convolution with Co outputs: ng = 1..4 groups of 32 channels per workgroup, chosen to minimise

@@ -3,11 +3,13 @@ from .ef_conv_lstm import EF_ConvLSTM, Encoder_Forecaster  # noqa: F401
 from .ef_traj_gru import EF_TrajGRU  # noqa: F401
 from .phydnet import PhyDNet  # noqa: F401
 from .predrnn_v2 import PredRNN_V2  # noqa: F401
+from .st_phy import STPhy  # noqa: F401
 
 MODEL_CLASSES = {
     "convlstm-shi": EF_ConvLSTM,
     "predrnn-pp": PredRNN_V2,
     "trajgru": EF_TrajGRU,
     "phy": PhyDNet,
+    "st-phy": STPhy,
 }
 AVAILABLE_MODELS = MODEL_CLASSES.keys()
