@@ -27,6 +27,22 @@ def test_library_exports_every_declared_symbol(vpx):
     assert L.vpx_version() == 100
 
 
+def test_binding_argument_counts_match_the_header(vpx):
+    """Every prototype of include/vpx.h has as many parameters as the bound function has argtypes (`(void)` = none): a miscounted
+    ctypes argument list would hand a launcher garbage without any error."""
+    hdr = open(os.path.join(ROOT, "include", "vpx.h")).read()
+    declared = set(re.findall(r"\b(vpx_[a-z0-9_]+)\s*\(", hdr))
+    code = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    protos = re.findall(r"\b(vpx_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", code)
+    assert len(protos) == len(declared) and {name for name, _ in protos} == declared
+    L = vpx._lib.lib()
+    for name, params in protos:
+        n = 0 if params.strip() in ("", "void") else params.count(",") + 1
+        fn = getattr(L, name)
+        assert fn.argtypes is not None and fn.restype is not None, f"{name}: restype / argtypes not set"
+        assert len(fn.argtypes) == n, f"{name}: {n} parameters in include/vpx.h, {len(fn.argtypes)} argtypes in _lib.py"
+
+
 def test_workspace_queries_run_without_gpu(vpx):
     L = vpx._lib.lib()
     d = vpx._lib.ConvLSTMDesc(4, 10, 64, 64, 64, 64, 3, 3, 0, 0, 0, 1)

@@ -26,33 +26,6 @@ OPT_EXPERIMENT = 4
 OPT_DRY_RUN = 5      # host-side work only, no HIP call (tests/test_workspace_contract.py)
 OPT_MFMA_SHAPE = 3   # 0: v_mfma_f32_32x32x16_bf16, 1: v_mfma_f32_16x16x32_bf16 in the second-generation kernels' main loop
 
-EXPORTED_SYMBOLS = [
-    "vpx_version", "vpx_last_error", "vpx_set_deterministic", "vpx_set_option", "vpx_option_epoch",
-    "vpx_convlstm_workspace_bytes", "vpx_convlstm_reserve_bytes", "vpx_convlstm_takes_split_input", "vpx_convlstm_writes_split_output", "vpx_convlstm_seq_fwd",
-    "vpx_convlstm_seq_bwd",
-    "vpx_stlstm_workspace_bytes", "vpx_stlstm_reserve_bytes", "vpx_stlstm_step_fwd", "vpx_stlstm_step_bwd",
-    "vpx_stlstm_uses_split", "vpx_stlstm_step_fwd_ex", "vpx_stlstm_step_bwd_ex",
-    "vpx_stlstm_defers_wgrad", "vpx_stlstm_wgrad_batch_workspace_bytes", "vpx_stlstm_wgrad_batch",
-    "vpx_decouple_workspace_bytes", "vpx_decouple_fwd", "vpx_decouple_bwd",
-    "vpx_conv2d_workspace_bytes", "vpx_conv2d_nhwc_fwd", "vpx_conv2d_bwd_workspace_bytes", "vpx_conv2d_nhwc_bwd",
-    "vpx_conv2d_ex_out_shape", "vpx_conv2d_ex_workspace_bytes", "vpx_conv2d_ex_fwd", "vpx_conv2d_ex_fwd_split",
-    "vpx_conv2d_ex_takes_split", "vpx_split_convert", "vpx_conv2d_ex_split_workspace_bytes", "vpx_conv2d_ex_fwd_from_split",
-    "vpx_conv2d_ex_bwd_workspace_bytes", "vpx_conv2d_ex_bwd", "vpx_conv2d_ex_bwd_uses_split", "vpx_conv2d_ex_bwd_ex",
-    "vpx_conv2d_nhwc_fwd_ex",
-    "vpx_acstlstm_workspace_bytes", "vpx_acstlstm_reserve_bytes", "vpx_acstlstm_step_fwd", "vpx_acstlstm_step_bwd",
-    "vpx_trajgru_workspace_bytes", "vpx_trajgru_reserve_bytes", "vpx_trajgru_seq_fwd", "vpx_trajgru_seq_bwd",
-    "vpx_nchw_to_nhwc", "vpx_nhwc_to_nchw",
-    "vpx_layernorm_workspace_bytes", "vpx_layernorm_fwd", "vpx_layernorm_bwd",
-    "vpx_mse_loss_workspace_bytes", "vpx_mse_loss", "vpx_adam_step",
-    "vpx_groupnorm_fwd", "vpx_groupnorm_bwd_workspace_bytes", "vpx_groupnorm_bwd",
-    "vpx_phycell_correct_fwd", "vpx_phycell_correct_bwd", "vpx_moment_loss_fwd", "vpx_moment_loss_bwd",
-    "vpx_sigmoid_head_fwd", "vpx_sigmoid_head_bwd",
-    "vpx_conv2d_act_workspace_bytes", "vpx_conv2d_act_fwd", "vpx_conv2d_act_bwd_workspace_bytes", "vpx_conv2d_act_bwd",
-    "vpx_relu_rownorm_fwd", "vpx_relu_rownorm_bwd",
-    "vpx_merge1x1_workspace_bytes", "vpx_merge1x1_fwd", "vpx_merge1x1_bwd_workspace_bytes", "vpx_merge1x1_bwd",
-]
-
-
 class ConvLSTMDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("B", "T", "Cin", "Ch", "H", "W", "kh", "kw", "gate_order", "layout",
                                               "precision", "flags")]
@@ -86,6 +59,110 @@ class VpxError(RuntimeError):
     pass
 
 
+# ---- the C ABI, once: name -> (restype, argtypes), one entry per function of include/vpx.h, grouped and ordered as the header is.
+#      tests/test_host_logic.py holds every entry's argument count against the header's prototype. ----
+vp, sz, ci, ll, fl, dbl = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_double
+_clstm, _stlstm, _conv, _acst, _traj = (ctypes.POINTER(D) for D in (ConvLSTMDesc, STLSTMDesc, ConvDesc, ACSTLSTMDesc, TrajGRUDesc))
+_int_p = ctypes.POINTER(ci)
+_ws = [vp, sz, vp]           # void* workspace, size_t workspace_bytes, void* stream
+_rs_ws = [vp, sz] + _ws      # void* reserve, size_t reserve_bytes, then the workspace and the stream
+_stlstm_fwd = [_stlstm] + [vp] * 4 + [vp] * 5 + [vp] + [vp] * 5 + _rs_ws                                  # x h c m | 5 weights | ln | 5 outputs
+_stlstm_bwd = [_stlstm] + [vp] * 6 + [vp] * 5 + [vp] + [vp, sz] + [vp] * 5 + [vp] * 4 + [vp] * 5 + [vp] + _ws
+#             x h c m c_new m_new | 5 weights | ln | reserve | 5 incoming gradients | dx dh dc dm | 5 weight gradients | dln
+
+SIGNATURES = {
+    "vpx_version": (ci, []),
+    "vpx_last_error": (ctypes.c_char_p, []),
+    "vpx_set_deterministic": (ci, [ci]),
+    "vpx_set_option": (ci, [ci, ci]),
+    "vpx_option_epoch": (ci, []),
+    # ConvLSTM over a sequence
+    "vpx_convlstm_workspace_bytes": (sz, [_clstm]),
+    "vpx_convlstm_takes_split_input": (ci, [_clstm]),
+    "vpx_convlstm_writes_split_output": (ci, [_clstm]),
+    "vpx_convlstm_reserve_bytes": (sz, [_clstm]),
+    "vpx_convlstm_seq_fwd": (ci, [_clstm] + [vp] * 8 + [vp] * 3 + _rs_ws),                     # x h0 c0 W bias Wci Wcf Wco | out hT cT
+    "vpx_convlstm_seq_bwd": (ci, [_clstm] + [vp] * 8 + [vp, sz] + [vp] * 3 + [vp] * 8 + _ws),  # x h0 c0 W Wci Wcf Wco out | reserve | dout dhT dcT | 8 gradients
+    # ST-LSTM cell step
+    "vpx_stlstm_workspace_bytes": (sz, [_stlstm]),
+    "vpx_stlstm_reserve_bytes": (sz, [_stlstm]),
+    "vpx_stlstm_uses_split": (ci, [_stlstm]),
+    "vpx_stlstm_defers_wgrad": (ci, [_stlstm]),
+    "vpx_stlstm_wgrad_batch_workspace_bytes": (sz, [_stlstm]),
+    "vpx_stlstm_wgrad_batch": (ci, [_stlstm, vp, vp] + [vp] * 5 + _ws),
+    "vpx_stlstm_step_fwd": (ci, _stlstm_fwd),
+    "vpx_stlstm_step_bwd": (ci, _stlstm_bwd),
+    "vpx_stlstm_step_fwd_ex": (ci, _stlstm_fwd + [ctypes.POINTER(STLSTMShadows)]),
+    "vpx_stlstm_step_bwd_ex": (ci, _stlstm_bwd + [ctypes.POINTER(STLSTMShadows)]),
+    # decoupling-loss term
+    "vpx_decouple_workspace_bytes": (sz, [ci] * 4),
+    "vpx_decouple_fwd": (ci, [vp] * 4 + [ci] * 5 + _ws),
+    "vpx_decouple_bwd": (ci, [vp] * 7 + [ci] * 5 + _ws),
+    # training tail
+    "vpx_mse_loss_workspace_bytes": (sz, []),
+    "vpx_mse_loss": (ci, [vp, vp, ll, ll, fl, vp, vp] + _ws),
+    "vpx_adam_step": (ci, [vp] * 4 + [ll] + [dbl] * 5 + [ci, dbl, vp]),
+    # plain stride-1 "same" convolution
+    "vpx_conv2d_workspace_bytes": (sz, [ci] * 4),
+    "vpx_conv2d_nhwc_fwd": (ci, [vp] * 4 + [ci] * 8 + _ws),
+    "vpx_conv2d_bwd_workspace_bytes": (sz, [ci] * 7),
+    "vpx_conv2d_nhwc_bwd": (ci, [vp] * 6 + [ci] * 8 + _ws),
+    # general convolution / transposed convolution + bias + LeakyReLU (stage glue)
+    "vpx_conv2d_ex_out_shape": (ci, [_conv, _int_p, _int_p]),
+    "vpx_conv2d_ex_workspace_bytes": (sz, [_conv]),
+    "vpx_conv2d_ex_fwd": (ci, [_conv] + [vp] * 4 + _ws),
+    "vpx_conv2d_ex_fwd_split": (ci, [_conv] + [vp] * 5 + _ws),
+    "vpx_conv2d_ex_takes_split": (ci, [_conv]),
+    "vpx_split_convert": (ci, [vp, vp, ll, ci, vp]),
+    "vpx_conv2d_ex_split_workspace_bytes": (sz, [_conv]),
+    "vpx_conv2d_ex_fwd_from_split": (ci, [_conv, vp, ll, ll, ci, vp, vp, vp, vp, ci] + _ws),
+    "vpx_conv2d_ex_bwd_workspace_bytes": (sz, [_conv]),
+    "vpx_conv2d_ex_bwd": (ci, [_conv] + [vp] * 7 + _ws),
+    "vpx_conv2d_ex_bwd_uses_split": (ci, [_conv]),
+    "vpx_conv2d_ex_bwd_ex": (ci, [_conv] + [vp] * 8 + _ws),
+    "vpx_conv2d_nhwc_fwd_ex": (ci, [vp] * 4 + [ci] * 9 + [fl] + _ws),
+    # TrajGRU over a sequence
+    "vpx_trajgru_workspace_bytes": (sz, [_traj]),
+    "vpx_trajgru_reserve_bytes": (sz, [_traj]),
+    "vpx_trajgru_seq_fwd": (ci, [_traj, vp, vp, vp, vp] + _rs_ws),
+    "vpx_trajgru_seq_bwd": (ci, [_traj, vp, vp, vp, vp, vp, sz] + [vp] * 5 + _ws),
+    # action-conditional ST-LSTM cell step
+    "vpx_acstlstm_workspace_bytes": (sz, [_acst]),
+    "vpx_acstlstm_reserve_bytes": (sz, [_acst]),
+    "vpx_acstlstm_step_fwd": (ci, [_acst] + [vp] * 5 + [vp, vp] + [vp] * 5 + _rs_ws),                              # x h c m a | params ln | 5 outputs
+    "vpx_acstlstm_step_bwd": (ci, [_acst] + [vp] * 5 + [vp, vp] + [vp, sz] + [vp] * 5 + [vp] * 5 + [vp, vp] + _ws),  # ... | reserve | 5 incoming | dx dh dc dm da | dparams dln
+    # LayerNorm([C,H,W])
+    "vpx_layernorm_workspace_bytes": (sz, [ci]),
+    "vpx_layernorm_fwd": (ci, [vp] * 6 + [ci, ll] + _ws),
+    "vpx_layernorm_bwd": (ci, [vp] * 7 + [ci, ci, ci] + _ws),
+    # GroupNorm
+    "vpx_groupnorm_fwd": (ci, [vp] * 6 + [ci] * 5 + [fl, vp]),
+    "vpx_groupnorm_bwd_workspace_bytes": (sz, [ci, ci]),
+    "vpx_groupnorm_bwd": (ci, [vp] * 8 + [ci] * 5 + [fl] + _ws),
+    # PhyDNet
+    "vpx_phycell_correct_fwd": (ci, [vp] * 5 + [ll, vp]),
+    "vpx_phycell_correct_bwd": (ci, [vp] * 9 + [ll, vp]),
+    "vpx_moment_loss_fwd": (ci, [vp, vp] + [ci] * 4 + [fl, vp]),
+    "vpx_moment_loss_bwd": (ci, [vp, vp, vp] + [ci] * 4 + [fl, vp]),
+    "vpx_sigmoid_head_fwd": (ci, [vp, vp] + [ci] * 7 + [vp]),
+    "vpx_sigmoid_head_bwd": (ci, [vp, vp, vp] + [ci] * 7 + [vp]),
+    # ST-Phy
+    "vpx_conv2d_act_workspace_bytes": (sz, [_conv, ci]),
+    "vpx_conv2d_act_fwd": (ci, [_conv, ci] + [vp] * 4 + _ws),
+    "vpx_conv2d_act_bwd_workspace_bytes": (sz, [_conv, ci]),
+    "vpx_conv2d_act_bwd": (ci, [_conv, ci] + [vp] * 7 + _ws),
+    "vpx_relu_rownorm_fwd": (ci, [vp] * 3 + [ci] * 4 + [fl, vp]),
+    "vpx_relu_rownorm_bwd": (ci, [vp] * 4 + [ci] * 4 + [fl, vp]),
+    "vpx_merge1x1_workspace_bytes": (sz, [ci] * 3),
+    "vpx_merge1x1_fwd": (ci, [vp] * 5 + [ci] * 7 + _ws),
+    "vpx_merge1x1_bwd_workspace_bytes": (sz, [ci] * 6),
+    "vpx_merge1x1_bwd": (ci, [vp] * 8 + [ci] * 7 + _ws),
+    # layout adaptors
+    "vpx_nchw_to_nhwc": (ci, [vp, vp] + [ci] * 4 + [vp]),
+    "vpx_nhwc_to_nchw": (ci, [vp, vp] + [ci] * 4 + [vp]),
+}
+EXPORTED_SYMBOLS = list(SIGNATURES)
+
 _lib = None
 
 
@@ -107,153 +184,9 @@ def lib():
             raise VpxError(f"HIP extension not built: {LIB_PATH} is missing (run `python -c 'import __graft_entry__ as g; "
                            f"g.build()'` or `make -C {CSRC_DIR}`). There is no CPU fallback.")
         L = ctypes.CDLL(LIB_PATH)
-        vp = ctypes.c_void_p
-        sz = ctypes.c_size_t
-        L.vpx_version.restype = ctypes.c_int
-        L.vpx_last_error.restype = ctypes.c_char_p
-        L.vpx_set_deterministic.restype = ctypes.c_int
-        L.vpx_set_deterministic.argtypes = [ctypes.c_int]
-        L.vpx_option_epoch.restype = ctypes.c_int
-        L.vpx_option_epoch.argtypes = []
-        L.vpx_set_option.restype = ctypes.c_int
-        L.vpx_set_option.argtypes = [ctypes.c_int, ctypes.c_int]
-        for name in ("vpx_convlstm_workspace_bytes", "vpx_convlstm_reserve_bytes"):
-            getattr(L, name).restype = sz
-            getattr(L, name).argtypes = [ctypes.POINTER(ConvLSTMDesc)]
-        for name in ("vpx_stlstm_workspace_bytes", "vpx_stlstm_reserve_bytes"):
-            getattr(L, name).restype = sz
-            getattr(L, name).argtypes = [ctypes.POINTER(STLSTMDesc)]
-        L.vpx_convlstm_takes_split_input.restype = ctypes.c_int
-        L.vpx_convlstm_takes_split_input.argtypes = [ctypes.POINTER(ConvLSTMDesc)]
-        L.vpx_convlstm_writes_split_output.restype = ctypes.c_int
-        L.vpx_convlstm_writes_split_output.argtypes = [ctypes.POINTER(ConvLSTMDesc)]
-        L.vpx_convlstm_seq_fwd.restype = ctypes.c_int
-        L.vpx_convlstm_seq_fwd.argtypes = [ctypes.POINTER(ConvLSTMDesc)] + [vp] * 11 + [vp, sz, vp, sz, vp]
-        L.vpx_convlstm_seq_bwd.restype = ctypes.c_int
-        L.vpx_convlstm_seq_bwd.argtypes = [ctypes.POINTER(ConvLSTMDesc)] + [vp] * 8 + [vp, sz] + [vp] * 11 + [vp, sz, vp]
-        L.vpx_stlstm_uses_split.restype = ctypes.c_int
-        L.vpx_stlstm_uses_split.argtypes = [ctypes.POINTER(STLSTMDesc)]
-        L.vpx_stlstm_step_fwd.restype = ctypes.c_int
-        L.vpx_stlstm_step_fwd.argtypes = [ctypes.POINTER(STLSTMDesc)] + [vp] * 9 + [vp] + [vp] * 5 + [vp, sz, vp, sz, vp]
-        L.vpx_stlstm_step_bwd.restype = ctypes.c_int
-        L.vpx_stlstm_step_bwd.argtypes = [ctypes.POINTER(STLSTMDesc)] + [vp] * 11 + [vp] + [vp, sz] + [vp] * 5 + [vp] * 9 + [vp] + [vp, sz, vp]
-        L.vpx_stlstm_defers_wgrad.restype = ctypes.c_int
-        L.vpx_stlstm_defers_wgrad.argtypes = [ctypes.POINTER(STLSTMDesc)]
-        L.vpx_stlstm_wgrad_batch_workspace_bytes.restype = sz
-        L.vpx_stlstm_wgrad_batch_workspace_bytes.argtypes = [ctypes.POINTER(STLSTMDesc)]
-        L.vpx_stlstm_wgrad_batch.restype = ctypes.c_int
-        L.vpx_stlstm_wgrad_batch.argtypes = [ctypes.POINTER(STLSTMDesc), vp, vp] + [vp] * 5 + [vp, sz, vp]
-        L.vpx_stlstm_step_fwd_ex.restype = ctypes.c_int
-        L.vpx_stlstm_step_fwd_ex.argtypes = L.vpx_stlstm_step_fwd.argtypes + [ctypes.POINTER(STLSTMShadows)]
-        L.vpx_stlstm_step_bwd_ex.restype = ctypes.c_int
-        L.vpx_stlstm_step_bwd_ex.argtypes = L.vpx_stlstm_step_bwd.argtypes + [ctypes.POINTER(STLSTMShadows)]
-        L.vpx_decouple_workspace_bytes.restype = sz
-        L.vpx_decouple_workspace_bytes.argtypes = [ctypes.c_int] * 4
-        L.vpx_decouple_fwd.restype = ctypes.c_int
-        L.vpx_decouple_fwd.argtypes = [vp] * 4 + [ctypes.c_int] * 5 + [vp, sz, vp]
-        L.vpx_decouple_bwd.restype = ctypes.c_int
-        L.vpx_decouple_bwd.argtypes = [vp] * 7 + [ctypes.c_int] * 5 + [vp, sz, vp]
-        L.vpx_conv2d_workspace_bytes.restype = sz
-        L.vpx_conv2d_workspace_bytes.argtypes = [ctypes.c_int] * 4
-        L.vpx_conv2d_nhwc_fwd.restype = ctypes.c_int
-        L.vpx_conv2d_nhwc_fwd.argtypes = [vp] * 4 + [ctypes.c_int] * 8 + [vp, sz, vp]
-        L.vpx_conv2d_bwd_workspace_bytes.restype = sz
-        L.vpx_conv2d_bwd_workspace_bytes.argtypes = [ctypes.c_int] * 7
-        L.vpx_conv2d_nhwc_bwd.restype = ctypes.c_int
-        L.vpx_conv2d_nhwc_bwd.argtypes = [vp] * 6 + [ctypes.c_int] * 8 + [vp, sz, vp]
-        L.vpx_conv2d_ex_out_shape.restype = ctypes.c_int
-        L.vpx_conv2d_ex_out_shape.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-        L.vpx_conv2d_ex_workspace_bytes.restype = sz
-        L.vpx_conv2d_ex_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc)]
-        L.vpx_conv2d_ex_fwd.restype = ctypes.c_int
-        L.vpx_conv2d_ex_fwd.argtypes = [ctypes.POINTER(ConvDesc)] + [vp] * 4 + [vp, sz, vp]
-        L.vpx_conv2d_ex_bwd_workspace_bytes.restype = sz
-        L.vpx_conv2d_ex_bwd_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc)]
-        L.vpx_conv2d_ex_bwd.restype = ctypes.c_int
-        L.vpx_conv2d_ex_bwd.argtypes = [ctypes.POINTER(ConvDesc)] + [vp] * 7 + [vp, sz, vp]
-        L.vpx_conv2d_ex_bwd_uses_split.restype = ctypes.c_int
-        L.vpx_conv2d_ex_bwd_uses_split.argtypes = [ctypes.POINTER(ConvDesc)]
-        L.vpx_conv2d_ex_bwd_ex.restype = ctypes.c_int
-        L.vpx_conv2d_ex_bwd_ex.argtypes = [ctypes.POINTER(ConvDesc)] + [vp] * 8 + [vp, sz, vp]
-        ll, fl, ci = ctypes.c_longlong, ctypes.c_float, ctypes.c_int
-        L.vpx_conv2d_nhwc_fwd_ex.restype = ci
-        L.vpx_conv2d_nhwc_fwd_ex.argtypes = [vp] * 4 + [ci] * 9 + [fl, vp, sz, vp]
-        for name in ("vpx_acstlstm_workspace_bytes", "vpx_acstlstm_reserve_bytes"):
-            getattr(L, name).restype = sz
-            getattr(L, name).argtypes = [ctypes.POINTER(ACSTLSTMDesc)]
-        L.vpx_acstlstm_step_fwd.restype = ci
-        L.vpx_acstlstm_step_fwd.argtypes = [ctypes.POINTER(ACSTLSTMDesc)] + [vp] * 12 + [vp, sz, vp, sz, vp]
-        L.vpx_acstlstm_step_bwd.restype = ci
-        L.vpx_acstlstm_step_bwd.argtypes = [ctypes.POINTER(ACSTLSTMDesc)] + [vp] * 7 + [vp, sz] + [vp] * 12 + [vp, sz, vp]
-        for name in ("vpx_trajgru_workspace_bytes", "vpx_trajgru_reserve_bytes"):
-            getattr(L, name).restype = sz
-            getattr(L, name).argtypes = [ctypes.POINTER(TrajGRUDesc)]
-        L.vpx_trajgru_seq_fwd.restype = ci
-        L.vpx_trajgru_seq_fwd.argtypes = [ctypes.POINTER(TrajGRUDesc), vp, vp, vp, vp, vp, sz, vp, sz, vp]
-        L.vpx_trajgru_seq_bwd.restype = ci
-        L.vpx_trajgru_seq_bwd.argtypes = [ctypes.POINTER(TrajGRUDesc), vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp]
-        L.vpx_conv2d_ex_fwd_split.restype = ci
-        L.vpx_conv2d_ex_fwd_split.argtypes = [ctypes.POINTER(ConvDesc)] + [vp] * 5 + [vp, sz, vp]
-        L.vpx_conv2d_ex_takes_split.restype = ci
-        L.vpx_conv2d_ex_takes_split.argtypes = [ctypes.POINTER(ConvDesc)]
-        L.vpx_split_convert.restype = ci
-        L.vpx_split_convert.argtypes = [vp, vp, ll, ci, vp]
-        L.vpx_conv2d_ex_split_workspace_bytes.restype = sz
-        L.vpx_conv2d_ex_split_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc)]
-        L.vpx_conv2d_ex_fwd_from_split.restype = ci
-        L.vpx_conv2d_ex_fwd_from_split.argtypes = [ctypes.POINTER(ConvDesc), vp, ll, ll, ci, vp, vp, vp, vp, ci, vp, sz, vp]
-        L.vpx_layernorm_workspace_bytes.restype = sz
-        L.vpx_layernorm_workspace_bytes.argtypes = [ci]
-        L.vpx_layernorm_fwd.restype = ci
-        L.vpx_layernorm_fwd.argtypes = [vp] * 6 + [ci, ll, vp, sz, vp]
-        L.vpx_layernorm_bwd.restype = ci
-        L.vpx_layernorm_bwd.argtypes = [vp] * 7 + [ci, ci, ci, vp, sz, vp]
-        L.vpx_mse_loss_workspace_bytes.restype = sz
-        L.vpx_mse_loss_workspace_bytes.argtypes = []
-        L.vpx_mse_loss.restype = ctypes.c_int
-        L.vpx_mse_loss.argtypes = [vp, vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_float, vp, vp, vp, sz, vp]
-        L.vpx_adam_step.restype = ctypes.c_int
-        L.vpx_adam_step.argtypes = [vp] * 4 + [ctypes.c_longlong] + [ctypes.c_double] * 5 + [ctypes.c_int, ctypes.c_double, vp]
-        L.vpx_groupnorm_fwd.restype = ci
-        L.vpx_groupnorm_fwd.argtypes = [vp] * 6 + [ci] * 5 + [fl, vp]
-        L.vpx_groupnorm_bwd_workspace_bytes.restype = sz
-        L.vpx_groupnorm_bwd_workspace_bytes.argtypes = [ci, ci]
-        L.vpx_groupnorm_bwd.restype = ci
-        L.vpx_groupnorm_bwd.argtypes = [vp] * 8 + [ci] * 5 + [fl, vp, sz, vp]
-        L.vpx_phycell_correct_fwd.restype = ci
-        L.vpx_phycell_correct_fwd.argtypes = [vp] * 5 + [ll, vp]
-        L.vpx_phycell_correct_bwd.restype = ci
-        L.vpx_phycell_correct_bwd.argtypes = [vp] * 9 + [ll, vp]
-        L.vpx_moment_loss_fwd.restype = ci
-        L.vpx_moment_loss_fwd.argtypes = [vp, vp] + [ci] * 4 + [fl, vp]
-        L.vpx_moment_loss_bwd.restype = ci
-        L.vpx_moment_loss_bwd.argtypes = [vp, vp, vp] + [ci] * 4 + [fl, vp]
-        for name in ("vpx_sigmoid_head_fwd", "vpx_sigmoid_head_bwd"):
-            getattr(L, name).restype = ci
-        L.vpx_sigmoid_head_fwd.argtypes = [vp, vp] + [ci] * 7 + [vp]
-        L.vpx_sigmoid_head_bwd.argtypes = [vp, vp, vp] + [ci] * 7 + [vp]
-        for name in ("vpx_conv2d_act_workspace_bytes", "vpx_conv2d_act_bwd_workspace_bytes"):
-            getattr(L, name).restype = sz
-            getattr(L, name).argtypes = [ctypes.POINTER(ConvDesc), ci]
-        L.vpx_conv2d_act_fwd.restype = ci
-        L.vpx_conv2d_act_fwd.argtypes = [ctypes.POINTER(ConvDesc), ci] + [vp] * 4 + [vp, sz, vp]
-        L.vpx_conv2d_act_bwd.restype = ci
-        L.vpx_conv2d_act_bwd.argtypes = [ctypes.POINTER(ConvDesc), ci] + [vp] * 7 + [vp, sz, vp]
-        L.vpx_relu_rownorm_fwd.restype = ci
-        L.vpx_relu_rownorm_fwd.argtypes = [vp] * 3 + [ci] * 4 + [fl, vp]
-        L.vpx_relu_rownorm_bwd.restype = ci
-        L.vpx_relu_rownorm_bwd.argtypes = [vp] * 4 + [ci] * 4 + [fl, vp]
-        L.vpx_merge1x1_workspace_bytes.restype = sz
-        L.vpx_merge1x1_workspace_bytes.argtypes = [ci] * 3
-        L.vpx_merge1x1_fwd.restype = ci
-        L.vpx_merge1x1_fwd.argtypes = [vp] * 5 + [ci] * 7 + [vp, sz, vp]
-        L.vpx_merge1x1_bwd_workspace_bytes.restype = sz
-        L.vpx_merge1x1_bwd_workspace_bytes.argtypes = [ci] * 6
-        L.vpx_merge1x1_bwd.restype = ci
-        L.vpx_merge1x1_bwd.argtypes = [vp] * 8 + [ci] * 7 + [vp, sz, vp]
-        for name in ("vpx_nchw_to_nhwc", "vpx_nhwc_to_nchw"):
-            getattr(L, name).restype = ctypes.c_int
-            getattr(L, name).argtypes = [vp, vp] + [ctypes.c_int] * 4 + [vp]
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -274,3 +207,8 @@ def check(rc: int, what: str):
 def ptr(t):
     """Device pointer of a torch tensor or None."""
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def ptr_array(tensors):
+    """C array of the device pointers of `tensors` (NULL for None): the `const float* const*` arguments."""
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])

@@ -1,13 +1,15 @@
 """torch-level operators over the C ABI (include/vpx.h). Tensors keep the reference's LOGICAL shapes
 ([B,T,C,H,W], [B,C,H,W]) but live channels-last in memory (NHWC) so that kernels get coalesced channel rows and the
 glue convolutions of the models (MIOpen, channels_last) exchange activations with them without a copy."""
+import collections
+import contextlib
 import ctypes
-import os
+import weakref
 
 import torch
 
 from . import _lib
-from ._lib import ConvDesc, ConvLSTMDesc, STLSTMDesc, check, ptr
+from ._lib import ConvDesc, ConvLSTMDesc, STLSTMDesc, check, ptr, ptr_array
 
 VpxError = _lib.VpxError
 PRECISIONS = {"f32": _lib.PREC_F32, "bf16x3": _lib.PREC_BF16X3, "bf16": _lib.PREC_BF16}
@@ -32,8 +34,23 @@ class KernelProfile:
 PROFILE = None  # set to a KernelProfile() to collect
 BWD_WEIGHT_PACK_REUSE = True   #: ST-LSTM backward: keep the transposed weight packs between the steps of one cell (tests switch it off)
 
-def _require_gpu(t: torch.Tensor, what: str):
-    _sync_determinism()
+
+@contextlib.contextmanager
+def _profiled(tag, launches, work, wide_read_bytes=0.0):
+    """The HIP-event bracket around one fused-cell library call while PROFILE collects (the call is the `with` body; a call that raises
+    leaves no record). work() -> (algorithmic flops, algorithmic bytes), evaluated only then."""
+    if PROFILE is None:
+        yield
+        return
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    yield
+    ev1.record()
+    PROFILE.records.append((ev0, ev1, *work(), launches, tag, wide_read_bytes))
+
+
+def require_gpu(t: torch.Tensor, what: str):
+    sync_determinism()
     if not t.is_cuda:
         raise _lib.VpxError(f"{what}: tensors must live on the GPU (got device '{t.device}'). The hot path runs only as "
                             f"HIP kernels on MI355X; there is no CPU fallback.")
@@ -44,7 +61,7 @@ def _require_gpu(t: torch.Tensor, what: str):
 _det_state = None
 
 
-def _sync_determinism():
+def sync_determinism():
     """Mirrors torch.use_deterministic_algorithms() into the library (deterministic mode forbids the K-split
     convolutions' floating-point atomics, see include/vpx.h). Called at the start of every op, before any size query."""
     global _det_state
@@ -54,8 +71,56 @@ def _sync_determinism():
         _det_state = det
 
 
-def _stream():
+def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def needs_grad(*tensors):
+    """True when a call on these tensors (None and non-tensor operands allowed) will need a backward. Asked in the wrappers: inside
+    Function.forward grad mode is always off and ctx.needs_input_grad ignores torch.no_grad()."""
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+
+
+NOT_IMPLEMENTED = b"not implemented"
+
+
+def workspace_bytes(query, *args, unsupported=None):
+    """Answer of a `*_workspace_bytes` query. With `unsupported` — the words by which the query's message tells a problem the library
+    does not implement (NotImplementedError) from a bad argument (ValueError) — an answer of 0, the query's refusal, raises through
+    check(). Without it the answer is passed on as it is: those queries leave no message, the launch reports the error."""
+    nbytes = query(*args)
+    if nbytes == 0 and unsupported is not None:
+        check(-4 if unsupported in _lib.lib().vpx_last_error() else -1, query.__name__)
+    return nbytes
+
+
+def workspace(dev, query, *args, unsupported=None):
+    """(uint8 tensor, nbytes): the workspace a `*_workspace_bytes` query asks for (see workspace_bytes)."""
+    nbytes = workspace_bytes(query, *args, unsupported=unsupported)
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+
+
+def reserve_buffer(dev, query, d):
+    """(uint8 tensor, nbytes): the saved-for-backward buffer a `*_reserve_bytes` query asks for (0 bytes without SAVE_FOR_BWD: one byte,
+    so that the library still gets a pointer)."""
+    nbytes = query(ctypes.byref(d))
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), nbytes
+
+
+def conv_desc(xshape, wshape, stride, padding, transposed, slope, precision, out_pad=(0, 0)):
+    """ConvDesc of a Conv2d / ConvTranspose2d layer with weight shape `wshape` (the reference's layout) on an input of logical shape
+    `xshape` = (N, Ci, H, W). `precision`: a PREC_* code."""
+    N, Ci, H, Wd = (int(s) for s in xshape)
+    Co = int(wshape[1] if transposed else wshape[0])
+    return ConvDesc(N, H, Wd, Ci, Co, int(wshape[2]), int(wshape[3]), int(stride), int(padding), int(bool(transposed)), float(slope), precision,
+                    int(out_pad[0]), int(out_pad[1]))
+
+
+def conv_out_shape(d):
+    """(Ho, Wo) of the layer a ConvDesc describes; a descriptor the library refuses raises through check()."""
+    ho, wo = ctypes.c_int(0), ctypes.c_int(0)
+    check(_lib.lib().vpx_conv2d_ex_out_shape(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)), "vpx_conv2d_ex_out_shape")
+    return ho.value, wo.value
 
 
 def to_channels_last(t: torch.Tensor) -> torch.Tensor:
@@ -66,6 +131,16 @@ def to_channels_last(t: torch.Tensor) -> torch.Tensor:
     return t.permute(perm).contiguous().permute(inv)
 
 
+def _unchanged(ref, version, addr, t=None, at=None):
+    """The cache-entry test 'same tensor, still alive and unmodified': the weak reference still leads to a tensor (to `t` itself, when
+    given) whose version counter is `version` and whose data is at `addr` (`at`: the address the caller is about to hand to the
+    library instead of the tensor's own, i.e. that of its contiguous form)."""
+    live = ref()
+    if live is None or (t is not None and live is not t):
+        return False
+    return live._version == version and (live.data_ptr() if at is None else at) == addr
+
+
 class _WorkspaceCache:
     """Workspaces (and with them packed weights) kept between inference calls while the owning weight tensor is unchanged.
     LRU with a byte budget; an entry whose weight tensor died, changed version or moved, or whose kernel-option epoch is
@@ -73,7 +148,6 @@ class _WorkspaceCache:
     HBM beyond the budget."""
 
     def __init__(self, budget_bytes=4 << 30):
-        import collections
         self.budget, self.bytes, self.ents = budget_bytes, 0, collections.OrderedDict()
 
     def get(self, key, w, addr, need_bytes, dev, exact=True):
@@ -81,7 +155,7 @@ class _WorkspaceCache:
         if ent is None:
             return None
         ref, version, a, ws, _ = ent
-        ok = ref() is w and version == w._version and a == addr and ws.device == dev and \
+        ok = _unchanged(ref, version, a, w, addr) and ws.device == dev and \
             (ws.numel() == need_bytes if exact else ws.numel() >= need_bytes)
         if not ok:
             self._drop(key)
@@ -90,10 +164,8 @@ class _WorkspaceCache:
         return ws
 
     def put(self, key, w, addr, ws, epoch):
-        import weakref
         self._drop(key)
-        for k in [k for k, (ref, version, a, _, ep) in self.ents.items()
-                  if ref() is None or ref()._version != version or ref().data_ptr() != a or ep != epoch]:
+        for k in [k for k, (ref, version, a, _, ep) in self.ents.items() if not _unchanged(ref, version, a) or ep != epoch]:
             self._drop(k)
         if ws.numel() > self.budget:   # larger than the whole budget: never kept (the caller re-packs every call)
             return
@@ -126,15 +198,11 @@ def _cached_channels_last(p: torch.Tensor) -> torch.Tensor:
     through a weak reference — a recycled address can never hit — plus (_version, data_ptr)): the peephole tensors
     [1,Ch,H,W] of a ConvLSTM block are converted once per optimizer step instead of once per call. Writes through
     `.data` do not bump `_version`; code doing that must call `ops.clear_layout_cache()`."""
-    import weakref
     ent = _cl_cache.get(id(p))
-    if ent is not None:
-        ref, version, addr, cl = ent
-        if ref() is p and version == p._version and addr == p.data_ptr():
-            return cl
+    if ent is not None and _unchanged(*ent[:3], p):
+        return ent[3]
     if len(_cl_cache) > 256:   # drop what died or went stale first; only a cache full of live entries is cleared
-        for k in [k for k, (ref, version, addr, _) in _cl_cache.items()
-                  if ref() is None or ref()._version != version or ref().data_ptr() != addr]:
+        for k in [k for k, ent in _cl_cache.items() if not _unchanged(*ent[:3])]:
             del _cl_cache[k]
         if len(_cl_cache) > 256:
             _cl_cache.clear()
@@ -197,7 +265,7 @@ class _ConvLSTMSeqFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, h0, c0, W, b, Wci, Wcf, Wco, seq_len, gate_order, precision, in_channels, need_grad, out_split=False):
         ref = x.buf if isinstance(x, SplitActivation) else (x if x is not None else h0)
-        _require_gpu(ref, "convlstm_seq")
+        require_gpu(ref, "convlstm_seq")
         dev = ref.device
         Ch = W.shape[0] // 4
         kh, kw = int(W.shape[2]), int(W.shape[3])
@@ -232,10 +300,7 @@ class _ConvLSTMSeqFn(torch.autograd.Function):
                          (_lib.FLAG_SAVE_FOR_BWD if need_grad else 0) | (_lib.FLAG_X_SPLIT if x_split else 0) |
                          (_lib.FLAG_OUT_SPLIT if out_split else 0))
         L = _lib.lib()
-        ws_bytes = L.vpx_convlstm_workspace_bytes(ctypes.byref(d))
-        rs_bytes = L.vpx_convlstm_reserve_bytes(ctypes.byref(d))
-        if ws_bytes == 0:
-            check(-1 if "not implemented" not in L.vpx_last_error().decode() else -4, "vpx_convlstm_workspace_bytes")
+        ws_bytes = workspace_bytes(L.vpx_convlstm_workspace_bytes, ctypes.byref(d), unsupported=NOT_IMPLEMENTED)
         ws = None
         if not need_grad and ws_bytes <= _CLSTM_WS_CACHE_LIMIT:
             # inference: the block keeps its workspace, and with it the weight packs, while the weight tensor is unchanged
@@ -250,7 +315,7 @@ class _ConvLSTMSeqFn(torch.autograd.Function):
                 _clstm_ws.put(key, W, Wc.data_ptr(), ws, _kernel_options())
         if ws is None:
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        reserve = torch.empty(max(rs_bytes, 1), dtype=torch.uint8, device=dev)
+        reserve, rs_bytes = reserve_buffer(dev, L.vpx_convlstm_reserve_bytes, d)
         if out_split:   # the sequence in operand format (no fp32 copy exists); h_T separately in fp32
             out = torch.empty(B * T * H * Wd * Ch, dtype=torch.float32, device=dev)
             hT = new_channels_last((B, Ch, H, Wd), dev)
@@ -258,19 +323,13 @@ class _ConvLSTMSeqFn(torch.autograd.Function):
             out = new_channels_last((B, T, Ch, H, Wd), dev)
             hT = out[:, T - 1]  # h_T IS the last slice of the output slab: a view, no copy
         cT = new_channels_last((B, Ch, H, Wd), dev)
-        if PROFILE is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        rc = L.vpx_convlstm_seq_fwd(ctypes.byref(d), ptr(x), ptr(h0c), ptr(c0c), ptr(Wc), ptr(bc), ptr(wci), ptr(wcf),
-                                    ptr(wco), ptr(out), ptr(hT) if out_split else None, ptr(cT), ptr(reserve), rs_bytes, ptr(ws),
-                                    ws_bytes, _stream())
-        check(rc, "vpx_convlstm_seq_fwd")
-        if PROFILE is not None:
-            ev1.record()
-            fl, by = convlstm_algorithmic_work(B, T, Cin if x is not None else 0, Ch, H, Wd, kh, kw,
-                                               h0 is not None, peep)
-            wide = 4.0 * H * Wd * Ch * B * (T if h0 is not None else T - 1)   # c_{t-1}, read by the fused step's epilogue in full lines
-            PROFILE.records.append((ev0, ev1, fl, by, T, "convlstm_fwd", wide))
+        wide = 4.0 * H * Wd * Ch * B * (T if h0 is not None else T - 1)   # c_{t-1}, read by the fused step's epilogue in full lines
+        with _profiled("convlstm_fwd", T, lambda: convlstm_algorithmic_work(B, T, Cin if x is not None else 0, Ch, H, Wd, kh, kw,
+                                                                            h0 is not None, peep), wide):
+            rc = L.vpx_convlstm_seq_fwd(ctypes.byref(d), ptr(x), ptr(h0c), ptr(c0c), ptr(Wc), ptr(bc), ptr(wci), ptr(wcf),
+                                        ptr(wco), ptr(out), ptr(hT) if out_split else None, ptr(cT), ptr(reserve), rs_bytes, ptr(ws),
+                                        ws_bytes, stream())
+            check(rc, "vpx_convlstm_seq_fwd")
         if need_grad:
             ctx.save_for_backward(x, h0c, c0c, Wc, wci, wcf, wco, out, reserve)
             ctx.desc = d
@@ -282,7 +341,7 @@ class _ConvLSTMSeqFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, dhT, dcT):
-        _sync_determinism()
+        sync_determinism()
         x, h0c, c0c, Wc, wci, wcf, wco, out, reserve = ctx.saved_tensors
         d = ctx.desc
         dev = out.device
@@ -301,12 +360,11 @@ class _ConvLSTMSeqFn(torch.autograd.Function):
         dwci = new_channels_last((1, Ch, H, Wd), dev) if (peep and needs[5]) else None
         dwcf = new_channels_last((1, Ch, H, Wd), dev) if (peep and needs[6]) else None
         dwco = new_channels_last((1, Ch, H, Wd), dev) if (peep and needs[7]) else None
-        ws_bytes = L.vpx_convlstm_workspace_bytes(ctypes.byref(d))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws, ws_bytes = workspace(dev, L.vpx_convlstm_workspace_bytes, ctypes.byref(d))
         rc = L.vpx_convlstm_seq_bwd(ctypes.byref(d), ptr(x), ptr(h0c), ptr(c0c), ptr(Wc), ptr(wci), ptr(wcf), ptr(wco),
                                     ptr(out), ptr(reserve), ctx.rs_bytes, ptr(dout), ptr(dhT), ptr(dcT), ptr(dx),
                                     ptr(dh0), ptr(dc0), ptr(dW), ptr(db), ptr(dwci), ptr(dwcf), ptr(dwco), ptr(ws),
-                                    ws_bytes, _stream())
+                                    ws_bytes, stream())
         check(rc, "vpx_convlstm_seq_bwd")
         return dx, dh0, dc0, dW, db, dwci, dwcf, dwco, None, None, None, None, None
 
@@ -339,8 +397,7 @@ def convlstm_seq(x, h0, c0, W, b, Wci=None, Wcf=None, Wco=None, *, seq_len, in_c
     if x is None and h0 is None:
         raise ValueError("convlstm_seq: inputs and states must not both be None")
     # grad mode is always off INSIDE Function.forward, so decide here whether the forward must fill the reserve
-    need_grad = torch.is_grad_enabled() and any(
-        isinstance(t, torch.Tensor) and t.requires_grad for t in (x, h0, c0, W, b, Wci, Wcf, Wco))
+    need_grad = needs_grad(x, h0, c0, W, b, Wci, Wcf, Wco)
     if isinstance(x, SplitActivation) or out_split:   # autograd.Function.apply only takes / returns tensors: call the forward body directly
         if need_grad:
             raise ValueError("convlstm_seq: split-format input / output is inference-only")
@@ -363,7 +420,7 @@ class _Conv2dSameFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, bias, precision):
-        _require_gpu(x, "conv2d_same")
+        require_gpu(x, "conv2d_same")
         xs = to_channels_last(x)
         N, Ci, H, Wd = xs.shape
         Co, ci_w, kh, kw = w.shape
@@ -372,11 +429,10 @@ class _Conv2dSameFn(torch.autograd.Function):
         wc = w.contiguous()
         bc = None if bias is None else bias.contiguous()
         L = _lib.lib()
-        ws_bytes = L.vpx_conv2d_workspace_bytes(Ci, Co, kh, kw)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        ws, ws_bytes = workspace(x.device, L.vpx_conv2d_workspace_bytes, Ci, Co, kh, kw)
         y = new_channels_last((N, Co, H, Wd), x.device)
         rc = L.vpx_conv2d_nhwc_fwd(ptr(xs), ptr(wc), ptr(bc), ptr(y), N, H, Wd, Ci, Co, kh, kw, precision, ptr(ws),
-                                   ws_bytes, _stream())
+                                   ws_bytes, stream())
         check(rc, "vpx_conv2d_nhwc_fwd")
         ctx.save_for_backward(xs, wc)
         ctx.has_bias = bias is not None
@@ -385,7 +441,7 @@ class _Conv2dSameFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        _sync_determinism()
+        sync_determinism()
         xs, wc = ctx.saved_tensors
         N, Ci, H, Wd = xs.shape
         Co, _, kh, kw = wc.shape
@@ -395,10 +451,9 @@ class _Conv2dSameFn(torch.autograd.Function):
         dw = torch.empty_like(wc) if needs[1] else None
         db = torch.empty(Co, device=xs.device) if (ctx.has_bias and needs[2]) else None
         L = _lib.lib()
-        ws_bytes = L.vpx_conv2d_bwd_workspace_bytes(N, H, Wd, Ci, Co, kh, kw)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=xs.device)
+        ws, ws_bytes = workspace(xs.device, L.vpx_conv2d_bwd_workspace_bytes, N, H, Wd, Ci, Co, kh, kw)
         rc = L.vpx_conv2d_nhwc_bwd(ptr(xs), ptr(wc), ptr(dys), ptr(dx), ptr(dw), ptr(db), N, H, Wd, Ci, Co, kh, kw,
-                                   ctx.precision, ptr(ws), ws_bytes, _stream())
+                                   ctx.precision, ptr(ws), ws_bytes, stream())
         check(rc, "vpx_conv2d_nhwc_bwd")
         return dx, dw, db, None
 
@@ -419,49 +474,41 @@ class _ConvExFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, bias, stride, padding, transposed, slope, precision, out_pad=(0, 0)):
-        kh, kw = int(w.shape[2]), int(w.shape[3])
-        _require_gpu(x, "conv2d_ex")
+        require_gpu(x, "conv2d_ex")
         xs = to_channels_last(x)
         N, Ci, H, Wd = xs.shape
-        kh, kw = int(w.shape[2]), int(w.shape[3])
-        Co = int(w.shape[1] if transposed else w.shape[0])
         if int(w.shape[0] if transposed else w.shape[1]) != Ci:
             raise ValueError(f"conv2d_ex: weight {tuple(w.shape)} does not match {Ci} input channels")
         wc = w.contiguous()
         bc = None if bias is None else bias.contiguous()
-        d = ConvDesc(N, H, Wd, Ci, Co, kh, kw, int(stride), int(padding), int(bool(transposed)), float(slope), precision,
-                     int(out_pad[0]), int(out_pad[1]))
+        d = conv_desc(xs.shape, w.shape, stride, padding, transposed, slope, precision, out_pad)
         L = _lib.lib()
-        ho, wo = ctypes.c_int(0), ctypes.c_int(0)
-        check(L.vpx_conv2d_ex_out_shape(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)), "vpx_conv2d_ex_out_shape")
-        y = new_channels_last((N, Co, ho.value, wo.value), x.device)
+        y = new_channels_last((N, d.Co, *conv_out_shape(d)), x.device)
         x_sp = None
         if (ctx.needs_input_grad[1] and tuple(out_pad) == (0, 0) and L.vpx_conv2d_ex_bwd_uses_split(ctypes.byref(d))
                 and L.vpx_conv2d_ex_takes_split(ctypes.byref(d))):
             # a training call whose weight gradient will want x in the split operand format anyway (wgrad2.hip, glue form): convert once,
             # run the forward on the split-input kernels (convq / c16 / first generation without its in-kernel conversion) and keep the copy
             x_sp = torch.empty(xs.numel(), dtype=torch.float32, device=x.device)
-            check(L.vpx_split_convert(ptr(xs), ptr(x_sp), N * H * Wd, Ci, _stream()), "vpx_split_convert")
-            ws_bytes = L.vpx_conv2d_ex_split_workspace_bytes(ctypes.byref(d))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+            check(L.vpx_split_convert(ptr(xs), ptr(x_sp), N * H * Wd, Ci, stream()), "vpx_split_convert")
+            ws, ws_bytes = workspace(x.device, L.vpx_conv2d_ex_split_workspace_bytes, ctypes.byref(d))
             check(L.vpx_conv2d_ex_fwd_from_split(ctypes.byref(d), ptr(x_sp), 0, 0, 1, ptr(wc), ptr(bc), ptr(y), None, 0, ptr(ws), ws_bytes,
-                                                 _stream()), "vpx_conv2d_ex_fwd_from_split")
+                                                 stream()), "vpx_conv2d_ex_fwd_from_split")
         else:
-            ws_bytes = L.vpx_conv2d_ex_workspace_bytes(ctypes.byref(d))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-            check(L.vpx_conv2d_ex_fwd(ctypes.byref(d), ptr(xs), ptr(wc), ptr(bc), ptr(y), ptr(ws), ws_bytes, _stream()),
+            ws, ws_bytes = workspace(x.device, L.vpx_conv2d_ex_workspace_bytes, ctypes.byref(d))
+            check(L.vpx_conv2d_ex_fwd(ctypes.byref(d), ptr(xs), ptr(wc), ptr(bc), ptr(y), ptr(ws), ws_bytes, stream()),
                   "vpx_conv2d_ex_fwd")
         ctx.x_sp = x_sp
         ctx.save_for_backward(xs, wc, y)
-        ctx.cfg = (int(stride), int(padding), bool(transposed), float(slope), bias is not None)
+        ctx.cfg = (float(slope), bias is not None)
         ctx.desc = d
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        _sync_determinism()
+        sync_determinism()
         xs, wc, y = ctx.saved_tensors
-        stride, padding, transposed, slope, has_bias = ctx.cfg
+        slope, has_bias = ctx.cfg
         mask = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]]
         d = ctx.desc
         if d.kh >= d.stride and d.kw >= d.stride and slope >= 0.0:
@@ -469,19 +516,16 @@ class _ConvExFn(torch.autograd.Function):
             # dw on the MFMA weight-gradient kernel
             L = _lib.lib()
             dyc = to_channels_last(dy)
-            ws_bytes = L.vpx_conv2d_ex_bwd_workspace_bytes(ctypes.byref(d))
-            if ws_bytes == 0:
-                check(-4 if b"not implemented" in L.vpx_last_error() else -1, "vpx_conv2d_ex_bwd_workspace_bytes")
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dy.device)
+            ws, ws_bytes = workspace(dy.device, L.vpx_conv2d_ex_bwd_workspace_bytes, ctypes.byref(d), unsupported=NOT_IMPLEMENTED)
             dx = new_channels_last(tuple(xs.shape), dy.device) if mask[0] else None
             dw = torch.empty_like(wc) if mask[1] else None
             db = torch.empty(d.Co, device=dy.device) if mask[2] else None
             check(L.vpx_conv2d_ex_bwd_ex(ctypes.byref(d), ptr(xs), ptr(ctx.x_sp), ptr(wc), ptr(y), ptr(dyc), ptr(dx), ptr(dw), ptr(db), ptr(ws),
-                                         ws_bytes, _stream()), "vpx_conv2d_ex_bwd")
+                                         ws_bytes, stream()), "vpx_conv2d_ex_bwd")
             ctx.x_sp = None
             return dx, dw, db, None, None, None, None, None, None
         # No second backend in the product path: a layer the library's glue backward does not implement fails loudly.
-        raise _lib.VpxError(f"conv2d_ex backward: layer (k={d.kh}x{d.kw}, stride={stride}, transposed={bool(transposed)}, slope={slope}) "
+        raise _lib.VpxError(f"conv2d_ex backward: layer (k={d.kh}x{d.kw}, stride={d.stride}, transposed={bool(d.transposed)}, slope={slope}) "
                        f"is outside vpx_conv2d_ex_bwd (needs kernel >= stride and a non-negative LeakyReLU slope): unsupported")
 
 
@@ -489,13 +533,10 @@ def conv2d_ex(x, w, bias, stride, padding, transposed=False, leaky_slope=0.0, pr
     """Conv2d / ConvTranspose2d (stride 1 or 2; `output_padding` for transposed layers) + bias + LeakyReLU, differentiable."""
     kh, kw = int(w.shape[2]), int(w.shape[3])
     # (decided here: inside Function.forward grad mode is always off and needs_input_grad ignores torch.no_grad())
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w, bias)):
+    if needs_grad(x, w, bias):
         ok = kh >= stride and kw >= stride and leaky_slope >= 0.0
         if ok and x.dim() == 4:   # ... and the adjoint layer must be one the library runs (the same query the backward makes)
-            N, Ci, H, Wd = x.shape
-            Co = int(w.shape[1] if transposed else w.shape[0])
-            d = ConvDesc(N, H, Wd, Ci, Co, kh, kw, int(stride), int(padding), int(bool(transposed)), float(leaky_slope), PRECISIONS[precision],
-                         int(output_padding[0]), int(output_padding[1]))
+            d = conv_desc(x.shape, w.shape, stride, padding, transposed, leaky_slope, PRECISIONS[precision], output_padding)
             L = _lib.lib()
             ho, wo = ctypes.c_int(0), ctypes.c_int(0)
             if L.vpx_conv2d_ex_out_shape(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)) == 0:
@@ -510,31 +551,25 @@ def conv2d_ex(x, w, bias, stride, padding, transposed=False, leaky_slope=0.0, pr
 def conv2d_ex_split(x, w, bias, stride, padding, transposed=False, leaky_slope=0.0, precision="f32"):
     """conv2d_ex in inference with the output ONLY in the split-bf16 operand format: returns (buffer, (N, Co, Ho, Wo)).
     The buffer has the byte size of the fp32 NHWC output it replaces."""
-    _require_gpu(x, "conv2d_ex_split")
+    require_gpu(x, "conv2d_ex_split")
     xs = to_channels_last(x)
-    N, Ci, H, Wd = xs.shape
-    kh, kw = int(w.shape[2]), int(w.shape[3])
-    Co = int(w.shape[1] if transposed else w.shape[0])
-    d = ConvDesc(N, H, Wd, Ci, Co, kh, kw, int(stride), int(padding), int(bool(transposed)), float(leaky_slope),
-                 PRECISIONS[precision], 0, 0)
+    d = conv_desc(xs.shape, w.shape, stride, padding, transposed, leaky_slope, PRECISIONS[precision])
     L = _lib.lib()
-    ho, wo = ctypes.c_int(0), ctypes.c_int(0)
-    check(L.vpx_conv2d_ex_out_shape(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)), "vpx_conv2d_ex_out_shape")
-    ws_bytes = L.vpx_conv2d_ex_workspace_bytes(ctypes.byref(d))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-    buf = torch.empty(N * ho.value * wo.value * Co, dtype=torch.float32, device=x.device)
+    ho, wo = conv_out_shape(d)
+    ws, ws_bytes = workspace(x.device, L.vpx_conv2d_ex_workspace_bytes, ctypes.byref(d))
+    buf = torch.empty(d.N * ho * wo * d.Co, dtype=torch.float32, device=x.device)
     wc = w.contiguous()
     bc = None if bias is None else bias.contiguous()
-    check(L.vpx_conv2d_ex_fwd_split(ctypes.byref(d), ptr(xs), ptr(wc), ptr(bc), None, ptr(buf), ptr(ws), ws_bytes, _stream()),
+    check(L.vpx_conv2d_ex_fwd_split(ctypes.byref(d), ptr(xs), ptr(wc), ptr(bc), None, ptr(buf), ptr(ws), ws_bytes, stream()),
           "vpx_conv2d_ex_fwd_split")
-    return buf, (N, Co, ho.value, wo.value)
+    return buf, (d.N, d.Co, ho, wo)
 
 
 def split_convert(x, native=True):
     """fp32 [..., C, H, W] tensor -> SplitActivation-style buffer in the split-bf16 operand format (vpx_split_convert for a
     channels-last 4-D batch; otherwise — and with native=False, the tests' cross-check — the same rounding with torch ops).
     Returns (buffer, logical shape)."""
-    _require_gpu(x, "split_convert")
+    require_gpu(x, "split_convert")
     xs = to_channels_last(x)
     C = xs.shape[-3]
     if C % 8:
@@ -542,7 +577,7 @@ def split_convert(x, native=True):
     if native and xs.dim() == 4 and xs.dtype == torch.float32 and xs.is_contiguous(memory_format=torch.channels_last):
         buf = torch.empty(xs.numel(), device=xs.device, dtype=torch.float32)
         n, _, h, w = xs.shape
-        check(_lib.lib().vpx_split_convert(ptr(xs), ptr(buf), n * h * w, C, _stream()), "vpx_split_convert")
+        check(_lib.lib().vpx_split_convert(ptr(xs), ptr(buf), n * h * w, C, stream()), "vpx_split_convert")
         return buf, tuple(x.shape)
     # fp32 hi/lo split on the GPU with torch ops (same rounding as the kernels: round-to-nearest-even to bf16, twice)
     flat = xs.permute(*range(xs.dim() - 3), xs.dim() - 2, xs.dim() - 1, xs.dim() - 3).contiguous()   # [..., H, W, C]
@@ -557,14 +592,14 @@ _convq_ws = _WorkspaceCache()
 
 
 def conv2d_ex_takes_split(N, H, W, Ci, Co, kh, kw, stride, padding, transposed, precision="bf16x3"):
-    d = ConvDesc(N, H, W, Ci, Co, kh, kw, int(stride), int(padding), int(bool(transposed)), 0.0, PRECISIONS[precision], 0, 0)
+    d = conv_desc((N, Ci, H, W), (Ci, Co, kh, kw) if transposed else (Co, Ci, kh, kw), stride, padding, transposed, 0.0, PRECISIONS[precision])
     return bool(_lib.lib().vpx_conv2d_ex_takes_split(ctypes.byref(d)))
 
 
 def conv2d_ex_prefers_split(N, H, W, Ci, Co, kh, kw, stride, padding, transposed, precision="bf16x3"):
     """True when the layer runs on the schedule-driven K = 32 kernel (convq) given split input — for stride-2 transposed layers
     that is worth converting an fp32 input first (all four output phases in one launch)."""
-    d = ConvDesc(N, H, W, Ci, Co, kh, kw, int(stride), int(padding), int(bool(transposed)), 0.0, PRECISIONS[precision], 0, 0)
+    d = conv_desc((N, Ci, H, W), (Ci, Co, kh, kw) if transposed else (Co, Ci, kh, kw), stride, padding, transposed, 0.0, PRECISIONS[precision])
     return _lib.lib().vpx_conv2d_ex_takes_split(ctypes.byref(d)) == 2
 
 
@@ -573,15 +608,11 @@ def conv2d_ex_from_split(xbuf, xshape, w, bias, stride, padding, transposed=Fals
     """The stage-glue layer on an input that already is in the split-bf16 operand format (inference): xbuf / xshape =
     (buffer, (N, Ci, H, W)). Returns (y or None, ybuf or None, (N, Co, Ho, Wo)). The packed weights stay in a per-layer
     workspace while the weight tensor is unchanged (keyed on the tensor object, its version and address)."""
-    import weakref
     N, Ci, H, Wd = xshape
-    kh, kw = int(w.shape[2]), int(w.shape[3])
-    Co = int(w.shape[1] if transposed else w.shape[0])
-    d = ConvDesc(N, H, Wd, Ci, Co, kh, kw, int(stride), int(padding), int(bool(transposed)), float(leaky_slope),
-                 PRECISIONS[precision], 0, 0)
+    d = conv_desc(xshape, w.shape, stride, padding, transposed, leaky_slope, PRECISIONS[precision])
+    Co, kh, kw = d.Co, d.kh, d.kw
     L = _lib.lib()
-    ho, wo = ctypes.c_int(0), ctypes.c_int(0)
-    check(L.vpx_conv2d_ex_out_shape(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)), "vpx_conv2d_ex_out_shape")
+    ho, wo = conv_out_shape(d)
     ws_bytes = L.vpx_conv2d_ex_split_workspace_bytes(ctypes.byref(d))
     if ws_bytes == 0:
         raise _lib.VpxError("conv2d_ex_from_split: layer not implemented on split input: " + L.vpx_last_error().decode())
@@ -598,11 +629,11 @@ def conv2d_ex_from_split(xbuf, xshape, w, bias, stride, padding, transposed=Fals
     if wc.data_ptr() != w.data_ptr():
         packed = 0
     bc = None if bias is None else bias.contiguous()
-    y = new_channels_last((N, Co, ho.value, wo.value), xbuf.device) if out_fp32 else None
-    ybuf = torch.empty(N * ho.value * wo.value * Co, dtype=torch.float32, device=xbuf.device) if out_split else None
+    y = new_channels_last((N, Co, ho, wo), xbuf.device) if out_fp32 else None
+    ybuf = torch.empty(N * ho * wo * Co, dtype=torch.float32, device=xbuf.device) if out_split else None
     check(L.vpx_conv2d_ex_fwd_from_split(ctypes.byref(d), ptr(xbuf), 0, 0, 1, ptr(wc), ptr(bc), ptr(y), ptr(ybuf), packed, ptr(ws),
-                                         ws_bytes, _stream()), "vpx_conv2d_ex_fwd_from_split")
-    return y, ybuf, (N, Co, ho.value, wo.value)
+                                         ws_bytes, stream()), "vpx_conv2d_ex_fwd_from_split")
+    return y, ybuf, (N, Co, ho, wo)
 
 
 def conv_transpose2d_to_size(x, w, stride, padding, out_hw, precision="f32"):
@@ -633,15 +664,14 @@ class _DecoupleFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, delta_c, delta_m, adapter_w, precision):
-        _require_gpu(delta_c, "decouple_term")
+        require_gpu(delta_c, "decouple_term")
         dc, dm = to_channels_last(delta_c), to_channels_last(delta_m)
         B, Ch, H, Wd = dc.shape
         A = adapter_w.reshape(Ch, Ch).contiguous()
         L = _lib.lib()
-        ws_bytes = L.vpx_decouple_workspace_bytes(B, Ch, H, Wd)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dc.device)
+        ws, ws_bytes = workspace(dc.device, L.vpx_decouple_workspace_bytes, B, Ch, H, Wd)
         value = torch.empty((), device=dc.device)
-        rc = L.vpx_decouple_fwd(ptr(dc), ptr(dm), ptr(A), ptr(value), B, Ch, H, Wd, precision, ptr(ws), ws_bytes, _stream())
+        rc = L.vpx_decouple_fwd(ptr(dc), ptr(dm), ptr(A), ptr(value), B, Ch, H, Wd, precision, ptr(ws), ws_bytes, stream())
         check(rc, "vpx_decouple_fwd")
         ctx.save_for_backward(dc, dm, A)
         ctx.precision = precision
@@ -650,7 +680,7 @@ class _DecoupleFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dvalue):
-        _sync_determinism()
+        sync_determinism()
         dc, dm, A = ctx.saved_tensors
         B, Ch, H, Wd = dc.shape
         needs = ctx.needs_input_grad
@@ -662,11 +692,10 @@ class _DecoupleFn(torch.autograd.Function):
             g_dm = new_channels_last((B, Ch, H, Wd), dc.device) if needs[1] else None
         g_A = torch.empty_like(A) if needs[2] else None
         L = _lib.lib()
-        ws_bytes = L.vpx_decouple_workspace_bytes(B, Ch, H, Wd)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dc.device)
+        ws, ws_bytes = workspace(dc.device, L.vpx_decouple_workspace_bytes, B, Ch, H, Wd)
         dv = dvalue.contiguous().reshape(1)
         rc = L.vpx_decouple_bwd(ptr(dc), ptr(dm), ptr(A), ptr(dv), ptr(g_dc), ptr(g_dm), ptr(g_A), B, Ch, H, Wd,
-                                ctx.precision, ptr(ws), ws_bytes, _stream())
+                                ctx.precision, ptr(ws), ws_bytes, stream())
         check(rc, "vpx_decouple_bwd")
         return g_dc, g_dm, (None if g_A is None else g_A.reshape(ctx.wshape)), None
 
@@ -684,7 +713,7 @@ class _DecoupleBatchFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, adapter_w, precision, slab, K, B, *deltas):
-        _require_gpu(slab, "decouple_term_batched")
+        require_gpu(slab, "decouple_term_batched")
         _, KB, Ch, H, Wd = slab.shape
         if KB != K * B or len(deltas) != 2 * K:
             raise ValueError("decouple_term_batched: the slab does not hold K steps of B samples / 2K delta tensors")
@@ -697,17 +726,16 @@ class _DecoupleBatchFn(torch.autograd.Function):
             raise ValueError("decouple_term_batched: slab must be one dense channels-last block")
         A = adapter_w.reshape(Ch, Ch).contiguous()
         L = _lib.lib()
-        ws_bytes = L.vpx_decouple_workspace_bytes(KB, Ch, H, Wd)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=slab.device)
+        ws, ws_bytes = workspace(slab.device, L.vpx_decouple_workspace_bytes, KB, Ch, H, Wd)
         value = torch.empty((), device=slab.device)
-        check(L.vpx_decouple_fwd(ptr(dc), ptr(dm), ptr(A), ptr(value), KB, Ch, H, Wd, precision, ptr(ws), ws_bytes, _stream()), "vpx_decouple_fwd")
+        check(L.vpx_decouple_fwd(ptr(dc), ptr(dm), ptr(A), ptr(value), KB, Ch, H, Wd, precision, ptr(ws), ws_bytes, stream()), "vpx_decouple_fwd")
         ctx.save_for_backward(slab, A)
         ctx.geo = (K, B, precision, tuple(adapter_w.shape))
         return value
 
     @staticmethod
     def backward(ctx, dvalue):
-        _sync_determinism()
+        sync_determinism()
         slab, A = ctx.saved_tensors
         K, B, precision, wshape = ctx.geo
         _, KB, Ch, H, Wd = slab.shape
@@ -715,11 +743,10 @@ class _DecoupleBatchFn(torch.autograd.Function):
         g_dc, g_dm = gg[:KB], gg[KB:]
         g_A = torch.empty_like(A) if ctx.needs_input_grad[0] else None
         L = _lib.lib()
-        ws_bytes = L.vpx_decouple_workspace_bytes(KB, Ch, H, Wd)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=slab.device)
+        ws, ws_bytes = workspace(slab.device, L.vpx_decouple_workspace_bytes, KB, Ch, H, Wd)
         dv = dvalue.contiguous().reshape(1)
         check(L.vpx_decouple_bwd(ptr(slab[0]), ptr(slab[1]), ptr(A), ptr(dv), ptr(g_dc), ptr(g_dm), ptr(g_A), KB, Ch, H, Wd, precision,
-                                 ptr(ws), ws_bytes, _stream()), "vpx_decouple_bwd")
+                                 ptr(ws), ws_bytes, stream()), "vpx_decouple_bwd")
         per_step = []
         for k in range(K):   # every step's gradients are views of the two slabs: no copies
             per_step += [g_dc[k * B:(k + 1) * B], g_dm[k * B:(k + 1) * B]]
@@ -747,7 +774,7 @@ class _MSELossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, target, scale):
-        _require_gpu(pred, "mse_loss")
+        require_gpu(pred, "mse_loss")
         if pred.ndim != 5 or target.ndim != 5:
             raise ValueError("Mean Squared Error (MSE) / L2 Loss expects 5-D inputs!")
         if pred.shape != target.shape:
@@ -756,13 +783,12 @@ class _MSELossFn(torch.autograd.Function):
         # the sum runs over memory order, so the target only has to share the prediction's memory layout
         tg = target if (target.stride() == p.stride() and target.dtype == p.dtype) else torch.empty_like(p).copy_(target)
         L = _lib.lib()
-        ws_bytes = L.vpx_mse_loss_workspace_bytes()
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=p.device)
+        ws, ws_bytes = workspace(p.device, L.vpx_mse_loss_workspace_bytes)
         loss = torch.empty((), device=p.device)
         need = ctx.needs_input_grad[0]
         g = torch.empty_like(p) if need else None
         rc = L.vpx_mse_loss(ptr(p), ptr(tg), p.numel(), p.shape[0] * p.shape[1], float(scale), ptr(loss), ptr(g),
-                            ptr(ws), ws_bytes, _stream())
+                            ptr(ws), ws_bytes, stream())
         check(rc, "vpx_mse_loss")
         if need:
             ctx.save_for_backward(g)
@@ -783,13 +809,13 @@ def mse_loss(pred, target, scale: float = 1.0):
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
     """One torch.optim.Adam update of flat fp32 buckets, in place (vpsuite.py:353; torch/optim/adam.py semantics)."""
-    _require_gpu(param, "adam_step")
+    require_gpu(param, "adam_step")
     for t in (param, grad, exp_avg, exp_avg_sq):
         if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == param.numel()):
             raise ValueError("adam_step: buckets must be contiguous float32 GPU tensors of equal size")
     rc = _lib.lib().vpx_adam_step(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), float(lr),
                                   float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
-                                  float(grad_scale), _stream())
+                                  float(grad_scale), stream())
     check(rc, "vpx_adam_step")
 
 
@@ -901,8 +927,7 @@ class STWeightBank:
             raise _lib.VpxError("STWeightBank: vpx_stlstm_wgrad_batch is not available for this cell")
         ws = torch.empty(nb, dtype=torch.uint8, device=self.g.device)
         dWs = [torch.empty_like(w) for w in self.w5]
-        src = (ctypes.c_void_p * 5)(*[t.data_ptr() for t in self.sources])
-        check(L.vpx_stlstm_wgrad_batch(ctypes.byref(d), ptr(self.g), src, *[ptr(g) for g in dWs], ptr(ws), nb, _stream()), "vpx_stlstm_wgrad_batch")
+        check(L.vpx_stlstm_wgrad_batch(ctypes.byref(d), ptr(self.g), ptr_array(self.sources), *[ptr(g) for g in dWs], ptr(ws), nb, stream()), "vpx_stlstm_wgrad_batch")
         self.deposited.clear()
         return dWs
 
@@ -916,7 +941,7 @@ class _BankFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        _sync_determinism()
+        sync_determinism()
         dWs = ctx.bank.run()
         for i, g in enumerate(grads):       # (a consumer that did not defer — none today — adds its gradient the ordinary way)
             if g is not None:
@@ -930,7 +955,7 @@ class _STLSTMStepFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h, c, m, Wx, Wh, Wm, Wo, Wlast, precision, need_grad, wsholder, use_shadows, slots, delta_out, *ln):
-        _require_gpu(x, "stlstm_step")
+        require_gpu(x, "stlstm_step")
         dev = x.device
         B, Cin, H, Wd = x.shape
         Ch = h.shape[1]
@@ -942,10 +967,7 @@ class _STLSTMStepFn(torch.autograd.Function):
         flags = _lib.FLAG_SAVE_FOR_BWD if need_grad else 0
         d = STLSTMDesc(B, Cin, Ch, H, Wd, k, int(use_ln), _lib.LAYOUT_NHWC, precision, flags)
         L = _lib.lib()
-        ws_bytes = L.vpx_stlstm_workspace_bytes(ctypes.byref(d))
-        if ws_bytes == 0:
-            check(-4 if b"not implemented" in L.vpx_last_error() else -1, "vpx_stlstm_workspace_bytes")
-        rs_bytes = L.vpx_stlstm_reserve_bytes(ctypes.byref(d))
+        ws_bytes = workspace_bytes(L.vpx_stlstm_workspace_bytes, ctypes.byref(d), unsupported=NOT_IMPLEMENTED)
         key = (B, Cin, Ch, H, Wd, k, precision, flags, _det_state, _kernel_options(), tuple((w.data_ptr(), w._version) for w in W5),
                tuple((t.data_ptr(), t._version) for t in lnc))
         if wsholder is not None:
@@ -954,7 +976,7 @@ class _STLSTMStepFn(torch.autograd.Function):
             ws, packed = torch.empty(ws_bytes, dtype=torch.uint8, device=dev), False
         if packed:
             d.flags |= _lib.FLAG_WEIGHTS_PACKED
-        reserve = torch.empty(max(rs_bytes, 1), dtype=torch.uint8, device=dev)
+        reserve, rs_bytes = reserve_buffer(dev, L.vpx_stlstm_reserve_bytes, d)
         outs = [new_channels_last((B, Ch, H, Wd), dev) for _ in range(3)]
         if delta_out is not None:   # the caller's slab slots (decouple_term_batched: one decoupling tail over all the steps of a pass)
             for t in delta_out:
@@ -964,7 +986,7 @@ class _STLSTMStepFn(torch.autograd.Function):
         else:
             dd = new_channels_last((2 * B, Ch, H, Wd), dev)  # delta_c | delta_m adjacent: the decoupling tail runs the pair as one conv
             outs += [dd[:B], dd[B:]]
-        ln_arr = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in lnc]) if use_ln else None
+        ln_arr = ptr_array(lnc) if use_ln else None
         # split-format shadows (vpx.h): operands a previous step left in the kernels' operand format are handed back instead of being
         # converted again (h_new is the next step's h and the next layer's x, m_new the next layer's m), and this step's h_new / c_new /
         # m_new come back with shadows of their own
@@ -977,7 +999,7 @@ class _STLSTMStepFn(torch.autograd.Function):
                 raise _lib.VpxError("stlstm_step: operand slots need the split-operand kernels in a call that saves for the backward")
             sp_in[:3] = list(slot_in)
             if convert_x:   # an input without a split copy (the first layer's frame): converted into its slot of the owner's x slab
-                check(L.vpx_split_convert(ptr(xs), ptr(sp_in[0]), B * H * Wd, Cin, _stream()), "vpx_split_convert")
+                check(L.vpx_split_convert(ptr(xs), ptr(sp_in[0]), B * H * Wd, Cin, stream()), "vpx_split_convert")
             sp_out = list(slot_out)
             for buf, n in zip(sp_in[:3] + sp_out, (Cin, Ch, Ch, Ch, Ch, Ch)):
                 if buf.numel() != B * H * Wd * n or not buf.is_contiguous() or buf.dtype != torch.float32:
@@ -986,19 +1008,12 @@ class _STLSTMStepFn(torch.autograd.Function):
             sp_in[:3] = [_shadow_of(x, xs, Cin), _shadow_of(h, hs, Ch), _shadow_of(m, ms, Ch)]
             sp_out = [torch.empty(B * H * Wd * Ch, dtype=torch.float32, device=dev) for _ in range(3)]
         if sp_out is not None:
-            shadows = _lib.STLSTMShadows((ctypes.c_void_p * 5)(*[None if t is None else t.data_ptr() for t in sp_in]),
-                                         (ctypes.c_void_p * 3)(*[t.data_ptr() for t in sp_out]), None)
-        if PROFILE is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        rc = L.vpx_stlstm_step_fwd_ex(ctypes.byref(d), ptr(xs), ptr(hs), ptr(cs), ptr(ms), *[ptr(w) for w in W5], ln_arr,
-                                      *[ptr(o) for o in outs], ptr(reserve), rs_bytes, ptr(ws), ws_bytes, _stream(),
-                                      None if shadows is None else ctypes.byref(shadows))
-        check(rc, "vpx_stlstm_step_fwd")
-        if PROFILE is not None:
-            ev1.record()
-            fl, by = stlstm_algorithmic_work(B, Cin, Ch, H, Wd, k)
-            PROFILE.records.append((ev0, ev1, fl, by, 4, "stlstm_fwd", 0.0))
+            shadows = _lib.STLSTMShadows(ptr_array(sp_in), ptr_array(sp_out), None)
+        with _profiled("stlstm_fwd", 4, lambda: stlstm_algorithmic_work(B, Cin, Ch, H, Wd, k)):
+            rc = L.vpx_stlstm_step_fwd_ex(ctypes.byref(d), ptr(xs), ptr(hs), ptr(cs), ptr(ms), *[ptr(w) for w in W5], ln_arr,
+                                          *[ptr(o) for o in outs], ptr(reserve), rs_bytes, ptr(ws), ws_bytes, stream(),
+                                          None if shadows is None else ctypes.byref(shadows))
+            check(rc, "vpx_stlstm_step_fwd")
         if sp_out is not None and bank is None:
             for t, buf in zip(outs[:3], sp_out):
                 _attach_shadow(t, buf)
@@ -1016,7 +1031,7 @@ class _STLSTMStepFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dh_new, dc_new, dm_new, ddc, ddm):
-        _sync_determinism()
+        sync_determinism()
         saved = ctx.saved_tensors
         xs, hs, cs, ms, c_new, m_new, Wx, Wh, Wm, Wo, Wlast, reserve = saved[:12]
         lnc = list(saved[12:])
@@ -1032,8 +1047,8 @@ class _STLSTMStepFn(torch.autograd.Function):
         bank = getattr(ctx, "bank", None)
         dWs = [torch.empty_like(w) if (needs[4 + i] and bank is None) else None for i, w in enumerate((Wx, Wh, Wm, Wo, Wlast))]
         dln = [torch.empty_like(t) if needs[15 + i] else None for i, t in enumerate(lnc)]
-        ln_arr = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in lnc]) if ctx.use_ln else None
-        dln_arr = (ctypes.c_void_p * 8)(*[None if t is None else t.data_ptr() for t in dln]) if ctx.use_ln else None
+        ln_arr = ptr_array(lnc) if ctx.use_ln else None
+        dln_arr = ptr_array(dln) if ctx.use_ln else None
         ws_bytes = L.vpx_stlstm_workspace_bytes(ctypes.byref(d))
         flags0 = d.flags
         if ctx.bwd_holder is not None and BWD_WEIGHT_PACK_REUSE:
@@ -1045,12 +1060,12 @@ class _STLSTMStepFn(torch.autograd.Function):
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         shadows = None
         if getattr(ctx, "sp", None) is not None:   # the forward's split shadows: the weight-gradient kernel stages them as they are
-            shadows = _lib.STLSTMShadows((ctypes.c_void_p * 5)(*[None if t is None else t.data_ptr() for t in ctx.sp]), (ctypes.c_void_p * 3)(),
+            shadows = _lib.STLSTMShadows(ptr_array(ctx.sp), ptr_array((None,) * 3),
                                          None if bank is None else bank[0].g[bank[1]].data_ptr())
         rc = L.vpx_stlstm_step_bwd_ex(ctypes.byref(d), ptr(xs), ptr(hs), ptr(cs), ptr(ms), ptr(c_new), ptr(m_new), ptr(Wx),
                                       ptr(Wh), ptr(Wm), ptr(Wo), ptr(Wlast), ln_arr, ptr(reserve), ctx.rs_bytes,
                                       *[ptr(g) for g in gin], ptr(dx), ptr(dh), ptr(dc), ptr(dm), *[ptr(g) for g in dWs],
-                                      dln_arr, ptr(ws), ws_bytes, _stream(), None if shadows is None else ctypes.byref(shadows))
+                                      dln_arr, ptr(ws), ws_bytes, stream(), None if shadows is None else ctypes.byref(shadows))
         d.flags = flags0
         check(rc, "vpx_stlstm_step_bwd")
         if bank is not None:
@@ -1079,7 +1094,7 @@ def stlstm_step(x, h, c, m, Wx, Wh, Wm, Wo, Wlast, precision="f32", wsholder=Non
     ln = tuple(ln)
     if len(ln) not in (0, 8):
         raise ValueError("stlstm_step: ln must hold 0 or 8 tensors")
-    need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (x, h, c, m, Wx, Wh, Wm, Wo, Wlast) + ln)
+    need_grad = needs_grad(x, h, c, m, Wx, Wh, Wm, Wo, Wlast, *ln)
     return _STLSTMStepFn.apply(x, h, c, m, Wx, Wh, Wm, Wo, Wlast, PRECISIONS[precision], need_grad, wsholder, bool(use_shadows), slots, delta_out, *ln)
 
 
@@ -1090,20 +1105,19 @@ class _LayerNormCHWFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        _require_gpu(x, "layer_norm_chw")
+        require_gpu(x, "layer_norm_chw")
         xs = to_channels_last(x)
         B, C, H, Wd = xs.shape
         # keyed on the parameter itself (a `weight[None]` temporary is a new object every call and can never hit)
         g = _cached_channels_last(weight)
         b = _cached_channels_last(bias)
         L = _lib.lib()
-        ws_bytes = L.vpx_layernorm_workspace_bytes(B)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        ws, ws_bytes = workspace(x.device, L.vpx_layernorm_workspace_bytes, B)
         y = new_channels_last((B, C, H, Wd), x.device)
         need = any(ctx.needs_input_grad)
         xhat = new_channels_last((B, C, H, Wd), x.device) if need else None
         stats = torch.empty(B, 2, device=x.device)
-        check(L.vpx_layernorm_fwd(ptr(xs), ptr(g), ptr(b), ptr(y), ptr(xhat), ptr(stats), B, C * H * Wd, ptr(ws), ws_bytes, _stream()),
+        check(L.vpx_layernorm_fwd(ptr(xs), ptr(g), ptr(b), ptr(y), ptr(xhat), ptr(stats), B, C * H * Wd, ptr(ws), ws_bytes, stream()),
               "vpx_layernorm_fwd")
         if need:
             ctx.save_for_backward(xhat, stats, g)
@@ -1112,18 +1126,17 @@ class _LayerNormCHWFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        _sync_determinism()
+        sync_determinism()
         xhat, stats, g = ctx.saved_tensors
         B, C, H, Wd = xhat.shape
         dys = to_channels_last(dy)
         L = _lib.lib()
-        ws_bytes = L.vpx_layernorm_workspace_bytes(B)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dy.device)
+        ws, ws_bytes = workspace(dy.device, L.vpx_layernorm_workspace_bytes, B)
         dx = new_channels_last((B, C, H, Wd), dy.device)
         dg = new_channels_last((1, C, H, Wd), dy.device)
         db = new_channels_last((1, C, H, Wd), dy.device)
         check(L.vpx_layernorm_bwd(ptr(dys), ptr(xhat), ptr(stats), ptr(g), ptr(dx), ptr(dg), ptr(db), B, H * Wd, C, ptr(ws), ws_bytes,
-                                  _stream()), "vpx_layernorm_bwd")
+                                  stream()), "vpx_layernorm_bwd")
         return dx, dg.reshape(ctx.wshape), db.reshape(ctx.wshape)
 
 
@@ -1142,7 +1155,7 @@ class _ACSTStepFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h, c, m, a, precision, forget_bias, *tensors):
-        _require_gpu(x, "acstlstm_step")
+        require_gpu(x, "acstlstm_step")
         dev = x.device
         B, Cin, H, Wd = x.shape
         Ch = h.shape[1]
@@ -1154,18 +1167,14 @@ class _ACSTStepFn(torch.autograd.Function):
         need = any(ctx.needs_input_grad)
         d = _lib.ACSTLSTMDesc(B, Cin, Ch, H, Wd, k, int(bool(lnc)), precision, _lib.FLAG_SAVE_FOR_BWD if need else 0, float(forget_bias))
         L = _lib.lib()
-        ws_bytes = L.vpx_acstlstm_workspace_bytes(ctypes.byref(d))
-        if ws_bytes == 0:
-            check(-1, "vpx_acstlstm_workspace_bytes")
-        rs_bytes = L.vpx_acstlstm_reserve_bytes(ctypes.byref(d))
+        ws, ws_bytes = workspace(dev, L.vpx_acstlstm_workspace_bytes, ctypes.byref(d), unsupported=NOT_IMPLEMENTED)   # (none of its messages says so: ValueError)
+        reserve, rs_bytes = reserve_buffer(dev, L.vpx_acstlstm_reserve_bytes, d)
         xs, hs, cs, ms, as_ = (to_channels_last(t) for t in (x, h, c, m, a))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        reserve = torch.empty(max(rs_bytes, 1), dtype=torch.uint8, device=dev)
         outs = [new_channels_last((B, Ch, H, Wd), dev) for _ in range(5)]
-        p_arr = (ctypes.c_void_p * 12)(*[t.data_ptr() for t in prm])
-        ln_arr = (ctypes.c_void_p * 10)(*[t.data_ptr() for t in lnc]) if lnc else None
+        p_arr = ptr_array(prm)
+        ln_arr = ptr_array(lnc) if lnc else None
         check(L.vpx_acstlstm_step_fwd(ctypes.byref(d), ptr(xs), ptr(hs), ptr(cs), ptr(ms), ptr(as_), p_arr, ln_arr, *[ptr(o) for o in outs],
-                                      ptr(reserve), rs_bytes, ptr(ws), ws_bytes, _stream()), "vpx_acstlstm_step_fwd")
+                                      ptr(reserve), rs_bytes, ptr(ws), ws_bytes, stream()), "vpx_acstlstm_step_fwd")
         if need:
             ctx.save_for_backward(xs, hs, cs, ms, as_, reserve, *prm, *lnc)
             ctx.desc, ctx.rs_bytes = d, rs_bytes
@@ -1173,7 +1182,7 @@ class _ACSTStepFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dh_new, dc_new, dm_new, ddc, ddm):
-        _sync_determinism()
+        sync_determinism()
         saved = ctx.saved_tensors
         xs, hs, cs, ms, as_, reserve = saved[:6]
         prm, lnc = list(saved[6:18]), list(saved[18:])
@@ -1185,14 +1194,12 @@ class _ACSTStepFn(torch.autograd.Function):
         dins = [new_channels_last(tuple(t.shape), dev) if needs[i] else None for i, t in enumerate((xs, hs, cs, ms, as_))]
         dprm = [torch.empty_like(t) if needs[7 + i] else None for i, t in enumerate(prm)]
         dln = [torch.empty_like(t) if needs[19 + i] else None for i, t in enumerate(lnc)]
-        p_arr = (ctypes.c_void_p * 12)(*[t.data_ptr() for t in prm])
-        dp_arr = (ctypes.c_void_p * 12)(*[None if t is None else t.data_ptr() for t in dprm])
-        ln_arr = (ctypes.c_void_p * 10)(*[t.data_ptr() for t in lnc]) if lnc else None
-        dln_arr = (ctypes.c_void_p * 10)(*[None if t is None else t.data_ptr() for t in dln]) if lnc else None
-        ws_bytes = L.vpx_acstlstm_workspace_bytes(ctypes.byref(d))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        p_arr, dp_arr = ptr_array(prm), ptr_array(dprm)
+        ln_arr = ptr_array(lnc) if lnc else None
+        dln_arr = ptr_array(dln) if lnc else None
+        ws, ws_bytes = workspace(dev, L.vpx_acstlstm_workspace_bytes, ctypes.byref(d))
         check(L.vpx_acstlstm_step_bwd(ctypes.byref(d), ptr(xs), ptr(hs), ptr(cs), ptr(ms), ptr(as_), p_arr, ln_arr, ptr(reserve), ctx.rs_bytes,
-                                      *[ptr(g) for g in gin], *[ptr(t) for t in dins], dp_arr, dln_arr, ptr(ws), ws_bytes, _stream()),
+                                      *[ptr(g) for g in gin], *[ptr(t) for t in dins], dp_arr, dln_arr, ptr(ws), ws_bytes, stream()),
               "vpx_acstlstm_step_bwd")
         return (*dins, None, None, *dprm, *dln)
 

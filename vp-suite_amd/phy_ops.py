@@ -10,11 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
-from .ops import _require_gpu, _stream, _sync_determinism, new_channels_last, to_channels_last
-
-
-def _needs_grad(*tensors):
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+from .ops import needs_grad, new_channels_last, require_gpu, stream, sync_determinism, to_channels_last, workspace
 
 
 # ---- GroupNorm ------------------------------------------------------------------------------------------------------------------
@@ -28,7 +24,7 @@ class _GroupNormFn(torch.autograd.Function):
         stats = torch.empty(N * G * 2, device=x.device)
         gc, bc = gamma.contiguous(), beta.contiguous()
         check(_lib.lib().vpx_groupnorm_fwd(ptr(xs), ptr(gc), ptr(bc), ptr(rs), ptr(y), ptr(stats), N, H * W, C, G, int(act), float(slope),
-                                           _stream()), "vpx_groupnorm_fwd")
+                                           stream()), "vpx_groupnorm_fwd")
         if need_grad:
             ctx.save_for_backward(xs, stats, gc, bc)
             ctx.cfg = (G, int(act), float(slope), r is not None)
@@ -36,7 +32,7 @@ class _GroupNormFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        _sync_determinism()
+        sync_determinism()
         xs, stats, gc, bc = ctx.saved_tensors
         G, act, slope, has_r = ctx.cfg
         N, C, H, W = xs.shape
@@ -46,10 +42,9 @@ class _GroupNormFn(torch.autograd.Function):
         want_param = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         dg = torch.empty(C, device=dy.device) if want_param else None
         db = torch.empty(C, device=dy.device) if want_param else None
-        ws_bytes = L.vpx_groupnorm_bwd_workspace_bytes(N, C) if want_param else 0
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dy.device) if want_param else None
+        ws, ws_bytes = workspace(dy.device, L.vpx_groupnorm_bwd_workspace_bytes, N, C) if want_param else (None, 0)
         check(L.vpx_groupnorm_bwd(ptr(xs), ptr(stats), ptr(gc), ptr(bc), ptr(dys), ptr(dx), ptr(dg), ptr(db), N, H * W, C, G, act, slope,
-                                  ptr(ws), ws_bytes, _stream()), "vpx_groupnorm_bwd")
+                                  ptr(ws), ws_bytes, stream()), "vpx_groupnorm_bwd")
         dr = dy if (has_r and ctx.needs_input_grad[3]) else None
         return dx, dg, db, dr, None, None, None, None
 
@@ -59,7 +54,7 @@ def group_norm(x, num_groups, weight, bias, leaky_slope=None, residual=None):
     GPU (any memory layout; the output is channels-last)."""
     for t in (x, weight, bias, residual):
         if t is not None:
-            _require_gpu(t, "group_norm")
+            require_gpu(t, "group_norm")
     if x.dim() != 4:
         raise ValueError(f"group_norm: expected a [N,C,H,W] tensor, got shape {tuple(x.shape)}")
     C = int(x.shape[1])
@@ -75,7 +70,7 @@ def group_norm(x, num_groups, weight, bias, leaky_slope=None, residual=None):
     if act and leaky_slope < 0.0:
         raise ValueError("group_norm: the LeakyReLU slope must be non-negative (the backward reads its derivative from the sign)")
     return _GroupNormFn.apply(x, weight, bias, residual, int(num_groups), act, float(leaky_slope or 0.0),
-                              _needs_grad(x, weight, bias, residual))
+                              needs_grad(x, weight, bias, residual))
 
 
 # ---- PhyCell correction ----------------------------------------------------------------------------------------------------------
@@ -84,7 +79,7 @@ class _PhyCellCorrectFn(torch.autograd.Function):
     def forward(ctx, G, Fh, h, E, need_grad):
         ts = [to_channels_last(t) for t in (G, Fh, h, E)]
         nxt = new_channels_last(tuple(G.shape), G.device)
-        check(_lib.lib().vpx_phycell_correct_fwd(*[ptr(t) for t in ts], ptr(nxt), nxt.numel(), _stream()), "vpx_phycell_correct_fwd")
+        check(_lib.lib().vpx_phycell_correct_fwd(*[ptr(t) for t in ts], ptr(nxt), nxt.numel(), stream()), "vpx_phycell_correct_fwd")
         if need_grad:
             ctx.save_for_backward(*ts)
         return nxt
@@ -94,21 +89,21 @@ class _PhyCellCorrectFn(torch.autograd.Function):
         ts = ctx.saved_tensors
         dns = to_channels_last(dn)
         outs = [new_channels_last(tuple(ts[0].shape), dn.device) if ctx.needs_input_grad[i] else None for i in range(4)]
-        check(_lib.lib().vpx_phycell_correct_bwd(*[ptr(t) for t in ts], ptr(dns), *[ptr(o) for o in outs], dns.numel(), _stream()),
+        check(_lib.lib().vpx_phycell_correct_bwd(*[ptr(t) for t in ts], ptr(dns), *[ptr(o) for o in outs], dns.numel(), stream()),
               "vpx_phycell_correct_bwd")
         return (*outs, None)
 
 
 def phycell_correct(G, Fh, h, E):
     """PhyCell_Cell's update: ht = h + Fh, next = ht + sigmoid(G) * (E - ht). Four [B,C,H,W] tensors of one shape."""
-    _require_gpu(G, "phycell_correct")
+    require_gpu(G, "phycell_correct")
     for name, t in (("F(h)", Fh), ("h", h), ("E", E)):
         if tuple(t.shape) != tuple(G.shape):
             raise ValueError(f"phycell_correct: {name} {tuple(t.shape)} does not match the gate {tuple(G.shape)}")
-        _require_gpu(t, "phycell_correct")
+        require_gpu(t, "phycell_correct")
     if G.dim() != 4:
         raise ValueError(f"phycell_correct: expected [B,C,H,W] tensors, got shape {tuple(G.shape)}")
-    return _PhyCellCorrectFn.apply(G, Fh, h, E, _needs_grad(G, Fh, h, E))
+    return _PhyCellCorrectFn.apply(G, Fh, h, E, needs_grad(G, Fh, h, E))
 
 
 # ---- moment loss -----------------------------------------------------------------------------------------------------------------
@@ -118,7 +113,7 @@ class _MomentLossFn(torch.autograd.Function):
         Wc = W.contiguous()
         hidden, Cin, kh, kw = (int(s) for s in Wc.shape)
         loss = torch.empty((), device=W.device)
-        check(_lib.lib().vpx_moment_loss_fwd(ptr(Wc), ptr(loss), hidden, Cin, kh, kw, float(scale), _stream()), "vpx_moment_loss_fwd")
+        check(_lib.lib().vpx_moment_loss_fwd(ptr(Wc), ptr(loss), hidden, Cin, kh, kw, float(scale), stream()), "vpx_moment_loss_fwd")
         if need_grad:
             ctx.save_for_backward(Wc)
             ctx.scale = float(scale)
@@ -130,17 +125,17 @@ class _MomentLossFn(torch.autograd.Function):
         hidden, Cin, kh, kw = (int(s) for s in Wc.shape)
         dl = dloss.detach().to(torch.float32).contiguous()
         dW = torch.empty_like(Wc)
-        check(_lib.lib().vpx_moment_loss_bwd(ptr(Wc), ptr(dl), ptr(dW), hidden, Cin, kh, kw, ctx.scale, _stream()), "vpx_moment_loss_bwd")
+        check(_lib.lib().vpx_moment_loss_bwd(ptr(Wc), ptr(dl), ptr(dW), hidden, Cin, kh, kw, ctx.scale, stream()), "vpx_moment_loss_bwd")
         return dW, None, None
 
 
 def moment_loss(W, scale=1.0):
     """scale * sum_b mean((K2M(W[:, b]) - C)^2) for the PhyCell filter bank W [hidden, Cin, kh, kw] (phydnet.py PhyDNet.forward),
     evaluated in fp64 in one launch. C[o, i, j] = 1 where o == i * kw + j."""
-    _require_gpu(W, "moment_loss")
+    require_gpu(W, "moment_loss")
     if W.dim() != 4 or W.shape[2] > 8 or W.shape[3] > 8:
         raise ValueError(f"moment_loss: expected a [hidden, Cin, kh, kw] filter bank with kh, kw <= 8, got {tuple(W.shape)}")
-    return _MomentLossFn.apply(W, float(scale), _needs_grad(W))
+    return _MomentLossFn.apply(W, float(scale), needs_grad(W))
 
 
 # ---- sigmoid output head ---------------------------------------------------------------------------------------------------------
@@ -158,7 +153,7 @@ class _SigmoidHeadFn(torch.autograd.Function):
     def forward(ctx, x, nT, need_grad):
         xs, (B, C, H, W) = _head_frames(x, nT)
         out = torch.empty(B, nT, C, H, W, device=x.device)
-        check(_lib.lib().vpx_sigmoid_head_fwd(ptr(xs), ptr(out), B, nT, 0, nT, C, H, W, _stream()), "vpx_sigmoid_head_fwd")
+        check(_lib.lib().vpx_sigmoid_head_fwd(ptr(xs), ptr(out), B, nT, 0, nT, C, H, W, stream()), "vpx_sigmoid_head_fwd")
         if need_grad:
             ctx.save_for_backward(out)
             ctx.xshape = tuple(xs.shape)
@@ -169,7 +164,7 @@ class _SigmoidHeadFn(torch.autograd.Function):
         (out,) = ctx.saved_tensors
         B, nT, C, H, W = out.shape
         dx = new_channels_last(ctx.xshape, dout.device)
-        check(_lib.lib().vpx_sigmoid_head_bwd(ptr(out), ptr(dout.contiguous()), ptr(dx), B, nT, 0, nT, C, H, W, _stream()),
+        check(_lib.lib().vpx_sigmoid_head_bwd(ptr(out), ptr(dout.contiguous()), ptr(dx), B, nT, 0, nT, C, H, W, stream()),
               "vpx_sigmoid_head_bwd")
         return dx, None, None
 
@@ -178,17 +173,17 @@ def sigmoid_head(x, n_frames=1, out=None, t0=0):
     """sigmoid of the decoder's output. x: [n_frames*B, C, H, W], frame-major. With `out` ([B, T, C, H, W], contiguous) and no gradient
     needed, the frames are written straight into out[:, t0:t0+n_frames] and that view is returned; otherwise a new [B, n_frames, C, H, W]
     tensor is returned (differentiable)."""
-    _require_gpu(x, "sigmoid_head")
+    require_gpu(x, "sigmoid_head")
     if out is not None:
-        _require_gpu(out, "sigmoid_head")
+        require_gpu(out, "sigmoid_head")
     if x.dim() != 4:
         raise ValueError(f"sigmoid_head: expected a [N,C,H,W] tensor, got shape {tuple(x.shape)}")
-    if out is not None and not _needs_grad(x):
+    if out is not None and not needs_grad(x):
         xs, (B, C, H, W) = _head_frames(x, n_frames)
         if out.dim() != 5 or tuple(out.shape[:1]) + tuple(out.shape[2:]) != (B, C, H, W) or not out.is_contiguous() \
                 or not 0 <= t0 <= out.shape[1] - n_frames:
             raise ValueError(f"sigmoid_head: result buffer {tuple(out.shape)} cannot take {n_frames} frames of {(B, C, H, W)} at slot {t0}")
-        check(_lib.lib().vpx_sigmoid_head_fwd(ptr(xs), ptr(out), B, int(out.shape[1]), int(t0), int(n_frames), C, H, W, _stream()),
+        check(_lib.lib().vpx_sigmoid_head_fwd(ptr(xs), ptr(out), B, int(out.shape[1]), int(t0), int(n_frames), C, H, W, stream()),
               "vpx_sigmoid_head_fwd")
         return out[:, t0:t0 + n_frames]
-    return _SigmoidHeadFn.apply(x, int(n_frames), _needs_grad(x))
+    return _SigmoidHeadFn.apply(x, int(n_frames), needs_grad(x))

@@ -12,8 +12,8 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import check, ptr
-from .ops import PRECISIONS, _require_gpu, _stream, _sync_determinism
+from ._lib import check, ptr, ptr_array
+from .ops import PRECISIONS, needs_grad, require_gpu, reserve_buffer, stream, sync_determinism, workspace
 
 FLOW_FEATURES = 32  # channels of the flow generator's hidden layer (traj_gru.py:108-122, fixed by the reference)
 
@@ -24,16 +24,12 @@ def _nhwc(t):
     return t.permute(*range(nd - 3), nd - 2, nd - 1, nd - 3).contiguous()
 
 
-def _ptr_array(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
-
-
 class _TrajGRUSeqFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, h0, i2h_w, i2h_b, i2f_w, i2f_b, h2f_w, h2f_b, fl_w, fl_b, ret_w, ret_b, seq_len, L, slope, precision,
                 need_grad, state_hw):
         ref = x if x is not None else h0
-        _require_gpu(ref, "trajgru_seq")
+        require_gpu(ref, "trajgru_seq")
         dev = ref.device
         C = ret_w.shape[0] // 3
         T = int(seq_len)
@@ -50,16 +46,12 @@ class _TrajGRUSeqFn(torch.autograd.Function):
         params = [t.contiguous() for t in (i2h_w, i2h_b, i2f_w, i2f_b, h2f_w, h2f_b, fl_w, fl_b, ret_w, ret_b)]
         d = _lib.TrajGRUDesc(B, T, Cin, C, H, W, int(L), int(i2h_w.shape[-1]), precision, _lib.FLAG_SAVE_FOR_BWD if need_grad else 0, float(slope))
         Lb = _lib.lib()
-        ws_bytes = Lb.vpx_trajgru_workspace_bytes(ctypes.byref(d))
-        if ws_bytes == 0:
-            check(-4 if b"must be" in Lb.vpx_last_error() else -1, "vpx_trajgru_workspace_bytes")
-        rs_bytes = Lb.vpx_trajgru_reserve_bytes(ctypes.byref(d))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        reserve = torch.empty(max(rs_bytes, 1), dtype=torch.uint8, device=dev)
+        ws, ws_bytes = workspace(dev, Lb.vpx_trajgru_workspace_bytes, ctypes.byref(d), unsupported=b"must be")
+        reserve, rs_bytes = reserve_buffer(dev, Lb.vpx_trajgru_reserve_bytes, d)
         h_init = _nhwc(h0) if h0 is not None else None
         hs = torch.empty(T, B, H, W, C, device=dev, dtype=torch.float32)   # h_1 .. h_T, time-major
-        check(Lb.vpx_trajgru_seq_fwd(ctypes.byref(d), ptr(x_tm), ptr(h_init), _ptr_array(params), ptr(hs), ptr(reserve), rs_bytes,
-                                     ptr(ws), ws_bytes, _stream()), "vpx_trajgru_seq_fwd")
+        check(Lb.vpx_trajgru_seq_fwd(ctypes.byref(d), ptr(x_tm), ptr(h_init), ptr_array(params), ptr(hs), ptr(reserve), rs_bytes,
+                                     ptr(ws), ws_bytes, stream()), "vpx_trajgru_seq_fwd")
         out = hs.permute(1, 0, 4, 2, 3)                          # [B,T,C,H,W] view of the time-major slab
         hT = hs[T - 1].permute(0, 3, 1, 2)
         if need_grad:
@@ -69,7 +61,7 @@ class _TrajGRUSeqFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, dhT):
-        _sync_determinism()
+        sync_determinism()
         x_tm, h_init, hs, reserve, *params = ctx.saved_tensors
         d = ctx.desc
         dev = hs.device
@@ -82,10 +74,9 @@ class _TrajGRUSeqFn(torch.autograd.Function):
         dparams = [torch.empty_like(p) if (have_x or i >= 4) else None for i, p in enumerate(params)]
         dx_tm = torch.empty(T, B, H, W, Cin, device=dev, dtype=torch.float32) if (have_x and ctx.needs_input_grad[0]) else None
         dh0_n = torch.empty(B, H, W, C, device=dev, dtype=torch.float32) if (h_init is not None and ctx.needs_input_grad[1]) else None
-        ws_bytes = Lb.vpx_trajgru_workspace_bytes(ctypes.byref(d))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        check(Lb.vpx_trajgru_seq_bwd(ctypes.byref(d), ptr(x_tm), ptr(h_init), _ptr_array(params), ptr(hs), ptr(reserve), ctx.rs_bytes,
-                                     ptr(dout_tm), ptr(dhT_n), ptr(dx_tm), ptr(dh0_n), _ptr_array(dparams), ptr(ws), ws_bytes, _stream()),
+        ws, ws_bytes = workspace(dev, Lb.vpx_trajgru_workspace_bytes, ctypes.byref(d))
+        check(Lb.vpx_trajgru_seq_bwd(ctypes.byref(d), ptr(x_tm), ptr(h_init), ptr_array(params), ptr(hs), ptr(reserve), ctx.rs_bytes,
+                                     ptr(dout_tm), ptr(dhT_n), ptr(dx_tm), ptr(dh0_n), ptr_array(dparams), ptr(ws), ws_bytes, stream()),
               "vpx_trajgru_seq_bwd")
         dx = None if dx_tm is None else dx_tm.permute(1, 0, 4, 2, 3)
         dh0 = None if dh0_n is None else dh0_n.permute(0, 3, 1, 2)
@@ -99,5 +90,5 @@ def trajgru_seq(x, h0, params, *, seq_len, L, slope, state_hw, precision="f32"):
         raise ValueError("TrajGRU received 'None' both in input and state")
     if x is not None and x.shape[1] > seq_len:
         x = x[:, :seq_len]
-    need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, h0, *params))
+    need_grad = needs_grad(x, h0, *params)
     return _TrajGRUSeqFn.apply(x, h0, *params, int(seq_len), int(L), float(slope), PRECISIONS[precision], need_grad, tuple(state_hw))
