@@ -21,6 +21,8 @@
  * vpx_conv2d_ex_fwd / _bwd         Conv2d / ConvTranspose2d + LeakyReLU     vp_suite/models/precipitation_nowcasting/ef_blocks.py:15-49
  * vpx_mse_loss                     MSE measure + loss provider              vp_suite/base/base_measure.py:55-57, measure/loss_provider.py:48-51
  * vpx_adam_step                    torch.optim.Adam(model.parameters(), lr)  vp_suite/vpsuite.py:353, base/base_model.py:174-176
+ * vpx_pixel_measures_fwd / _bwd    MSE, L1, SmoothL1, PSNR per frame         vp_suite/measure/image_wise.py:19-71
+ * vpx_ssim_fwd / _bwd              SSIM per frame (piqa defaults)           vp_suite/measure/image_wise.py:99-117
  * vpx_groupnorm_fwd / _bwd         GroupNorm + LeakyReLU (DCGAN layers)     vp_suite/model_blocks/conv.py, model_blocks/phydnet.py
  * vpx_phycell_correct_fwd / _bwd   PhyCell_Cell prediction-correction       vp_suite/model_blocks/phydnet.py (PhyCell_Cell.forward)
  * vpx_moment_loss_fwd / _bwd       K2M + moment regularisation loss         vp_suite/models/phydnet.py (PhyDNet.forward)
@@ -251,6 +253,30 @@ int vpx_mse_loss(const float* pred, const float* target, long long n_elements, l
  * forms them in Python floats, and rounded to fp32 once. */
 int vpx_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, double lr,
                   double beta1, double beta2, double eps, double weight_decay, int step, double grad_scale, void* stream);
+
+/* ---- image-wise measures (vp_suite/measure/image_wise.py): per-frame tables that serve every reduction ------------
+ * All of them: double partial sums, fixed-order final reduction, no atomics (bit-reproducible in either determinism mode).
+ * pred / target: n_frames = B*T dense frames of frame_elems = C*H*W floats, in any per-frame element order both share.
+ * sums [3, n_frames] (doubles): per-frame sums of d^2, |d| and smooth-L1(d) (beta = 1), d = pred - target — the criteria of MSE, L1,
+ * SmoothL1 and PSNR (nn.*Loss(reduction="none"); base_measure.py:57 and image_wise.py:69-71 reduce them further).
+ * Backward: dsums [3, n_frames] (floats) = the cotangents of that table, read on the device (no host sync):
+ *   dpred = 2 dsums[0][f] d + dsums[1][f] sign(d) + dsums[2][f] clamp(d, -1, 1), sign(0) = 0; written out of place.
+ * A PSNR term reaches it through row 0: d/dSE_f of mean_f 10 log10(SE_f / frame_elems) is 10 / (ln10 n_frames SE_f). */
+size_t vpx_pixel_measures_workspace_bytes(long long n_frames, long long frame_elems);
+int vpx_pixel_measures_fwd(const float* pred, const float* target, long long n_frames, long long frame_elems, double* sums,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int vpx_pixel_measures_bwd(const float* pred, const float* target, const float* dsums, long long n_frames,
+                           long long frame_elems, float* dpred, void* stream);
+/* ssim [n_frames]: SSIM of each frame with piqa's SSIM() defaults (image_wise.py:111-117 after base_measure.py:71-74): inputs
+ * mapped by clamp((x+1)/2, 0, 1) inside the kernel, 11-tap Gaussian (sigma 1.5, sum 1) per channel without padding, C1 = 0.01^2,
+ * C2 = 0.03^2, mean over the 3 (H-10) (W-10) map entries. Frames are [3,H,W] (VPX_LAYOUT_NCHW) or [H,W,3] (VPX_LAYOUT_NHWC);
+ * C must be 3 and H, W >= 11 (VPX_ERR_ARG otherwise). Backward: dpred = dssim[f] * d ssim[f] / d pred, recomputed from the
+ * inputs (the forward saves nothing), including the clamp's derivative: 0.5 where -1 <= pred <= 1, else 0. No workspace. */
+size_t vpx_ssim_workspace_bytes(long long n_frames, int H, int W);
+int vpx_ssim_fwd(const float* pred, const float* target, long long n_frames, int C, int H, int W, int layout, float* ssim,
+                 void* workspace, size_t workspace_bytes, void* stream);
+int vpx_ssim_bwd(const float* pred, const float* target, const float* dssim, long long n_frames, int C, int H, int W,
+                 int layout, float* dpred, void* stream);
 
 /* ---- plain stride-1 "same" convolution, NHWC, optional bias; y [N,H,W,Co] = conv(x [N,H,W,Ci], w [Co,Ci,kh,kw]) --- */
 size_t vpx_conv2d_workspace_bytes(int Ci, int Co, int kh, int kw);

@@ -102,6 +102,13 @@ SIGNATURES = {
     "vpx_mse_loss_workspace_bytes": (sz, []),
     "vpx_mse_loss": (ci, [vp, vp, ll, ll, fl, vp, vp] + _ws),
     "vpx_adam_step": (ci, [vp] * 4 + [ll] + [dbl] * 5 + [ci, dbl, vp]),
+    # image-wise measures
+    "vpx_pixel_measures_workspace_bytes": (sz, [ll, ll]),
+    "vpx_pixel_measures_fwd": (ci, [vp, vp, ll, ll, vp] + _ws),
+    "vpx_pixel_measures_bwd": (ci, [vp, vp, vp, ll, ll, vp, vp]),
+    "vpx_ssim_workspace_bytes": (sz, [ll, ci, ci]),
+    "vpx_ssim_fwd": (ci, [vp, vp, ll] + [ci] * 4 + [vp] + _ws),
+    "vpx_ssim_bwd": (ci, [vp, vp, vp, ll] + [ci] * 4 + [vp, vp]),
     # plain stride-1 "same" convolution
     "vpx_conv2d_workspace_bytes": (sz, [ci] * 4),
     "vpx_conv2d_nhwc_fwd": (ci, [vp] * 4 + [ci] * 8 + _ws),

@@ -366,7 +366,8 @@ class PredRNN_V2(VPModel):
         if self.reverse_input and self.fuse_reversed_pass and acts_ok and reversed_pair[0].shape == inp.shape and \
                 reversed_pair[1].shape == targets.shape:
             # One batch of 2B: rows [0, B) the sequence, rows [B, 2B) its reversal. Exact: the samples of a batch only meet in the two
-            # batch MEANS of the loss — MSE (mean over b, t of the per-frame sum, base_measure.py:57) and the decoupling term (mean over
+            # batch MEANS of the loss — MSE (mean over b, t of the per-frame sum, base_measure.py:57; L1, SmoothL1, PSNR and SSIM are
+            # likewise means over b of means over t of a per-frame value, measure.py) and the decoupling term (mean over
             # b, channel, predrnn_v2.py:197-211, then over steps x layers) — and a mean over two halves of equal size is the average of
             # the halves' means, i.e. (total + total_rev) / 2 term by term. The sampling masks are drawn in the reference's order (the
             # forward pass's, then the reversed pass's: same RNG stream, same per-call decrement of sampling_eta); the actions go to

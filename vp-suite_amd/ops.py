@@ -807,6 +807,91 @@ def mse_loss(pred, target, scale: float = 1.0):
     return _MSELossFn.apply(pred, target, scale)
 
 
+def _frame_operands(pred, target, what):
+    """(pred, target, layout) for the per-frame measure kernels: [B,T] dense frames whose elements lie in the reference's order
+    (LAYOUT_NCHW) or channels-last (LAYOUT_NHWC). A prediction in either form is used as it is, anything else is made contiguous;
+    the target is brought to the prediction's strides, as in _MSELossFn."""
+    require_gpu(pred, what)
+    if pred.ndim != 5 or target.ndim != 5:
+        raise ValueError(f"{what} expects 5-D inputs!")
+    if pred.shape != target.shape:
+        raise ValueError("Output images and target images are of different shape!")
+    if pred.is_contiguous():
+        p, layout = pred, _lib.LAYOUT_NCHW
+    elif is_channels_last(pred):
+        p, layout = pred, _lib.LAYOUT_NHWC
+    else:
+        p, layout = pred.contiguous(), _lib.LAYOUT_NCHW
+    tg = target if (target.stride() == p.stride() and target.dtype == p.dtype and target.device == p.device) else torch.empty_like(p).copy_(target)
+    return p, tg, layout
+
+
+class _PixelMeasuresFn(torch.autograd.Function):
+    """[3, B, T] per-frame sums of d^2, |d| and smooth-L1(d), d = pred - target (image_wise.py:19-71 before their reductions). The
+    backward is ONE launch on the incoming cotangent table, whatever mix of MSE / L1 / SmoothL1 / PSNR terms produced it."""
+
+    @staticmethod
+    def forward(ctx, pred, target):
+        p, tg, _ = _frame_operands(pred, target, "pixel_measures")
+        B, T = p.shape[:2]
+        L = _lib.lib()
+        ws, ws_bytes = workspace(p.device, L.vpx_pixel_measures_workspace_bytes, B * T, p[0, 0].numel())
+        sums = torch.empty(3, B, T, device=p.device, dtype=torch.float64)   # (a PSNR term takes the logarithm of these)
+        check(L.vpx_pixel_measures_fwd(ptr(p), ptr(tg), B * T, p[0, 0].numel(), ptr(sums), ptr(ws), ws_bytes, stream()), "vpx_pixel_measures_fwd")
+        ctx.save_for_backward(p, tg)
+        return sums
+
+    @staticmethod
+    def backward(ctx, dsums):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        p, tg = ctx.saved_tensors
+        B, T = p.shape[:2]
+        g = torch.empty_like(p)   # out of place: a second backward through the same node (retain_graph) stays correct
+        dsums = dsums.float().contiguous()
+        check(_lib.lib().vpx_pixel_measures_bwd(ptr(p), ptr(tg), ptr(dsums), B * T, p[0, 0].numel(), ptr(g), stream()), "vpx_pixel_measures_bwd")
+        return g, None
+
+
+def pixel_measures(pred, target):
+    """[3, B, T] float64: per-frame sums over (c,h,w) of (pred - target)^2, |pred - target| and smooth-L1(pred - target)."""
+    return _PixelMeasuresFn.apply(pred, target)
+
+
+class _SSIMFramesFn(torch.autograd.Function):
+    """[B, T] SSIM of every frame (piqa's SSIM() defaults on clamp((x+1)/2, 0, 1), image_wise.py:111-117); the backward recomputes
+    the derivative maps from the inputs, nothing but the inputs is saved."""
+
+    @staticmethod
+    def forward(ctx, pred, target):
+        p, tg, layout = _frame_operands(pred, target, "ssim_frames")
+        B, T, C, H, W = p.shape
+        L = _lib.lib()
+        nbytes = workspace_bytes(L.vpx_ssim_workspace_bytes, B * T, H, W)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=p.device)   # (0: the launch reports the bad shape)
+        out = torch.empty(B, T, device=p.device)
+        check(L.vpx_ssim_fwd(ptr(p), ptr(tg), B * T, C, H, W, layout, ptr(out), ptr(ws), nbytes, stream()), "vpx_ssim_fwd")
+        ctx.save_for_backward(p, tg)
+        ctx.layout = layout
+        return out
+
+    @staticmethod
+    def backward(ctx, dssim):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        p, tg = ctx.saved_tensors
+        B, T, C, H, W = p.shape
+        g = torch.empty_like(p)
+        dssim = dssim.contiguous()
+        check(_lib.lib().vpx_ssim_bwd(ptr(p), ptr(tg), ptr(dssim), B * T, C, H, W, ctx.layout, ptr(g), stream()), "vpx_ssim_bwd")
+        return g, None
+
+
+def ssim_frames(pred, target):
+    """[B, T]: SSIM of each predicted frame against its target frame (3-channel frames of at least 11x11)."""
+    return _SSIMFramesFn.apply(pred, target)
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
     """One torch.optim.Adam update of flat fp32 buckets, in place (vpsuite.py:353; torch/optim/adam.py semantics)."""
     require_gpu(param, "adam_step")

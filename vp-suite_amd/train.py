@@ -21,7 +21,7 @@ the single-process gradient of the global batch."""
 import torch
 import torch.distributed as dist
 
-from .measure import PredictionLossProvider
+from .measure import PredictionLossProvider, mse_measure
 
 
 def shard_batch(t: torch.Tensor, rank: int, world_size: int) -> torch.Tensor:
@@ -319,7 +319,10 @@ class DataParallelTrainer:
     def validate(self, batches, pred_frames: int):
         """Mean validation MSE over `batches` of (x, target), averaged over ranks; steps the LR scheduler."""
         self.model.eval()
-        vals = [self.loss_provider.get_losses(self.model(x, pred_frames=pred_frames)[0], y)[0]["mse"] for x, y in batches]
+        def mse(pred, y):   # a provider configured without "mse" still validates on it
+            disp = self.loss_provider.get_losses(pred, y)[0]
+            return disp["mse"] if "mse" in disp else mse_measure(pred, y)
+        vals = [mse(self.model(x, pred_frames=pred_frames)[0], y) for x, y in batches]
         self.model.train()
         v = torch.stack(vals).mean()
         if self.world > 1:
