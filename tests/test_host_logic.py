@@ -27,6 +27,16 @@ def test_library_exports_every_declared_symbol(vpx):
     assert L.vpx_version() == 100
 
 
+def test_library_never_reads_the_process_environment(vpx):
+    """Kernel selection depends on the descriptor, vpx_set_option and vpx_set_deterministic only: libvpx_hip.so imports neither
+    getenv nor secure_getenv (`nm -D --undefined-only`)."""
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--undefined-only", vpx._lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    imported = {ln.split()[-1].split("@")[0] for ln in out.splitlines() if ln.strip()}
+    assert "hipLaunchKernel" in imported, "undefined dynamic symbols not parsed"
+    assert not imported & {"getenv", "secure_getenv"}
+
+
 def test_binding_argument_counts_match_the_header(vpx):
     """Every prototype of include/vpx.h has as many parameters as the bound function has argtypes (`(void)` = none): a miscounted
     ctypes argument list would hand a launcher garbage without any error."""

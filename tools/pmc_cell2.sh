@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs ON THE GPU BOX: separate --pmc passes (kernel-trace only) over tools/pmc_cell.py for the cell kernel selected by
-# VPX_CELL2 (2 = second generation, 0 = first); BB = batch. Output: gpurun_out/pmc_cell2_<tag>/summary.txt
+# EXP (bits of VPX_OPT_EXPERIMENT); BB = batch. Output: $OUT/summary.txt (OUT below)
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 TAG=${1:-gen2}

@@ -126,21 +126,6 @@ size_t cell2_packed_bytes(int n_tiles, int chunks_total) { return (size_t)n_tile
 size_t cell2_packed_bytes_q(int n_tiles, int S) { return (size_t)n_tiles * cell2_qchunks(S) * CQ_WCHUNK; }
 
 // ---------------------------------------------------------------------------------------------------------------
-#ifdef VPX_ABLATE
-// developer build only (make ablate): per-wave s_memtime stamps of ONE workgroup (block id = Cell2Plan::_p), read back with
-// vpx_dbg_cell2_stamps(). Never compiled into the product library.
-__device__ unsigned long long c2_stamps[8 * 64];
-// ... and of EVERY workgroup of a half-tile q-form launch: start, loop end, end (s_memtime) and HW_ID | XCC_ID << 32 — which workgroups shared
-// a CU and in what phase relation (tools/trace_cell2q.py); vpx_dbg_cell2_trace() reads it back.
-__device__ unsigned long long c2_trace[8192 * 4];
-#define C2_TRACE(k) do { if (wave == 0 && lane == 0 && L < 8192) c2_trace[L * 4 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define C2_STAMP(slot) do { if (stamp_on && lane == 0) c2_stamps[wave * 64 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define C2_EPI_STAMP(slot) do { if (stamp_on && (lane & 63) == 0) c2_stamps[(prow >> 2) * 64 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define C2_STAMP(slot) do { } while (0)
-#define C2_EPI_STAMP(slot) do { } while (0)
-#define C2_TRACE(k) do { } while (0)
-#endif
 
 // The ConvLSTM epilogue (conv_lstm_hzzone.py:62-68), plus the split copy of h_t for the next step / the weight gradient.
 // Addressing: one 24-bit multiply per pixel (pixel index x Ch), every array is a wave-uniform base + that 32-bit element
@@ -273,8 +258,7 @@ struct Cell2Epi {
         // (LDS operations of one wave execute in order: vec_math's reads see these writes without a barrier)
     }
 
-    // (ab: timing-only ablations of the developer build — experiment bits 17 = no stores, 26 = no transcendentals; results are garbage)
-    __device__ __forceinline__ void vec_math(const VecIn& v, const char* lds, int b, int n_tile, int lane, int H, int W, int ab = 0) const {
+    __device__ __forceinline__ void vec_math(const VecIn& v, const char* lds, int b, int n_tile, int lane, int H, int W) const {
         const unsigned Ch = (unsigned)a.Ch;
         const float* ldsf = reinterpret_cast<const float*>(lds);
         const int cg = lane & 7, p4 = lane >> 3;
@@ -302,13 +286,6 @@ struct Cell2Epi {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float c0 = v.cp[k][e];
-#ifdef VPX_ABLATE
-                if (ab & (1 << 26)) {
-                    i4[e] = ai[e] + bi[e] + v.wi[k][e] * c0; f4[e] = af[e] + bf[e] + v.wf[k][e] * c0; g4[e] = ag[e] + bg[e];
-                    cn[e] = lstm_c(f4[e], c0, i4[e], g4[e]); o4[e] = ao[e] + bo[e] + v.wo[k][e] * cn[e]; hn[e] = o4[e] * cn[e];
-                    continue;
-                }
-#endif
                 i4[e] = sigmoid_f(ai[e] + bi[e] + v.wi[k][e] * c0);
                 f4[e] = sigmoid_f(af[e] + bf[e] + v.wf[k][e] * c0);
                 g4[e] = tanh_f(ag[e] + bg[e]);
@@ -317,9 +294,6 @@ struct Cell2Epi {
                 hn[e] = o4[e] * tanh_f(cn[e]);
             }
             const unsigned eo = v.eo[k];
-#ifdef VPX_ABLATE
-            if (ab & (1 << 17)) { if (cn[0] + hn[1] + i4[2] + f4[3] + g4[0] + o4[1] == 1.2345e-30f) cout_b[eo] = 0.f; continue; }
-#endif
             *reinterpret_cast<f32x4*>(cout_b + eo) = cn;
             if (a.h_out) *reinterpret_cast<f32x4*>(hout_b + eo) = hn;   // (null: the consumer reads the split copy below — VPX_FLAG_OUT_SPLIT)
             if (g0) {
@@ -363,60 +337,38 @@ struct Cell2Epi {
 
     // (the q form is only selected for tiles inside the image and whole 32-channel tiles: cell2_q_applicable)
     __device__ __forceinline__ void finish16(const f32x4 (&acc)[4][8], char* smem, int wave, int lane, int b, int y0, int x0, int n_tile,
-                                             int /*ngr*/, int H, int W, bool stamp_on = false, int ab = 0) const {
+                                             int /*ngr*/, int H, int W) const {
         const int prow = 4 * wave;
         char* const lds = smem + wave * 16384;
         VecIn v0, v1;
-#ifdef VPX_ABLATE
-        if (ab & (1 << 18)) {   // timing only: no epilogue (one never-taken store keeps the accumulators alive)
-            float t = 0.f;
-            for (int m = 0; m < 4; ++m) for (int nt = 0; nt < 8; ++nt) for (int r = 0; r < 4; ++r) t += acc[m][nt][r];
-            if (t == 1.2345e-30f) a.c_out[0] = t;
-            return;
-        }
-#endif
-        C2_EPI_STAMP(43);
         vec_load<false>(v0, b, y0, x0, n_tile, prow, lane, H, W);
-        C2_EPI_STAMP(44);
         c2_barrier();   // every wave has read its last fragments: the staging buffers become the epilogue's transposition space
-        C2_EPI_STAMP(45);
         vec_put16(acc, 0, lds, lane);
-        C2_EPI_STAMP(46);
         vec_load<false>(v1, b, y0, x0, n_tile, prow + 2, lane, H, W);
-        C2_EPI_STAMP(47);
-        vec_math(v0, lds, b, n_tile, lane, H, W, ab);
-        C2_EPI_STAMP(48);
+        vec_math(v0, lds, b, n_tile, lane, H, W);
         vec_put16(acc, 1, lds, lane);
-        C2_EPI_STAMP(49);
-        vec_math(v1, lds, b, n_tile, lane, H, W, ab);
-        C2_EPI_STAMP(50);
-        (void)stamp_on;
+        vec_math(v1, lds, b, n_tile, lane, H, W);
     }
 
     __device__ __forceinline__ void finish(const f32x16 (&acc)[2][4], char* smem, int wave, int lane, int b, int y0, int x0, int n_tile,
-                                           int /*ngr*/, int H, int W, bool stamp_on = false) const {
+                                           int /*ngr*/, int H, int W) const {
         const int j = lane & 31, hh = lane >> 5;
         const bool full = y0 + 32 <= H && x0 + 16 <= W;
         const bool vec = full && n_tile * 32 + 32 <= a.Ch && (a.Ch & 3) == 0;
         if (vec) {
-            // Order matters (in-kernel stamps, 158 k-cycle tile: the epilogue took 17-21 k, of which 2.7 + 4.2 k were the two
+            // Order matters (in-kernel clock readings, 158 k-cycle tile: the epilogue took 17-21 k, of which 2.7 + 4.2 k were the two
             // sub-tiles' waits for their state / peephole loads): sub-tile 0's loads go out BEFORE the barrier and the LDS
             // round trip, sub-tile 1's before sub-tile 0's arithmetic — their latency runs under work that does not need them.
-            const int prow = 4 * wave;   // (also the stamp row of C2_EPI_STAMP)
+            const int prow = 4 * wave;
             char* const lds = smem + wave * 16384;
             VecIn v0, v1;
-            C2_EPI_STAMP(43);
             vec_load(v0, b, y0, x0, n_tile, prow, lane, H, W);
             c2_barrier();   // every wave has read its last fragments: the staging buffers become the epilogue's transposition space
-            C2_EPI_STAMP(44);
             vec_put(acc[0], lds, lane);
             vec_load(v1, b, y0, x0, n_tile, prow + 2, lane, H, W);
-            C2_EPI_STAMP(45);
             vec_math(v0, lds, b, n_tile, lane, H, W);
-            C2_EPI_STAMP(46);
             vec_put(acc[1], lds, lane);
             vec_math(v1, lds, b, n_tile, lane, H, W);
-            C2_EPI_STAMP(47);
             return;
         }
 #pragma unroll
@@ -424,7 +376,6 @@ struct Cell2Epi {
             if (full) run<true>(acc[m], b, y0, x0, n_tile, 4 * wave + 2 * m, j, hh, H, W);
             else run<false>(acc[m], b, y0, x0, n_tile, 4 * wave + 2 * m, j, hh, H, W);
         }
-        (void)stamp_on;
     }
 };
 
@@ -557,10 +508,6 @@ __global__ __launch_bounds__(512, 2) void cell2_kernel(const Cell2Plan P, const 
 
     char* const Abuf = smem;
     char* const Wbuf = smem + 2 * C2_ABUF;
-#ifdef VPX_ABLATE
-    const bool stamp_on = (int)L == P._p;
-#endif
-    C2_STAMP(0);
 
     // this thread's five pieces of an activation stage: piece = tid + 512 u -> (plane, halo position)
     int pixoff[5], choff[5];
@@ -579,7 +526,7 @@ __global__ __launch_bounds__(512, 2) void cell2_kernel(const Cell2Plan P, const 
 
     // one 16-byte piece per call: the copies of a sync point are spread over the following gate groups (one or two pieces
     // behind each group's MFMAs) instead of issued as a burst — a burst right after the barrier kept all eight waves off
-    // the matrix pipe for the 0.3-0.8k cycles the 3-8 LDS-DMA issues take (measured with in-kernel stamps)
+    // the matrix pipe for the 0.3-0.8k cycles the 3-8 LDS-DMA issues take (measured with in-kernel clock readings)
     // scalars of a stage (wave-uniform arithmetic on kernel arguments, no memory access)
     const int nx = P.nx, S = P.nx + P.nh;
     const char* const xb = P.seg[0].sp + (size_t)b * P.seg[0].bstride;
@@ -643,10 +590,8 @@ __global__ __launch_bounds__(512, 2) void cell2_kernel(const Cell2Plan P, const 
         issue_A(0, 0);
         issue_W(stage_chunk0(0), 0);
         issue_W(stage_chunk0(0) + 1, 1);
-        C2_STAMP(1);
         C2_WAIT_VM(3);  // stage 0 and chunk 0 have landed (chunk 1 may still fly)
         c2_barrier();
-        C2_STAMP(2);
         load_A(Abuf + a_lane, 0, 0);
         load_B(Wbuf + w_lane, 0, 0);
     }
@@ -665,11 +610,8 @@ __global__ __launch_bounds__(512, 2) void cell2_kernel(const Cell2Plan P, const 
                 const int dx = n >> 2, g = n & 3;
                 if (n == 8) {
                     // ---- sync point P_c ----
-                    if (s < 3) C2_STAMP(3 + (s * 3 + dy) * 3);
                     if (dy == 1 && more) C2_WAIT_VM(5); else C2_WAIT_VM(0);   // dy == 1: stage s+1's tile may still fly
-                    if (s < 3) C2_STAMP(4 + (s * 3 + dy) * 3);
                     c2_barrier();
-                    if (s < 3) C2_STAMP(5 + (s * 3 + dy) * 3);
                 }
                 // ---- fragments of the next gate group ----
                 if (n < 11) {
@@ -712,13 +654,7 @@ __global__ __launch_bounds__(512, 2) void cell2_kernel(const Cell2Plan P, const 
             }
         }
     }
-    C2_STAMP(40);
-#ifdef VPX_ABLATE
-    epi.finish(acc, smem, wave, lane, b, y0, x0, n_tile, ngr, P.H, P.W, stamp_on);
-#else
     epi.finish(acc, smem, wave, lane, b, y0, x0, n_tile, ngr, P.H, P.W);
-#endif
-    C2_STAMP(42);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -787,15 +723,6 @@ __global__ __launch_bounds__(64 * NW, 2) void cell2_kernel_q(const Cell2Plan P, 
     int ngr = 4;
     if constexpr (!ALLG) { ngr = P.n_groups - n_tile * P.gpt; if (ngr > P.gpt) ngr = P.gpt; }
 
-#ifdef VPX_ABLATE
-    if (wave == 0 && lane == 0 && L < 8192) {
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        c2_trace[L * 4 + 3] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
-    }
-#endif
-    C2_TRACE(0);
     char* const Abuf = smem;
     char* const Wbuf = smem + 2 * G::ABUF;
 
@@ -832,10 +759,6 @@ __global__ __launch_bounds__(64 * NW, 2) void cell2_kernel_q(const Cell2Plan P, 
                      Wbuf + slot * CQ_WCHUNK + half * 8192 + w * (G::NT * 16) + dma_off);
     };
 
-#ifdef VPX_ABLATE
-    const bool stamp_on = (int)L == P._p;
-#endif
-    C2_STAMP(0);
     f32x4 acc[4][8];
 #pragma unroll
     for (int m = 0; m < 4; ++m)
@@ -880,9 +803,7 @@ __global__ __launch_bounds__(64 * NW, 2) void cell2_kernel_q(const Cell2Plan P, 
             if constexpr (NW == 8) issue_Wh(1, 1, 1);
             if constexpr (PLAIN) C2_WAIT_VM(1); else C2_WAIT_VM(2);
         } else C2_WAIT_VM(0);
-        C2_STAMP(1);
         c2_barrier();
-        C2_STAMP(2);
 #pragma unroll
         for (int m = 0; m < 4; ++m) load_A1(0, m, a_lane);
         load_B(0, 0);
@@ -983,19 +904,7 @@ __global__ __launch_bounds__(64 * NW, 2) void cell2_kernel_q(const Cell2Plan P, 
         }
         if constexpr (NW == 4) { const int t = wb0; wb0 = wb1; wb1 = t; }
     }
-    C2_STAMP(40);
-    C2_TRACE(1);
-#ifdef VPX_ABLATE
-    if constexpr (std::is_same<Epi, Cell2Epi>::value) epi.finish16(acc, smem, wave, lane, b, y0, x0, n_tile, ngr, P.H, P.W, stamp_on, P._q);
-    else
-#endif
     epi.finish16(acc, smem, wave, lane, b, y0, x0, n_tile, ngr, P.H, P.W);
-    C2_STAMP(41);
-#ifdef VPX_ABLATE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // how long the epilogue's stores take to complete
-#endif
-    C2_STAMP(42);
-    C2_TRACE(2);
 }
 
 // Half tile (cell2_kernel_q<.., 4>: 16x16-pixel tiles, two workgroups per CU) or the 32x16 tile? Measured (tools/ab_exp.py,
@@ -1024,9 +933,6 @@ static hipError_t launch_cell2_t(const Cell2Plan& plan, const Epi& epi, hipStrea
     p.grid_m = plan.B * plan.tiles_x * plan.tiles_y;
     if (plan.qform) {
         p._q = g_experiment;
-#ifdef VPX_ABLATE
-        p._p = dev_switch("VPX_C2_STAMP_BLOCK", -1);
-#endif
         if (plan.plain || cell2_half_tile(p, std::is_same<Epi, Conv2Epi>::value)) {
             p.tiles_y = (p.H + 15) / 16;
             p.grid_m = p.B * p.tiles_x * p.tiles_y;
@@ -1044,14 +950,6 @@ static hipError_t launch_cell2_t(const Cell2Plan& plan, const Epi& epi, hipStrea
                 }
             }
             if (plan.plain) return hipErrorInvalidValue;   // (only the fused cell step has the plain form)
-#ifdef VPX_ABLATE
-            if (g_experiment & (1 << 19)) {   // timing only: ONE workgroup per CU (an LDS request above half a CU's)
-                static bool attr_big = false;
-                if (!attr_big) { vpx_func_attr(reinterpret_cast<const void*>(&cell2_kernel_q<Epi, ALLG, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024); attr_big = true; }
-                VPX_LAUNCH((cell2_kernel_q<Epi, ALLG, 4>), dim3((unsigned)(per_xcd_h * 8)), dim3(256), 100 * 1024, s, p, epi);
-                return vpx_hip_last_error();
-            }
-#endif
             VPX_LAUNCH((cell2_kernel_q<Epi, ALLG, 4>), dim3((unsigned)(per_xcd_h * 8)), dim3(256), CQGeom<4>::LDS, s, p, epi);
             return vpx_hip_last_error();
         }
@@ -1059,9 +957,6 @@ static hipError_t launch_cell2_t(const Cell2Plan& plan, const Epi& epi, hipStrea
         VPX_LAUNCH((cell2_kernel_q<Epi, ALLG, 8>), dim3((unsigned)(per_xcd_q * 8)), dim3(512), CQGeom<8>::LDS, s, p, epi);
         return vpx_hip_last_error();
     }
-#ifdef VPX_ABLATE
-    p._p = dev_switch("VPX_C2_STAMP_BLOCK", -1);
-#endif
     const long long per_xcd = ((long long)p.grid_m * p.n_tiles + 7) / 8;
     VPX_LAUNCH((cell2_kernel<Epi, ALLG>), dim3((unsigned)(per_xcd * 8)), dim3(512), C2_LDS, s, p, epi);
     return vpx_hip_last_error();
@@ -1166,11 +1061,3 @@ hipError_t launch_conv2(const Conv2Args& c, hipStream_t s) {
 
 }  // namespace vpx
 
-#ifdef VPX_ABLATE
-extern "C" int vpx_dbg_cell2_trace(unsigned long long* out32768) {
-    return (int)hipMemcpyFromSymbol(out32768, HIP_SYMBOL(vpx::c2_trace), sizeof(unsigned long long) * 8192 * 4);
-}
-extern "C" int vpx_dbg_cell2_stamps(unsigned long long* out512) {
-    return (int)hipMemcpyFromSymbol(out512, HIP_SYMBOL(vpx::c2_stamps), sizeof(unsigned long long) * 512);
-}
-#endif

@@ -50,14 +50,6 @@ __device__ __forceinline__ void cx_dma16_masked(const char* sbase, unsigned voff
     asm volatile("s_mov_b64 %0, exec\n\ts_and_b64 exec, exec, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b64 exec, %0"
                  : "=&s"(keep) : "v"(voff), "s"(cx_uniform(sbase)), "{m0}"(__builtin_amdgcn_readfirstlane(lds)), "s"(lanes) : "memory", "scc");
 }
-#ifdef VPX_ABLATE
-// developer build only (make ablate): per-workgroup s_memtime stamps of wave 0 — start, first MFMA, loop end, end — and HW_ID | XCC_ID << 32
-// (tools/trace_cell2x.py); vpx_dbg_cell2x_trace() reads them back. Never compiled into the product library.
-__device__ unsigned long long cx_trace[8192 * 8];
-#define CX_TRACE(k) do { if (wave == 0 && lane == 0 && L < 8192) cx_trace[L * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define CX_TRACE(k) do { } while (0)
-#endif
 template <int N> __device__ __forceinline__ void cx_wait_vm_lgkm() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(N) : "memory"); }
 
 // PLAIN: VPX_PREC_BF16 — hi parts only (one MFMA per product); the lo planes of a stage and the lo half of every weight piece are
@@ -107,22 +99,6 @@ __global__ __launch_bounds__(512, 4) void cell2_kernel_x(const Cell2Plan P, cons
     const int x0 = tx * 16, y0 = ty * 16;
 
     char* const Abuf = smem;
-#ifdef VPX_ABLATE
-    // TIMING-ONLY ablations of the developer build (garbage results): experiment bits 20 no waits for copies at the sync points, 21 no
-    // barrier at the sync points, 22 no weight copies, 23 no stage copies, 24 no epilogue, 25 no fragment reads
-    const int ab = P._q;
-#else
-    constexpr int ab = 0;
-#endif
-#ifdef VPX_ABLATE
-    if (wave == 0 && lane == 0 && L < 8192) {
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        cx_trace[L * 8 + 4] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
-    }
-#endif
-    CX_TRACE(0);
 
     // this thread's pieces of a stage copy: piece = tid + 512 u -> (plane = part * 2 + channel half, halo position). The plane of a piece
     // is wave-uniform (a plane is 384 = 6 x 64 pieces): its byte offset inside a split pixel row stays in a scalar register. Positions
@@ -224,7 +200,6 @@ __global__ __launch_bounds__(512, 4) void cell2_kernel_x(const Cell2Plan P, cons
         for (int m = 0; m < RW; ++m) load_A1(0, m, a_lane);
         load_B(0, 0);
     }
-    CX_TRACE(1);
     for (int s0 = 0; s0 < S; s0 += 2) {
         const bool odd = s0 + 1 < S;         // the period's odd stage exists
         const bool more = s0 + 2 < S;        // another period follows
@@ -241,12 +216,11 @@ __global__ __launch_bounds__(512, 4) void cell2_kernel_x(const Cell2Plan P, cons
                         // ---- sync point X_q, before this wave's first read of half 1 of chunk q: the fragments of its half-0 tiles are in
                         //      registers (lgkmcnt) before that half is given away; the stage copy issued one step ago may still fly ----
                         const bool stage_flies = (p == 1 && odd) || (p == 6 && more);
-                        if (ab & (1 << 20)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        else if (stage_flies) {
+                        if (stage_flies) {
                             if constexpr (GROUPS) { if (grpA) cx_wait_vm_lgkm<2>(); else cx_wait_vm_lgkm<1>(); }
                             else cx_wait_vm_lgkm<3>();
                         } else cx_wait_vm_lgkm<0>();
-                        if (!(ab & (1 << 21))) c2_barrier();
+                        c2_barrier();
                     }
                     // ---- weight fragments of the next column tile (after the last step: bytes nobody uses, cheaper than a branch) ----
                     if (lt < NTW - 1) load_B(p, lt + 1);
@@ -270,16 +244,12 @@ __global__ __launch_bounds__(512, 4) void cell2_kernel_x(const Cell2Plan P, cons
                     // ---- this sync point's copies, behind the MFMAs of the following column tiles: the weights first, then the stage ----
                     if (lt == SYNC_LT) {
                         const int sl = (p & 1) ^ par;   // ring slot of chunk q (and q + 2)
-                        if (!(ab & (1 << 22))) {
-                            if (q + 1 < Q) issue_Wh(q + 1, sl ^ 1, 1);
-                            if (q + 2 < Q) issue_Wh(q + 2, sl, 0);
-                        }
+                        if (q + 1 < Q) issue_Wh(q + 1, sl ^ 1, 1);
+                        if (q + 2 < Q) issue_Wh(q + 2, sl, 0);
                     }
                     if (lt == SYNC_LT + 1) {
-                        if (!(ab & (1 << 23))) {
-                            if (p == 0 && odd) issue_A(s0 + 1, 1);
-                            if (p == 5 && more) issue_A(s0 + 2, 0);
-                        }
+                        if (p == 0 && odd) issue_A(s0 + 1, 1);
+                        if (p == 5 && more) issue_A(s0 + 2, 0);
                     }
                 }
             }
@@ -291,16 +261,6 @@ __global__ __launch_bounds__(512, 4) void cell2_kernel_x(const Cell2Plan P, cons
     //      two passes of two tile rows, image [gate][pixel 32][16 channels]; a lane then owns FOUR channels of a pixel for all four
     //      gates: 16-byte global accesses, four lanes = one pixel's 64-byte channel run ----
     const ConvLSTMStepArgs& a = E.a;
-    CX_TRACE(2);
-#ifdef VPX_ABLATE
-    if (ab & (1 << 24)) {   // timing only: no epilogue (one never-taken store keeps the accumulators alive)
-        float t = 0.f;
-        for (int m = 0; m < RW; ++m) for (int nt = 0; nt < NTW; ++nt) for (int r = 0; r < 4; ++r) t += acc[m][nt][r];
-        if (t == 1.2345e-30f) a.c_out[0] = t;
-        CX_TRACE(3);
-        return;
-    }
-#endif
     float* const lx = reinterpret_cast<float*>(smem + wave * 8192);
     // lane -> (four channels cg, pixel pp) of a pass: row split — a pass is ONE tile row x 32 channels (8 lanes = a pixel's whole 128-byte
     // channel run: every global access a full line); column split — two tile rows x the wave's 16 channels (4 lanes = 64 bytes)
@@ -319,7 +279,7 @@ __global__ __launch_bounds__(512, 4) void cell2_kernel_x(const Cell2Plan P, cons
     // Four iterations k = 2 * pass + it of 16 (row split: 8) pixels x 4 channels per lane. The global operands of iteration k + 1 (cell state,
     // three peepholes: 64 bytes per lane) are requested BEFORE the arithmetic of iteration k, those of iteration 0 before the barrier and the
     // first LDS round trip: issued right before their use (the first form of this epilogue) every iteration exposed a whole HBM / L2 round
-    // trip — 21-22 k cycles per tile of which the arithmetic is 7 k (developer build stamps, profiles/r06_cell2x_trace.txt).
+    // trip — 21-22 k cycles per tile of which the arithmetic is 7 k (in-kernel clock readings of the former developer build, profiles/r06_cell2x_trace.txt).
     struct EIn { unsigned eo; f32x4 cp, wi, wf, wo; };
     auto eload = [&](int k, EIn& v) {
         const int ps = k >> 1, it = k & 1;
@@ -410,10 +370,6 @@ __global__ __launch_bounds__(512, 4) void cell2_kernel_x(const Cell2Plan P, cons
         if (k + 1 < 2 * NPASS) eload(k + 1, v[(k + 1) & 1]);
         emath(k, v[k & 1]);
     }
-#ifdef VPX_ABLATE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (how long the epilogue's stores take to complete)
-#endif
-    CX_TRACE(3);
 }
 
 // the fused cell step on the eight-wave half tile; the caller (launch_cell2, cell2.hip) has checked that the q form applies (maps in
@@ -435,7 +391,6 @@ hipError_t launch_cell2x(const Cell2Plan& p_in, const ConvLSTMStepArgs& ea, void
     }
     const CellXEpi epi{ea, reinterpret_cast<char*>(h_sp), h_sp_bstride};
     Cell2Plan p = p_in;
-    p._q = g_experiment;   // (read by the developer build's timing ablations only)
     const long long per_xcd = ((long long)p.grid_m * p.n_tiles + 7) / 8;
     const dim3 grid((unsigned)(per_xcd * 8));
     if (p.plain) {
@@ -450,8 +405,3 @@ hipError_t launch_cell2x(const Cell2Plan& p_in, const ConvLSTMStepArgs& ea, void
 
 }  // namespace vpx
 
-#ifdef VPX_ABLATE
-extern "C" int vpx_dbg_cell2x_trace(unsigned long long* out65536) {
-    return (int)hipMemcpyFromSymbol(out65536, HIP_SYMBOL(vpx::cx_trace), sizeof(unsigned long long) * 8192 * 8);
-}
-#endif

@@ -253,13 +253,9 @@ __global__ __launch_bounds__(512, 2) void cell3_kernel(const Cell3Args P) {
     }
 }
 
-// bf16x3, 3x3, recurrent channels in whole 16-channel stages that fit the LDS, whole 16x16 tiles. VPX_CELL3=0 disables.
-int cell3_mode() {
-    if (g_cell3_mode < 0) g_cell3_mode = dev_switch("VPX_CELL3", 1) ? 1 : 0;
-    return g_cell3_mode;
-}
+// bf16x3, 3x3, recurrent channels in whole 16-channel stages that fit the LDS, whole 16x16 tiles. vpx_set_option(VPX_OPT_CELL3, 0) disables.
 bool cell3_applicable(const vpx_convlstm_desc* d) {
-    if (!cell3_mode() || d->precision != VPX_PREC_BF16X3 || d->kh != 3 || d->kw != 3) return false;
+    if (!g_cell3_mode || d->precision != VPX_PREC_BF16X3 || d->kh != 3 || d->kw != 3) return false;
     if ((d->Ch & 15) || d->Ch > C3_MAX_CH || (d->H & 15) || (d->W & 15)) return false;
     return true;
 }

@@ -130,8 +130,8 @@ bool c1_applicable(const C1Args& a, int prec) {
 hipError_t launch_c1(const C1Args& a, hipStream_t s) {
     const int K = a.xc[0] + a.xc[1];
     const long long ntile = (a.npix + 15) / 16;
-    const long long gmax = dev_switch("VPX_C1_GRID", 512);
-    const unsigned grid = (unsigned)(ntile < gmax ? ntile : gmax);   // two workgroups per CU, one round: every workgroup reads the weights once
+    constexpr long long C1_GRID = 512;
+    const unsigned grid = (unsigned)(ntile < C1_GRID ? ntile : C1_GRID);   // two workgroups per CU, one round: every workgroup reads the weights once
     if (a.x_split) {
         if (a.Co == 128 && K == 256) VPX_LAUNCH((c1_kernel<2, 8, true>), dim3(grid), dim3(256), 0, s, a);
         else if (a.Co == 256 && K == 128) VPX_LAUNCH((c1_kernel<4, 4, true>), dim3(grid), dim3(256), 0, s, a);

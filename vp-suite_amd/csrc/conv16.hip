@@ -9,7 +9,7 @@
 //   * a tile is 8 rows x 16 pixels; its 10x18 halo of ALL channels (180 positions x 256 B = 45 KiB) lands in one of three LDS buffers by
 //     LDS-DMA (two copies in flight) while the third is multiplied: one counted wait + one barrier per TILE, nothing inside the K loop but
 //     fragment reads (two per three MFMAs), MFMAs and the next copy's instructions, one at a time.
-// Measured (tools/ab_glue.py, tools/ab_c16.py; 1 280 frames): 0.41 ms = 0.29 PFLOP/s algorithmic (x3: 0.71 PF of bf16 MFMA work). The parts,
+// Measured (tools/ab_glue.py and ab_c16.py, the latter removed with the developer build; 1 280 frames): 0.41 ms = 0.29 PFLOP/s algorithmic (x3: 0.71 PF of bf16 MFMA work). The parts,
 // switched off one at a time in the developer build: MFMAs + fragment reads alone 222 us — 1.31 PF of bf16 MFMA work, the power ceiling
 // DESIGN.md §3.8 measured on the fused cell; tile copies alone 200 us (1.34 GB + halo: HBM rate); stores 45 us; the bare tile loop 65 us.
 // The whole is still nearer their sum than their maximum: what remains is overlap, not a shorter part.
@@ -57,13 +57,7 @@ struct C16Args {
     long long ntiles;
     float slope;                          // LeakyReLU slope (0: none ... applied when act != 0)
     int act;
-    int dbg;                              // developer build (VPX_ABLATE) only: timing ablations, VPX_OPT_EXPERIMENT bits 20-22
 };
-#ifdef VPX_ABLATE
-#define C16_DBG(bit) (a.dbg & (bit))
-#else
-#define C16_DBG(bit) 0
-#endif
 
 template <int S>   // 16-channel stages: C = 16 S
 __global__ __launch_bounds__(512, 2) void c16_kernel(const C16Args a) {
@@ -133,21 +127,20 @@ __global__ __launch_bounds__(512, 2) void c16_kernel(const C16Args a) {
     unsigned tile = blockIdx.x;
     int b0 = 0, b1 = C16_BUF, b2 = 2 * C16_BUF;   // ring of three tile buffers: multiplied now | landing | being requested
     if (tile < ntiles) issue(tile, b0);
-    if (tile + G < ntiles && !C16_DBG(2)) issue(tile + G, b1);
+    if (tile + G < ntiles) issue(tile + G, b1);
     for (; tile < ntiles; tile += G) {
         // this thread's pieces of `tile` have landed: everything but the newest batch (6 copies of waves 0-4, 5 of waves 5-7; loads
         // complete in order, so a pending store of the previous tile can only make this wait stricter)
-        if (tile + G < ntiles && !C16_DBG(2)) { if (wave < 5) C2_WAIT_VM(6); else C2_WAIT_VM(5); }
+        if (tile + G < ntiles) { if (wave < 5) C2_WAIT_VM(6); else C2_WAIT_VM(5); }
         else C2_WAIT_VM(0);
         c2_barrier();      // ... everybody's have; and every wave has finished reading the buffer of the tile before
         // The copy of the tile after next goes out one instruction at a time BETWEEN the K steps: issued as a burst, the 45 KiB fill the CU's
         // miss queue and every wave sits in its next copy instruction for about the transfer time before it multiplies anything
-        // (measured: copies alone 180 us + MFMAs alone 211 us = the whole kernel, nothing overlapped; tools/ab_c16.py)
-        const bool more = tile + 2 * G < ntiles && !C16_DBG(2);
+        // (measured: copies alone 180 us + MFMAs alone 211 us = the whole kernel, nothing overlapped; ab_c16.py, removed with the developer build)
+        const bool more = tile + 2 * G < ntiles;
         Where w2{};
         if (more) w2 = locate(tile + 2 * G);
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        if (!C16_DBG(1)) {
 #pragma unroll
         for (int s0 = 0; s0 < S; s0 += 2) {
             const bool pair = s0 + 1 < S;
@@ -168,14 +161,10 @@ __global__ __launch_bounds__(512, 2) void c16_kernel(const C16Args a) {
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[q], ph, acc, 0, 0, 0);
             }
         }
-        } else if (more) {
-#pragma unroll
-            for (int u = 0; u < 6; ++u) issue_piece(u, w2, b2);
-        }
         // ---- epilogue: lane = (pixel r16 of tile row `wave`, output channels 4 kg .. + 3) ----
         const Where w0 = locate(tile);
         const int n = w0.n, y = w0.y0 + wave, x = w0.x0 + r16;
-        if (y < a.H && x < a.W && !C16_DBG(4)) {
+        if (y < a.H && x < a.W) {
             f32x4 v = acc + bias4;
             if (a.act) {
 #pragma unroll
@@ -222,7 +211,6 @@ int c16_forward(const vpx_conv_desc* d, const char* x_split, long long x_bstride
     a.ntiles = (long long)d->N * a.tiles_x * a.tiles_y;
     if (a.ntiles >= (1ll << 31)) { set_error("c16: too many tiles"); return VPX_ERR_UNSUPPORTED; }
     a.slope = d->leaky_slope; a.act = d->leaky_slope != 0.0f ? 1 : 0;
-    a.dbg = (g_experiment >> 20) & 7;
     static bool attr_set = false;
     if (!attr_set) {
         const void* fn[4] = {reinterpret_cast<const void*>(&c16_kernel<1>), reinterpret_cast<const void*>(&c16_kernel<2>),

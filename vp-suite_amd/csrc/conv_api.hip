@@ -196,13 +196,9 @@ int ex_check(const vpx_conv_desc* d, ExGeo& g) {
 }
 
 // workgroup form of a glue launch: the 8-wave / 16x16-pixel tile when the grid stays large (pick_mw's rule) and the
-// stride-1 halo keeps two such workgroups per CU; VPX_GLUE_MW=1/2 forces a form (experiments)
+// stride-1 halo keeps two such workgroups per CU
 static int ex_mw(const vpx_conv_desc* d, int Ht, int Wt, int sd) {
-    static int forced = -1;
-    if (forced < 0) forced = dev_switch("VPX_GLUE_MW", 0);
-    if (d->precision == VPX_PREC_F32) return 1;
-    if (forced == 1 || forced == 2) return forced;
-    if (sd != 1) return 1;
+    if (d->precision == VPX_PREC_F32 || sd != 1) return 1;
     const int mw = pick_mw(d->N, Ht, Wt, plain_tiles(d->Co), d->precision);
     const int segC[1] = {d->Ci};
     return (mw > 1 && !conv_fits_lds(segC, 1, d->kh, d->kw, plain_groups(d->Co), d->precision, mw, sd)) ? 1 : mw;
@@ -351,12 +347,8 @@ int vpx_conv2d_ex_fwd_split(const vpx_conv_desc* d, const float* x, const float*
 // 32x32 0.32 -> 0.25, stride-2 transposed 4x4 96 -> 96 at 16x16 0.48 -> 0.38 and at 32x32 1.79 -> 1.47 (at 40 frames 0.12 -> 0.04 /
 // 0.15 -> 0.06: the phase form is one launch) — but plain convolutions only on grids of >= 256 workgroups (40 frames: 0.045 -> 0.049).
 // 3x3 stride-1 layers with 16 output channels (64 -> 16: 0.83 first generation, 1.22 convq) have their own kernel (conv16.hip: 0.41).
-// VPX_CONVQ=0 / 2: convq never / wherever it applies.
 static bool exq_preferred(const vpx_conv_desc* d, const ExGeo& g, ConvQProblem& pr) {
-    static int mode = -1;
-    if (mode < 0) mode = dev_switch("VPX_CONVQ", 1);
-    if (mode == 0 || !exq_problem(d, g, pr) || convq_wpk_bytes(pr) == 0) return false;
-    if (mode == 2) return true;
+    if (!exq_problem(d, g, pr) || convq_wpk_bytes(pr) == 0) return false;
     if (d->Co < 64) return false;
     if (pr.phases) return true;
     const long long wgs = (long long)pr.N * ((pr.W + 15) / 16) * ((pr.H + 15) / 16) * (((d->Co + 31) / 32 + 3) / 4);
@@ -626,7 +618,7 @@ int ex_adjoint(const vpx_conv_desc* d, const ExGeo& g, vpx_conv_desc& a) {
 
 // weight gradient on split copies of x and dy (wgrad2_kernel's glue form): bf16x3 on the 16x16x32 shape, channel counts in whole groups of 8
 static bool ex_wgrad_split(const vpx_conv_desc* d) {
-    return !(g_experiment & (1 << 29)) && d->precision == VPX_PREC_BF16X3 && mfma_shape() == 1 && (d->Ci & 7) == 0 && (d->Co & 7) == 0 &&
+    return !(g_experiment & (1 << 29)) && d->precision == VPX_PREC_BF16X3 && g_mfma_shape == 1 && (d->Ci & 7) == 0 && (d->Co & 7) == 0 &&
            d->kh <= 2 * d->stride + 1 && d->kw <= 2 * d->stride + 1 && d->kh * d->kw > 1 &&
            !(!d->transposed && wgrad_small_applicable(d->Co, d->Ci, d->kh, d->kw, d->stride, d->pad));
 }
@@ -636,12 +628,12 @@ size_t ex_bwd_slab_floats(const vpx_conv_desc* d, const ExGeo& g) {
     (void)g;
     const size_t full = (size_t)32 * d->kh * d->kw * d->Ci * d->Co;
     size_t b = full > (size_t)GLUE_SLAB_FLOATS ? full : (size_t)GLUE_SLAB_FLOATS;
-    // the glue form of wgrad2_kernel: up to wgrad2_target_wgs() workgroups = that many slices of ONE row x column tile pair
+    // the glue form of wgrad2_kernel: up to WGRAD2_TARGET_WGS workgroups = that many slices of ONE row x column tile pair
     // (a residue's slab is at most kh * kw * Ci * Co / stride^2 floats)
     if (ex_wgrad_split(d)) {
         const int rows = ((d->transposed ? d->Ci : d->Co) + 127) / 128, cols = ((d->transposed ? d->Co : d->Ci) + 63) / 64;
         const size_t per = (size_t)((d->kh + d->stride - 1) / d->stride) * ((d->kw + d->stride - 1) / d->stride) * d->Ci * d->Co;
-        const size_t need = (size_t)(wgrad2_target_wgs() / (rows * cols) + 1) * per;
+        const size_t need = (size_t)(WGRAD2_TARGET_WGS / (rows * cols) + 1) * per;
         if (need > b) b = need;
     }
     return b;

@@ -324,13 +324,6 @@ __device__ __forceinline__ void stage_store(char* dst, int lo_off, const f32x4 v
     }
 }
 
-// timing ablations (VPX_DBG bits) exist only in builds with -DVPX_ABLATE; the product kernel carries none of the tests
-#ifdef VPX_ABLATE
-#define DBGBIT(b) (P.dbg & (b))
-#else
-#define DBGBIT(b) false
-#endif
-
 template <int MODE, int QPCN = 2> struct ModeTraits {  // QPCN = k-steps per weight chunk (2 or 3)
     static constexpr int KSTEP = MODE == 0 ? 8 : 16;   // plain bf16 (MODE 2) shares the bf16x3 layout, only hi planes are read
     static constexpr int KC = KSTEP * QPCN;
@@ -372,7 +365,6 @@ __device__ __forceinline__ void conv_body(const ConvPlan& P, const Epi& epi, con
 
     char* A_lds = smem;
     char* W_lds = smem + P.a_bytes;
-    if (DBGBIT(256)) return;  // ablation: launch + dispatch floor
 
     f32x16 acc[MS][NG];
 #pragma unroll
@@ -407,7 +399,7 @@ __device__ __forceinline__ void conv_body(const ConvPlan& P, const Epi& epi, con
         if (ps < s_end) {
 #pragma unroll
             for (int it = 0; it < WIT; ++it)
-                if (tid + it * NTH < WV4 && !DBGBIT(4)) wr[it] = *reinterpret_cast<const f32x4*>(wnext + it * NTH * 16);
+                if (tid + it * NTH < WV4) wr[it] = *reinterpret_cast<const f32x4*>(wnext + it * NTH * 16);
             wnext += CHUNK_BYTES;
             if (--prem == 0 && ++ps < s_end) {
                 prem = stage_chunks(ps);
@@ -426,7 +418,7 @@ __device__ __forceinline__ void conv_body(const ConvPlan& P, const Epi& epi, con
         char* wdst = W_lds + buf * WBUF;
 #pragma unroll
         for (int it = 0; it < WIT; ++it)
-            if (tid + it * NTH < WV4 && !DBGBIT(64)) *reinterpret_cast<f32x4*>(wdst + wdst_off[it]) = wr[it];
+            if (tid + it * NTH < WV4) *reinterpret_cast<f32x4*>(wdst + wdst_off[it]) = wr[it];
     };
     f32x4 wr[WIT];
 #pragma unroll
@@ -444,8 +436,7 @@ __device__ __forceinline__ void conv_body(const ConvPlan& P, const Epi& epi, con
         {
             const float* src = sg.ptr + (size_t)b * sg.bstride;
             const int ld = sg.ld ? sg.ld : sg.C;
-            if (DBGBIT(128)) {
-                } else if (((sg.C | ld) & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) & 15) == 0)) {
+            if (((sg.C | ld) & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) & 15) == 0)) {
                 const int v4n = st.cn >> 2;
                 if ((v4n & (v4n - 1)) == 0) {
                     // cn/4 is a power of two (always for 16/32/64-channel stages): 256 threads cover 256/v4n halo
@@ -457,20 +448,9 @@ __device__ __forceinline__ void conv_body(const ConvPlan& P, const Epi& epi, con
                     int pos = tid >> sh;
                     int hy = pos / halo_w, hx = pos - hy * halo_w;
                     const int c = st.c0 + c4 * 4;
-                    const bool c_ok = c < sg.C && !DBGBIT(2);
+                    const bool c_ok = c < sg.C;
                     const bool spl = MODE != 0 && sg.split != 0;
                     char* dstc = A_lds + (MODE == 0 ? c4 * 16 : c4 * 8);
-                    if (DBGBIT(16)) {
-                    for (; pos < npos; pos += dpos) {
-                        const int gy = y0 * sd - ph + hy, gx = x0 * sd - pw + hx;
-                        f32x4 val = {0.f, 0.f, 0.f, 0.f};
-                        if (c_ok && gy >= 0 && gy < Hin && gx >= 0 && gx < Win)
-                            val = stage_load(src + ((size_t)gy * Win + gx) * ld, c, spl);
-                        stage_store<MODE>(dstc + pos * arow, st.cn * 2, val, spl);
-                        hx += dhx; hy += dhy;
-                        if (hx >= halo_w) { hx -= halo_w; ++hy; }
-                    }
-                    } else {
                     // AU loads in flight per thread before the first conversion: one exposed memory latency per AU
                     // positions instead of one per position (the MFMA fragment registers are dead here)
                     constexpr int AU = (MW >= 2 ? 3 : 4);
@@ -489,7 +469,6 @@ __device__ __forceinline__ void conv_body(const ConvPlan& P, const Epi& epi, con
                         for (int u = 0; u < AU; ++u)
                             if (pos + u * dpos < npos) stage_store<MODE>(dstc + (pos + u * dpos) * arow, st.cn * 2, val[u], spl);
                     }
-                    }
                 } else {
                     const int total = npos * v4n;
                     for (int v = tid; v < total; v += NTH) {
@@ -499,7 +478,7 @@ __device__ __forceinline__ void conv_body(const ConvPlan& P, const Epi& epi, con
                         const int c = st.c0 + c4 * 4;
                         f32x4 val = {0.f, 0.f, 0.f, 0.f};
                         const bool spl = MODE != 0 && sg.split != 0;
-                        if (gy >= 0 && gy < Hin && gx >= 0 && gx < Win && c < sg.C && !DBGBIT(2))
+                        if (gy >= 0 && gy < Hin && gx >= 0 && gx < Win && c < sg.C)
                             val = stage_load(src + ((size_t)gy * Win + gx) * ld, c, spl);
                         if constexpr (MODE == 0) {
                             *reinterpret_cast<f32x4*>(A_lds + pos * arow + c4 * 16) = val;
@@ -555,8 +534,7 @@ __device__ __forceinline__ void conv_body(const ConvPlan& P, const Epi& epi, con
 #pragma unroll
             for (int q = 0; q < QPC; ++q) {
                 if (q == 0 || kq + q < st.nq) {
-                    if (DBGBIT(1)) {
-                    } else if constexpr (MODE == 0) {
+                    if constexpr (MODE == 0) {
                         // fp32: one b128 = 4 consecutive channels; lanes 0-31 take k = 8*ks + s, lanes 32-63 k = 8*ks + 4 + s
                         f32x4 a4[MS];
 #pragma unroll
@@ -619,15 +597,11 @@ __device__ __forceinline__ void conv_body(const ConvPlan& P, const Epi& epi, con
             }
             __builtin_amdgcn_s_setprio(0);
             if (has_next) write_lds(wr, buf ^ 1);  // every wave finished reading that buffer before the last barrier
-            if (!DBGBIT(32)) __syncthreads();  // (bit 32: timing-only ablation of the per-chunk barrier; results are wrong)
+            __syncthreads();
             ++gidx;
         }
     }
 
-    if (DBGBIT(8)) {  // ablation: keep the accumulators alive with one store instead of the epilogue
-        if (acc[0][0][0] == 12345.678f) reinterpret_cast<float*>(const_cast<float*>(P.wpk))[0] = acc[MS - 1][0][1];
-        return;
-    }
 #pragma unroll
     for (int m = 0; m < MS; ++m) {
         TileCtx t{b, y0, x0, n_tile, 2 * (MS * wave + m), j, hh, P.H, P.W, kz};
@@ -675,12 +649,6 @@ __global__ __launch_bounds__(NTHREADS * MW, (MW == 2 ? 4 : 3)) void conv_gemm_du
     else conv_body<EpiB, MODE, MW>(PB, epiB, n_tile - nA, m_tile);
 }
 
-static bool xcd_map_enabled() {  // VPX_XCD_MAP=0 restores the plain 2-D grid (experiments)
-    static int on = -1;
-    if (on < 0) on = dev_switch("VPX_XCD_MAP", 1);
-    return on != 0;
-}
-
 template <class Epi, int MODE, int MW, int MS = 1, int QPCN = 2>
 static hipError_t launch_conv_m(const ConvPlan& plan, const Epi& epi, int n_tiles, hipStream_t s) {
     const size_t lds = (size_t)plan.a_bytes + 2 * (Epi::NG * 32 * (ModeTraits<MODE, QPCN>::WROW_DATA + 16));
@@ -694,27 +662,22 @@ static hipError_t launch_conv_m(const ConvPlan& plan, const Epi& epi, int n_tile
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     ConvPlan p2 = plan;
     p2.grid_m = plan.B * plan.tiles_x * plan.tiles_y;
-    p2.grid_n = xcd_map_enabled() ? n_tiles : 0;
+    p2.grid_n = n_tiles;   // the flattened, XCD-aware 1-D grid
     const long long per_xcd = ((long long)p2.grid_m * n_tiles + 7) / 8;
-    dim3 grid = p2.grid_n ? dim3((unsigned)(per_xcd * 8), 1, plan.ksplit > 1 ? plan.ksplit : 1)
-                          : dim3(p2.grid_m, n_tiles, plan.ksplit > 1 ? plan.ksplit : 1);
+    dim3 grid((unsigned)(per_xcd * 8), 1, plan.ksplit > 1 ? plan.ksplit : 1);
     VPX_LAUNCH((conv_gemm_kernel<Epi, MODE, MW, MS, QPCN>), grid, dim3(NTHREADS * MW), lds, s, p2, epi);
     return vpx_hip_last_error();
 }
 
 template <class Epi>
 static hipError_t launch_conv(const ConvPlan& plan_in, const Epi& epi, int n_tiles, hipStream_t s) {
-    static int dbg = -1;
-    if (dbg < 0) dbg = dev_switch("VPX_DBG", 0);
     ConvPlan plan = plan_in;
-    plan.dbg = dbg;
     if (!Epi::SPLITK) plan.ksplit = 0;  // only the plain epilogue can combine partial sums
     const int mw = plan.mw >= 4 ? 4 : (plan.mw > 1 ? 2 : 1);
     if ((plan.H + TILE_H * mw - 1) / (TILE_H * mw) != plan.tiles_y) return hipErrorInvalidValue;  // host geometry mismatch
     if (plan.prec == VPX_PREC_F32) return plan.qpc == 3 ? hipErrorInvalidValue : launch_conv_m<Epi, 0, 1>(plan, epi, n_tiles, s);  // fp32 is MFMA-bound: MW=1 only
     if (plan.prec == VPX_PREC_BF16X3) {
-        static int ms = -1;  // 16x16 tile as 4 waves x 2 sub-tiles (VPX_MS=2) instead of 8 waves x 1
-        if (ms < 0) ms = dev_switch("VPX_MS", 1);
+        constexpr int ms = 1;  // 2: the 16x16 tile as 4 waves x 2 sub-tiles instead of 8 waves x 1 (instantiated, never selected)
         if constexpr (Epi::Q3OK) {  // 3 k-steps per weight chunk (ConvLSTM cell and its data gradient on 3x3 kernels)
             if (plan.qpc == 3 && mw <= 2 && ms != 2)
                 return mw == 2 ? launch_conv_m<Epi, 1, 2, 1, 3>(plan, epi, n_tiles, s) : launch_conv_m<Epi, 1, 1, 1, 3>(plan, epi, n_tiles, s);
@@ -771,14 +734,11 @@ int plain_groups(int Co, long long m_tiles) {
 }
 
 int pick_ksplit(long long wgs, int nstage, bool bwd) {
-    static int forced = -1;
-    if (forced < 0) forced = dev_switch("VPX_KSPLIT", 0);
     if (g_deterministic) return 1;
     int k = 1;
-    if (forced > 0) k = forced;
     // aim at one workgroup per CU: measured on 16x16 maps (64 pixel tiles), PredRNN forward 25.8 ms with 12 splits,
     // 24.7 ms with 4, 28.7 ms with 3; ConvLSTM (96,96,16x16) B=32 (192 workgroups) 155 TF fused, 164 TF with 2 splits
-    else if (wgs > 0 && wgs < 256) k = (int)((256 + wgs - 1) / wgs);
+    if (wgs > 0 && wgs < 256) k = (int)((256 + wgs - 1) / wgs);
     // data-gradient convs at exactly one workgroup per CU unsplit (PredRNN's 16x16 maps at B=128: 256 pixel tiles x 1 N
     // tile): two halves of K per tile give every CU a second workgroup to overlap with (training step 260.5 -> 252.9 ms;
     // 4 splits 269.4). Not in the forward pass: its split convs pay a clear + a separate output pass (inference 58.9 -> 60.1 ms)
@@ -827,7 +787,6 @@ static hipError_t launch_st_dual_m(const ConvPlan& pc, const STGateArgs& ec, con
     ConvPlan pc2 = pc;
     pc2.grid_m = pc.B * pc.tiles_x * pc.tiles_y;
     pc2.grid_n = 0;  // the two groups have different weights and sources: interleaving them per XCD measured 2.6 % slower
-    (void)&xcd_map_enabled;
     const long long per_xcd = ((long long)pc2.grid_m * 2 * n_tiles + 7) / 8;
     dim3 grid = pc2.grid_n ? dim3((unsigned)(per_xcd * 8), 1) : dim3(pc2.grid_m, 2 * n_tiles);
     VPX_LAUNCH((conv_gemm_dual_kernel<KA, KB, MODE, MW>), grid, dim3(NTHREADS * MW), lds, s, pc2, KA{ec}, n_tiles, pm, KB{em});
@@ -878,25 +837,16 @@ int build_stages(ConvStage* st, int* chunks_total, const int* segC, int nseg, in
 
 // Channels per activation stage: the smallest stage that still fits the stage table buys the most workgroups per CU
 // (LDS = halo tile + double-buffered weight chunk; 144 registers cap residency at 3 waves/SIMD). Measured on MI355X,
-// fp32, B=32: 64 ch -> 95 TF (1 WG/CU), 32 -> 118 TF (2), 16 -> 120-128 TF (3).  VPX_CS overrides for experiments.
+// fp32, B=32: 64 ch -> 95 TF (1 WG/CU), 32 -> 118 TF (2), 16 -> 120-128 TF (3).
 int pick_mw(int B, int H, int W, int n_tiles, int prec) {
-    static int forced = -1;
-    if (forced < 0) forced = dev_switch("VPX_MW", 0);
     if (prec == VPX_PREC_F32) return 1;  // fp32 is MFMA-bound: the 8-wave form is not instantiated
-    if (forced == 1 || forced == 2 || (forced == 4 && prec == VPX_PREC_BF16X3)) return forced;
     // 8-wave workgroups halve the weight traffic per pixel; worth it only when the launch still fills the chip
     const long long wgs2 = (long long)B * ((H + 2 * TILE_H - 1) / (2 * TILE_H)) * ((W + TILE_W - 1) / TILE_W) * n_tiles;
     return wgs2 >= 512 ? 2 : 1;
 }
 
 int pick_stage_channels(const int* segC, int nseg, int kh, int kw, int ng, int prec, int mw, int stride, int qpc) {
-    static int forced = -1;
-    if (forced < 0) {
-        forced = dev_switch("VPX_CS", 0);
-        if (forced < 8 || (forced & 7) || forced > CS_MAX) forced = 0;
-    }
     const int kstep = mode_kstep(prec);
-    if (forced) return forced < kstep ? kstep : forced;
     const int npos = ((TILE_H * mw - 1) * stride + kh) * ((TILE_W - 1) * stride + kw);
     const int wbytes = 2 * ng * 32 * (mode_kc(prec, qpc) * 4 + 16);
     const int wg_cap = mw == 4 ? 1 : (mw == 2 ? 2 : 3);  // residency: 2 x 8 waves or 3 x 4 waves per CU (register budgets 128 / 168)

@@ -47,10 +47,8 @@ extern "C" int vpx_convlstm_seq_bwd(const vpx_convlstm_desc* d, const float* x, 
     float* peep_part[3];
     for (auto& pp_ : peep_part) pp_ = ws.take((size_t)GATE_BWD_MAX_SLICES * L.n_peep);
     // forward on the second-generation cell: the gate-backward kernel also writes dG in split operand format and the data
-    // gradient runs on the cell2 main loop with a plain epilogue (conv2); VPX_CONV2_DGRAD=0 keeps the first-generation kernel
-    static int c2d_env = -1;
-    if (c2d_env < 0) c2d_env = dev_switch("VPX_CONV2_DGRAD", 1);
-    const bool c2d = L.v2 && c2d_env != 0;
+    // gradient runs on the cell2 main loop with a plain epilogue (conv2)
+    const bool c2d = L.v2;
     char* dG_sp_all = nullptr; char* wpk2 = nullptr;
     if (L.v2) {
         dG_sp_all = (char*)ws.take((size_t)T * L.n_state * 4);
@@ -118,7 +116,7 @@ extern "C" int vpx_convlstm_seq_bwd(const vpx_convlstm_desc* d, const float* x, 
     const int col_start = need_dx ? 0 : Cin;
     const int n_out = need_dx ? Ct : Ch;
     const int d_tiles = plain_tiles(n_out);
-    const int qform = mfma_shape() == 1 ? 1 : 0;   // conv2's epilogue handles ragged tiles in both forms
+    const int qform = g_mfma_shape == 1 ? 1 : 0;   // conv2's epilogue handles ragged tiles in both forms
     if (c2d) {
         Conv2Pack pk{W, (long long)L.taps, (long long)Ct * L.taps, n_out, col_start, conv2_tiles(n_out), conv2_gpt(n_out),
                      qform ? cell2_qchunks(N4 / 16) : 3 * (N4 / 16), 1, qform, 0};

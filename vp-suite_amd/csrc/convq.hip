@@ -166,11 +166,6 @@ __global__ __launch_bounds__(64 * NW, 2) void convq_kernel(const ConvQPlan P, co
     // 36 instead of 48 ds_read_b128 per 96 MFMAs — the phase form is LDS-read-bound. Same products, same order.
     constexpr bool REMAP = PHASE && NW == 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef VPX_DEV_SWITCHES
-    const int dbg_bits = P.dbg;   // timing ablations of the developer build (VPX_CQ_DBG)
-#else
-    constexpr int dbg_bits = 0;   // (the product carries none of their tests: seven run-time tests per chunk of 96 MFMAs)
-#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r16 = lane & 15, kg = lane >> 4;
@@ -283,11 +278,8 @@ __global__ __launch_bounds__(64 * NW, 2) void convq_kernel(const ConvQPlan P, co
     if (S > 0 && P.nsub > 0) {
         // ---- prologue: stage 0 (and stage 1 where the schedule expects it to be under way), chunks 0 and 1 ----
         Src aq_src = stage_src(0);
-        if (dbg_bits & 32) return;
-        if (!(dbg_bits & 16)) {
 #pragma unroll
         for (int u = 0; u < NP; ++u) issue_A1(aq_src, 0, u);
-        }
         if (P.pro_stage1) {
             const Src s1 = stage_src(1);
 #pragma unroll
@@ -297,7 +289,6 @@ __global__ __launch_bounds__(64 * NW, 2) void convq_kernel(const ConvQPlan P, co
         if (P.nchunk_total > 1) { issue_W1(1, 1, 0); issue_W1(1, 1, 1); }
         C2_WAIT_VM(0);
         c2_barrier();
-        if (dbg_bits & 64) return;
 
         int idx = 0, base = 0, c = 0;
         bool a_pending = false;                 // a stage copy issued AFTER the last weight chunk may still fly at the next sync
@@ -321,9 +312,9 @@ __global__ __launch_bounds__(64 * NW, 2) void convq_kernel(const ConvQPlan P, co
             const int slot = c % WSLOTS, nslot = (c + 1) % WSLOTS;
             // ring of three: chunk c+2 into the slot chunk c-1 has left; ring of two: chunk c+1 (chunk 1 went out with the prologue)
             const int wq_c = WSLOTS == 3 ? c + 2 : (c > 0 ? c + 1 : 1 << 30);
-            const int wq = (wq_c < P.nchunk_total && !(dbg_bits & 4)) ? wq_c : -1, wq_slot = wq_c % WSLOTS;
+            const int wq = wq_c < P.nchunk_total ? wq_c : -1, wq_slot = wq_c % WSLOTS;
             bool aq = false, aq_first = false; int aq_buf = 0;
-            if (cur.issue && !(dbg_bits & 2)) {
+            if (cur.issue) {
                 const int st = base + cur.istage;
                 if (st <= S) {           // st == S: zero fill (a cross step may read that buffer against zero weights)
                     aq_src = stage_src(st);
@@ -363,7 +354,7 @@ __global__ __launch_bounds__(64 * NW, 2) void convq_kernel(const ConvQPlan P, co
                     const int at = PHASE ? t : k;        // accumulator tile
                     const int bt = REMAP ? k : t;        // weight-fragment set
                     if (!REMAP) { if (t < 7) load_B(slot, t + 1); else if (WSLOTS == 3) load_B(nslot, 0); }
-                    const bool go = on && ((tmask >> (REMAP ? 2 * wave + k : at)) & 1) && !(dbg_bits & 1);
+                    const bool go = on && ((tmask >> (REMAP ? 2 * wave + k : at)) & 1);
                     if (go) {
                         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -404,7 +395,7 @@ __global__ __launch_bounds__(64 * NW, 2) void convq_kernel(const ConvQPlan P, co
         }
         C2_WAIT_VM(0);                            // no copy may land in the epilogue's transposition space
     }
-    if (!(dbg_bits & 8)) epi.template finish16<REMAP>(acc, smem, wave, lane, b, y0, x0, n_tile, ngr, P.H, P.W);
+    epi.template finish16<REMAP>(acc, smem, wave, lane, b, y0, x0, n_tile, ngr, P.H, P.W);
 }
 
 // ---- weight pack: [n_tile][chunk][part][k group][n][8 bf16]; the table says, per chunk of a pass and 16-column tile, which
@@ -465,12 +456,10 @@ struct QBuild {
     int halo, NTS, nw;
 };
 
-// waves per workgroup: 4 = the half tile (two workgroups per CU), 3x3-halo layers only; VPX_CONVQ_NW=8 / experiment bit 4 keep the 32x16 tile
+// waves per workgroup: 4 = the half tile (two workgroups per CU), 3x3-halo layers only; experiment bit 4 keeps the 32x16 tile
 int convq_pick_nw(const ConvQProblem& pr) {
-    static int env = -1;
-    if (env < 0) env = dev_switch("VPX_CONVQ_NW", 4);
     if (g_experiment & 16) return 8;   // VPX_OPT_EXPERIMENT bit 4: the 32x16 tile (A/B runs, tests)
-    return (pr.halo == 2 && env == 4) ? 4 : 8;
+    return pr.halo == 2 ? 4 : 8;
 }
 
 int seg_of_stage(const ConvQProblem& pr, int s) {
@@ -584,10 +573,7 @@ int convq_build_impl(const ConvQProblem& pr, QBuild& out, int max_cpack = 8) {
         // chunks of time; (2) before the chunk (must land within ONE chunk: the sync may stall); (3) before the chunk and late.
         int ci = -1, afirst = 0, late = 0;
         static const int m_hi[4] = {3, 2, 2, 1}, m_af[4] = {0, 0, 1, 1}, m_late[4] = {0, 1, 0, 1};
-        static int mode_mask = -1;   // VPX_CONVQ_MODES: bit m allows mode m (experiments)
-        if (mode_mask < 0) mode_mask = dev_switch("VPX_CONVQ_MODES", 15);
         for (int mode = 0; mode < 4 && ci < 0; ++mode) {
-            if (!((mode_mask >> mode) & 1)) continue;
             const int hi = fu[t] - m_hi[mode];
             for (int k = lo; k <= hi; ++k)
                 if (k >= 0 && ev_stage[k] < 0) { ci = k; afirst = m_af[mode]; late = m_late[mode]; break; }
@@ -751,7 +737,6 @@ int convq_run(const ConvQProblem& pr, const ConvQEpiArgs& ea_in, char* wpk, bool
         VPX_CHECK_HIP(vpx_hip_last_error());
     }
     b.P.wpk = wpk;
-    { static int dbg = -1; if (dbg < 0) dbg = dev_switch("VPX_CQ_DBG", 0); b.P.dbg = dbg; }
     ConvQEpi epi{ea_in};
     epi.a.gpt = b.P.gpt;
     epi.a.phases = pr.phases;
@@ -1131,14 +1116,6 @@ __global__ __launch_bounds__(256, 2) void c5_kernel(const C5Plan P) {
 
     const int Q = J.Q;
     const int nt_active = J.nt_active;
-#if defined(VPX_DEV_SWITCHES) && defined(VPX_C5_ABL)   // (its branches cost the loop a third: a build of its own, hipcc -DVPX_C5_ABL)
-    const int abl = P.ablate;   // 1: no stage copies, 2: no weight copies, 4: no sync points, 8: no MFMAs, 16: no A reads, 32: no B reads (K loop only)
-#else
-    constexpr int abl = 0;
-#endif
-    // developer timing stamps (P.stamps != nullptr only from tools/): shader clock of one workgroup's waves at the phase boundaries
-    const bool stamp = P.stamps != nullptr && (int)blockIdx.x == P.stamp_block && lane == 0;
-    if (stamp) P.stamps[wave * 8 + 0] = __builtin_amdgcn_s_memtime();
     bool flies = false;                         // a stage copy was issued in the previous step (it may still fly at this step's sync)
     ClstmPre<(KS == 3 ? NT : 1)> clstm_pre;
     if constexpr (KS == 3) {
@@ -1170,11 +1147,10 @@ __global__ __launch_bounds__(256, 2) void c5_kernel(const C5Plan P) {
     }
     constexpr int SYNC_NT = NT == 8 ? 5 : (NT == 4 ? 2 : 1);    // the sync point sits before this column tile of every step
     constexpr int STAGE_NT = SYNC_NT + 1 < NT ? SYNC_NT + 1 : NT - 1;   // the stage copy follows the weight copy (same tile when there is no later one)
-    if (stamp) P.stamps[wave * 8 + 1] = __builtin_amdgcn_s_memtime();
     // A wave issues one instruction per four cycles: a step of the narrow tiles holds 24 or 48 MFMAs (384 / 768 cycles of the pipe), and
     // the step's scalar bookkeeping (which stage to request, the fragment offsets: three integer divisions per lane, the ring slot) stood
     // beside them with a hundred instructions of its own — with every copy, read, MFMA and sync point removed the loop still took 950
-    // cycles per step (developer build, VPX_C5_ABLATE = 63). 3x3: the period's nine steps are unrolled — the stage schedule and the ring
+    // cycles per step (measured on the former developer build). 3x3: the period's nine steps are unrolled — the stage schedule and the ring
     // slot (9 = 3 x RD) become constants, the fragment offsets of the nine steps nine registers.
     constexpr int UNR = G::SPS;
     int aoffs[G::SPS];
@@ -1201,18 +1177,16 @@ __global__ __launch_bounds__(256, 2) void c5_kernel(const C5Plan P) {
             for (int nt = 0; nt < NT; ++nt) {
                 if (nt == SYNC_NT) {
                     // ---- sync point S_q: chunk q + 1 has landed (the stage requested one step ago may still fly) ----
-                    if (abl & 4) {
-                    } else if constexpr (G::PD == 2) {
+                    if constexpr (G::PD == 2) {
                         if (flies) c5_wait_vm<G::NPC>(); else C2_WAIT_VM(0);
                     } else {
                         // chunks q + 2 .. q + PD - 1 may fly (a stage copy among them lands early: in-order completion); at the tail, where
                         // no further chunk is behind q + 1, everything must have landed
                         if (q + G::PD <= Q) c5_wait_vm<G::WAITN>(); else C2_WAIT_VM(0);
                     }
-                    if (!(abl & 4)) c2_barrier();
+                    c2_barrier();
                 }
-                if (abl & 32) {
-                } else if (nt < NT - 1) load_B(slot, nt + 1);
+                if (nt < NT - 1) load_B(slot, nt + 1);
                 else load_B(nslot, 0);
                 __builtin_amdgcn_s_setprio(1);
                 // (a gate job of three gates holds six column tiles of the eight: it skips the MFMAs of the last two. Only those two carry
@@ -1221,7 +1195,7 @@ __global__ __launch_bounds__(256, 2) void c5_kernel(const C5Plan P) {
                 if (nt < NT - 1) {
 #pragma unroll
                     for (int m = 0; m < 4; ++m) {
-                        if (go && !(abl & 8)) {
+                        if (go) {
                             f32x4 c = acc[m][nt];
                             c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[m], bh[nt & 1], c, 0, 0, 0);
                             c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[m], bl[nt & 1], c, 0, 0, 0);
@@ -1235,26 +1209,24 @@ __global__ __launch_bounds__(256, 2) void c5_kernel(const C5Plan P) {
                     // fragments behind the tenth MFMA and the next step opens with a wait); the hi fragments follow row by row in the third
 #pragma unroll
                     for (int m = 0; m < 4; ++m)
-                        if (go && !(abl & 8)) acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[m], bh[nt & 1], acc[m][nt], 0, 0, 0);
+                        if (go) acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[m], bh[nt & 1], acc[m][nt], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (!(abl & 16)) {
 #pragma unroll
-                        for (int m = 0; m < 4; ++m) al[m] = *reinterpret_cast<const bf16x8*>(smem + n_off + m * (HWP * 16) + C5_PLANE);
-                    }
+                    for (int m = 0; m < 4; ++m) al[m] = *reinterpret_cast<const bf16x8*>(smem + n_off + m * (HWP * 16) + C5_PLANE);
 #pragma unroll
                     for (int m = 0; m < 4; ++m)
-                        if (go && !(abl & 8)) acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[m], bl[nt & 1], acc[m][nt], 0, 0, 0);
+                        if (go) acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[m], bl[nt & 1], acc[m][nt], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int m = 0; m < 4; ++m) {
-                        if (go && !(abl & 8)) acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[m], bh[nt & 1], acc[m][nt], 0, 0, 0);
-                        if (!(abl & 16)) ah[m] = *reinterpret_cast<const bf16x8*>(smem + n_off + m * (HWP * 16));
+                        if (go) acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[m], bh[nt & 1], acc[m][nt], 0, 0, 0);
+                        ah[m] = *reinterpret_cast<const bf16x8*>(smem + n_off + m * (HWP * 16));
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 __builtin_amdgcn_s_setprio(0);
-                if (nt == SYNC_NT) { if (q + G::PD < Q && !(abl & 2)) issue_W(q + G::PD, slot == 0 ? G::RD - 1 : slot - 1); }
-                if (nt == STAGE_NT && issue && !(abl & 1)) issue_A(want, KS == 5 ? (want & 1) : (want & 3));
+                if (nt == SYNC_NT) { if (q + G::PD < Q) issue_W(q + G::PD, slot == 0 ? G::RD - 1 : slot - 1); }
+                if (nt == STAGE_NT && issue) issue_A(want, KS == 5 ? (want & 1) : (want & 3));
             }
             flies = issue;
             slot_rt = nslot;
@@ -1262,7 +1234,6 @@ __global__ __launch_bounds__(256, 2) void c5_kernel(const C5Plan P) {
         }
     }
     C2_WAIT_VM(0);
-    if (stamp) P.stamps[wave * 8 + 2] = __builtin_amdgcn_s_memtime();
     // ---- epilogue: ConvQEpi (fp32 destination, optional accumulate), the wave's four tile rows ----
     ConvQEpi epi{};
     epi.a.Co = J.Co; epi.a.split = J.Co; epi.a.gpt = NT / 2; epi.a.phases = 0; epi.a.accumulate = J.accumulate;
@@ -1273,7 +1244,6 @@ __global__ __launch_bounds__(256, 2) void c5_kernel(const C5Plan P) {
     if constexpr (KS == 3) {
         if (J.epi == 3) {
             c5_finish_clstm<NT>(acc, clstm_pre, smem, wave, lane, b, y0, x0, n_tile, J, P.H, P.W);
-            if (stamp) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); P.stamps[wave * 8 + 3] = __builtin_amdgcn_s_memtime(); }
             return;
         }
     }
@@ -1442,12 +1412,6 @@ static hipError_t launch_c5_t(const C5Plan& P, unsigned grid, hipStream_t s) {
     return vpx_hip_last_error();
 }
 
-#ifdef VPX_DEV_SWITCHES
-static unsigned long long* g_c5_stamps = nullptr;
-static int g_c5_stamp_block = 0;
-extern "C" int vpx_dbg_c5_stamps(unsigned long long* dev_buf, int block) { g_c5_stamps = dev_buf; g_c5_stamp_block = block; return 0; }
-#endif
-
 hipError_t launch_c5(const C5Plan& P_in, int NT, hipStream_t s) {
     { const hipError_t ep = c5_flush_packs(s); if (ep != hipSuccess) return ep; }   // the packs this launch (and later ones of the call) read
     C5Plan P = P_in;
@@ -1456,13 +1420,6 @@ hipError_t launch_c5(const C5Plan& P_in, int NT, hipStream_t s) {
     // together: FETCH_SIZE 211 -> 170 MB per launch at B = 128, same time; the narrow launches keep the N tiles of a pixel tile together
     // (conv_o: 49 MB that way, 55 MB the other).
     P.order = NT == 8 ? 1 : 0;
-#ifdef VPX_DEV_SWITCHES
-    P.stamps = g_c5_stamps; P.stamp_block = g_c5_stamp_block;
-    P.ablate = dev_switch("VPX_C5_ABLATE", 0);
-    { const int o = dev_switch("VPX_C5_ORDER", -1); if (o >= 0) P.order = (o >> (NT == 8 ? 0 : (NT == 4 ? 1 : 2))) & 1; }   // bit 0 / 1 / 2: 128- / 64- / 32-column launches
-#else
-    P.ablate = 0;
-#endif
     for (int j = 0; j < P.njobs; ++j)
         for (int r = 0; r < 3; ++r) {
             C5Job& J = P.job[j];

@@ -288,9 +288,7 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(const float* __restric
 }
 
 bool wgrad_small_applicable(int Co, int C, int kh, int kw, int stride, int pad) {
-    static int env = -1;   // VPX_WGRAD_SMALL=0: MFMA kernels for these layers too (experiments)
-    if (env < 0) env = dev_switch("VPX_WGRAD_SMALL", 1);
-    if (!env || stride != 1 || kh != kw) return false;
+    if (stride != 1 || kh != kw) return false;
     if (kh == 3 && pad == 1) return (C == 1 && Co % 16 == 0 && Co <= 64) || (C == 3 && Co % 4 == 0 && Co <= 64);
     if (kh == 1 && pad == 0) return C == 16 && (Co == 1 || Co == 3);
     return false;
@@ -1084,19 +1082,13 @@ __global__ __launch_bounds__(512, 2) void wgrad_tg_kernel(const WgradArgs a, con
         } else {
         // group 0: multiply, then stage; group 1: stage, then multiply — as ONE copy of each (a three-phase loop the
         // compiler must not unroll)
-#ifdef VPX_ABLATE  // timing-only variants (results are wrong): 1 no multiply, 2 no split+store, 4 no global loads, 8 same order in both groups
-        const bool do_mul = !(a.dbg & 1), do_st = !(a.dbg & 2), do_ld = !(a.dbg & 4);
-        const int stage_phase = (tg == 1 && !(a.dbg & 8)) ? 0 : 2;
-#else
-        constexpr bool do_mul = true, do_st = true, do_ld = true;
         const int stage_phase = tg == 1 ? 0 : 2;
-#endif
 #pragma nounroll
         for (int phase = 0; phase < 3; ++phase) {
-            if (phase == 1) { if (do_mul) multiply_g(bcur); }
+            if (phase == 1) multiply_g(bcur);
             else if (phase == stage_phase) {
-                if (nxt.t < a.T && do_st) store_item(bnxt);
-                if (nn.t < a.T && do_ld) load_item(nn);
+                if (nxt.t < a.T) store_item(bnxt);
+                if (nn.t < a.T) load_item(nn);
             }
         }
         }
@@ -1139,9 +1131,6 @@ static hipError_t launch_wgrad_group(const WgradArgs& a_in, int n_slices, int ta
         return dim3((unsigned)(8 * ((total + 7) / 8)), 1, groups);
     };
     WgradArgs a = a_in;
-#ifdef VPX_ABLATE
-    a.dbg = dev_switch("VPX_WG_DBG", 0);
-#endif
     const dim3 grid = xcd_grid(a, ((a.N4 + 63) / 64) * a.n_ctiles);
     if (a.prec == VPX_PREC_BF16X3 || a.prec == VPX_PREC_BF16) {
         // activation vectors per thread and item: halo positions * 16 / 256 (3x3: 12, 5x5: 15, 7x7: 20)
@@ -1165,33 +1154,25 @@ static hipError_t launch_wgrad_group(const WgradArgs& a_in, int n_slices, int ta
             a.vec_all = vec ? 1 : 0;
         }
         // tap-group form (wgrad_tg_kernel)
-        static int tg_env = -1;  // VPX_WGRAD_TG=0 falls back to the older forms below (experiments)
-        if (tg_env < 0) tg_env = dev_switch("VPX_WGRAD_TG", 1);
         if constexpr (NTAPS >= 2) {
             const long long items = (long long)a.T * a.B * ((a.W + TILE_W - 1) / TILE_W) * ((a.H + TILE_H - 1) / TILE_H);
-            if (tg_env && a.vec_all && items + n_slices < (1ll << 31)) {
+            if (a.vec_all && items + n_slices < (1ll << 31)) {
                 // kernels up to 3x3: two buffers of 8 x 16 pixels fit the LDS. Larger kernels would need 4-row items (halo
                 // overhead 2.5x for 5x5): measured slower than the 128-row form below (PredRNN 5x5 step 332 vs 311 ms)
                 if (a.kh <= 3 && a.kw <= 3) {
                     const size_t l2 = 2 * (size_t)(2 * 128 * 128 + 2 * npos * 128);
-                    static int asp_env = -1;  // VPX_WGRAD_ASP=0: convert the activation operand in the kernel as before (experiments)
-                    if (asp_env < 0) asp_env = dev_switch("VPX_WGRAD_ASP", 1);
-                    if (a.a_split && asp_env && !a.a_sub && !a.use_org && NTAPS == 9 && npos * 16 <= 6 * 512)
+                    if (a.a_split && !a.a_sub && !a.use_org && NTAPS == 9 && npos * 16 <= 6 * 512)
                         return go(&wgrad_tg_kernel<NTAPS, 8, 6, true, true>, grid, 512, l2);
                     return go(&wgrad_tg_kernel<NTAPS, 8, 6>, grid, 512, l2);
                 }
-                static int tg1_env = -1;  // VPX_WGRAD_TG1=0: larger kernels on the 128-row form below
-                if (tg1_env < 0) tg1_env = dev_switch("VPX_WGRAD_TG1", 1);
-                if (tg1_env && npos <= 256)  // up to 5x5: one item buffer, 8 activation vectors per thread
+                if (npos <= 256)  // up to 5x5: one item buffer, 8 activation vectors per thread
                     return go(&wgrad_tg_kernel<NTAPS, 8, 8, false>, grid, 512, (size_t)(2 * 128 * 128 + 2 * npos * 128));
             }
         }
-        static int rb_env = -1;  // VPX_WGRAD_RB=1 forces the 4-wave, 64-row form
-        if (rb_env < 0) rb_env = dev_switch("VPX_WGRAD_RB", 0);
         // 8 waves / 128 rows / pipelined items when the 4-wave form's planes (> 80 KB: 5x5 and larger) allow one workgroup
         // per CU anyway; 3x3 keeps two independent 4-wave workgroups per CU (measured, training step: ConvLSTM 3x3
-        // 46.2 ms vs 50.9 ms with the 8-wave form; PredRNN 5x5 134.7 ms vs 127.6 ms). VPX_WGRAD_RB=1/2 forces a form.
-        if (a.N4 >= 128 && rb_env != 1 && (lds > 80 * 1024 || rb_env == 2)) {
+        // 46.2 ms vs 50.9 ms with the 8-wave form; PredRNN 5x5 134.7 ms vs 127.6 ms).
+        if (a.N4 >= 128 && lds > 80 * 1024) {
             const int apre2 = (npos * 16 + 2 * NTHREADS - 1) / (2 * NTHREADS);
             const dim3 g2 = xcd_grid(a, ((a.N4 + 127) / 128) * a.n_ctiles);
             const size_t lds2 = 2 * 128 * 256 + (size_t)npos * 128 * 2;

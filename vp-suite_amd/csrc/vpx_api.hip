@@ -51,14 +51,11 @@ bool ws_write_ok(const void* dst_, size_t bytes, const char* what) {
 
 int g_dry_run = 0;
 int g_deterministic = 0;
-int g_cell3_mode = -1;
-int g_cell2_mode = -1;
+// the kernel-selection options at their defaults; vpx_set_option is their only writer
+int g_cell3_mode = 1;
+int g_cell2_mode = 1;
 int g_experiment = 0;
-int g_mfma_shape = -1;
-int mfma_shape() {
-    if (g_mfma_shape < 0) g_mfma_shape = dev_switch("VPX_MFMA_SHAPE", VPX_MFMA_SHAPE_DEFAULT) ? 1 : 0;
-    return g_mfma_shape;
-}
+int g_mfma_shape = 1;   // measured (tools/ab_shape.py, B=128, one process, interleaved): 1.05-1.11x per fused step, every block shape
 
 }  // namespace vpx
 
@@ -74,7 +71,7 @@ const char* vpx_last_error(void) { return g_err; }
 int vpx_set_option(int option, int value) {
     ++g_option_epoch;
     if (option == VPX_OPT_CELL2) {
-        const int prev = cell2_mode();
+        const int prev = g_cell2_mode;
         vpx::g_cell2_mode = value < 0 ? 0 : (value > 2 ? 2 : value);
         return prev;
     }
@@ -84,7 +81,7 @@ int vpx_set_option(int option, int value) {
         return prev;
     }
     if (option == VPX_OPT_MFMA_SHAPE) {
-        const int prev = mfma_shape();
+        const int prev = g_mfma_shape;
         vpx::g_mfma_shape = value ? 1 : 0;
         return prev;
     }
@@ -94,7 +91,7 @@ int vpx_set_option(int option, int value) {
         return prev;
     }
     if (option == VPX_OPT_CELL3) {
-        const int prev = cell3_mode();
+        const int prev = g_cell3_mode;
         vpx::g_cell3_mode = value ? 1 : 0;
         return prev;
     }
@@ -138,12 +135,12 @@ static int c3_nt(const vpx_convlstm_desc* d, const ConvLSTMLayout& L) {   // 0: 
     // Measured (round 4, B = 4, 64x64 maps, Ch = 64: 128 half-tile workgroups of 39 us). First pass: 32-column tiles (512 workgroups) 34 us,
     // 64-column tiles (256) 36 us — the narrow tiles were bound by their K loop's bookkeeping. With that gone (convq.hip, "the K loop's
     // diet") the 64-column tiles win: cell (64,64,64^2) B = 4 0.309 vs 0.336 ms per 10 steps, inference step 1.60 vs 1.63 ms
-    // (tools/ab_c3_rule.sh) — half the stage copies per MFMA. With 192 half-tile workgroups (64x64 maps, Ch = 96: configs[3]'s shard) the
+    // — half the stage copies per MFMA. With 192 half-tile workgroups (64x64 maps, Ch = 96: configs[3]'s shard) the
     // 64-column c3 tiles are 1.4 % ahead on the whole model (5.70 vs 5.78 ms per step, the (64,96,64^2) cell alone 2 %), equal at B = 8 / 16 on
     // 64x64 maps with Ch = 64 (256 / 512 half-tile workgroups) — and behind once the 128x128 maps' 512 workgroups join (5.88 vs 5.72):
     // c3 up to 256 half-tile workgroups (128 in the first pass of the round, for the 32-column tiles).
-    if (mt * L.n_tiles > dev_switch("VPX_C3_MAX", 256)) return 0;
-    if (const int f = dev_switch("VPX_C3_NT", 0)) return f;   // (developer build only)
+    constexpr int C3_MAX = 256;
+    if (mt * L.n_tiles > C3_MAX) return 0;
     return (g_experiment & 8192) ? 2 : 4;   // VPX_OPT_EXPERIMENT bit 13: the 32-column tiles (tests, A/B runs)
 }
 
@@ -196,13 +193,11 @@ int vpx_convlstm_writes_split_output(const vpx_convlstm_desc* d) {   // the seco
 
 // The hoisted input projection W_x (*) x_t of all B*T frames (small-grid paths) as ONE launch of the schedule-driven K = 32 kernel
 // (convq.hip): a plain 3x3 'same' convolution whose output channel is the reference row of W (gate-major), on operand-format input.
-// 40 frames 64 -> 4x96 channels at 32x32: 84 -> ~25 us against the first-generation launch. VPX_HOIST_Q=0 keeps the latter.
+// 40 frames 64 -> 4x96 channels at 32x32: 84 -> ~25 us against the first-generation launch.
 static bool hoist_q_problem(const vpx_convlstm_desc* d, ConvQProblem& pr) {
-    static int on = -1;
-    if (on < 0) on = dev_switch("VPX_HOIST_Q", 1);
     memset(&pr, 0, sizeof(pr));
     if (g_experiment & 32) return false;   // VPX_OPT_EXPERIMENT bit 5: the first-generation launch (tests, A/B)
-    if (!on || d->precision != VPX_PREC_BF16X3 || d->kh != 3 || d->kw != 3 || (d->Cin & 15) || d->Cin < 16 || d->layout != VPX_LAYOUT_NHWC) return false;
+    if (d->precision != VPX_PREC_BF16X3 || d->kh != 3 || d->kw != 3 || (d->Cin & 15) || d->Cin < 16 || d->layout != VPX_LAYOUT_NHWC) return false;
     pr.N = d->B * d->T; pr.H = d->H; pr.W = d->W; pr.halo = 2;
     pr.nseg = 1;
     CQSeg& sg = pr.seg[0];

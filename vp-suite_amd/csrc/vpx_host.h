@@ -59,12 +59,9 @@ static inline int check_convlstm_desc(const vpx_convlstm_desc* d) {
 
 // Three k-steps per weight chunk when that removes the half-empty chunk at the end of every stage (the tap count is a
 // multiple of 3, e.g. 3x3: 9 k-steps per 16-channel stage = 3 chunks instead of 5) and the larger weight buffers do not
-// lower the number of resident workgroups. bf16 modes only. VPX_QPC=2/3 forces it.
+// lower the number of resident workgroups. bf16 modes only.
 static inline int pick_qpc(const int* segC, int nseg, int kh, int kw, int ng, int prec, int mw) {
-    static int forced = -1;
-    if (forced < 0) forced = dev_switch("VPX_QPC", 0);
     if (prec == VPX_PREC_F32 || (kh * kw) % 3 != 0 || mw > 2) return 2;
-    if (forced == 2 || forced == 3) return forced;
     auto residency = [&](int qpc) {
         const int cs = pick_stage_channels(segC, nseg, kh, kw, ng, prec, mw, 1, qpc);
         const int npos = (TILE_H * mw + kh - 1) * (TILE_W + kw - 1);
@@ -76,50 +73,39 @@ static inline int pick_qpc(const int* segC, int nseg, int kh, int kw, int ng, in
     return residency(3) >= residency(2) ? 3 : 2;
 }
 
-// workgroups a weight-gradient launch aims at (K slices x output tiles); VPX_WGRAD_WGS overrides (experiments)
-static inline int wgrad_target_wgs() {
-    static int v = -1;
-    if (v < 0) v = dev_switch("VPX_WGRAD_WGS", 1024);
-    return v;
-}
+// workgroups a weight-gradient launch aims at (K slices x output tiles)
+constexpr int WGRAD_TARGET_WGS = 1024;
 
 // Second-generation fused cell (cell2.hip) applies to: bf16x3, 3x3, channel counts in whole 16-channel stages, maps
 // taller than half a 32x16 tile, and a launch of at least 128 workgroups (half the CUs: measured crossover, B=16 +11 %, B=32
-// +3 % against a bar of 256; below, the first-generation kernel's 128-pixel tiles fill more CUs). VPX_CELL2=0 disables it, =2 forces it
-// wherever the shape allows (experiments).
-extern int g_cell2_mode;  // vpx_api.hip: -1 = not yet read from the environment
-static inline int cell2_mode() {
-    if (g_cell2_mode < 0) g_cell2_mode = dev_switch("VPX_CELL2", 1);
-    return g_cell2_mode;
-}
+// +3 % against a bar of 256; below, the first-generation kernel's 128-pixel tiles fill more CUs). vpx_set_option(VPX_OPT_CELL2): 0 disables
+// it, 2 forces it wherever the shape allows (experiments).
+extern int g_cell2_mode;  // vpx_api.hip: 0 / 1 / 2, written by vpx_set_option only
+// workgroups of the launch from which the second-generation cell takes the step.
+// 64 (= 128 half tiles of four waves, cell2_kernel_q<.., 4>): the B=4 steps of the 64x64 blocks, whose first-generation launch
+// has exactly 256 workgroups, run 48 -> 38 us there (B=4 step 2.13 -> 1.93 ms; B=4 at 3x128x128 6.71 -> 5.89 ms)
+constexpr int CELL2_MIN_WGS = 64;
 static inline bool cell2_applicable(const vpx_convlstm_desc* d) {
-    if (cell2_mode() == 0) return false;
+    if (g_cell2_mode == 0) return false;
     if (d->kh != 3 || d->kw != 3) return false;
     if (d->precision == VPX_PREC_BF16) {
         // plain bf16 (BASELINE configs[1]'s literal dtype): inference only, on the half tile of the 16x16x32 form (cell2_kernel_q<.., 4, true>);
         // a call that saves for the backward pass stays on the first-generation kernel, whose BPTT kernels know this mode
-        if ((d->flags & VPX_FLAG_SAVE_FOR_BWD) || mfma_shape() != 1 || (d->H & 15) || (d->W & 15) || (d->Ch & 31)) return false;
+        if ((d->flags & VPX_FLAG_SAVE_FOR_BWD) || g_mfma_shape != 1 || (d->H & 15) || (d->W & 15) || (d->Ch & 31)) return false;
     } else if (d->precision != VPX_PREC_BF16X3) return false;
     if ((d->Cin & 15) || (d->Ch & 15) || (d->Cin + d->Ch) / 16 > MAX_STAGE) return false;
     // 16-row maps: on the half tile (q form) only. Measured at B=128, (96,96,16x16): 128 -> 106 us per step against the
-    // first-generation kernel (384 workgroups of four waves); VPX_CELL2_H16=0 keeps them there
-    static int h16 = -1;
-    if (h16 < 0) h16 = dev_switch("VPX_CELL2_H16", 1);
-    if (d->H < 16 || (d->H == 16 && !(h16 && mfma_shape() == 1 && (d->W & 15) == 0 && (d->Ch & 31) == 0))) return false;
-    if (cell2_mode() == 2) return true;
+    // first-generation kernel (384 workgroups of four waves)
+    if (d->H < 16 || (d->H == 16 && !(g_mfma_shape == 1 && (d->W & 15) == 0 && (d->Ch & 31) == 0))) return false;
+    if (g_cell2_mode == 2) return true;
     const long long wgs = (long long)d->B * ((d->H + 31) / 32) * ((d->W + 15) / 16) * ((d->Ch + 31) / 32);
-    static int min_wgs = -1;   // VPX_CELL2_MIN_WGS: experiment override of the bar below
-    // 64 (= 128 half tiles of four waves, cell2_kernel_q<.., 4>): the B=4 steps of the 64x64 blocks, whose first-generation launch
-    // has exactly 256 workgroups, run 48 -> 38 us there (B=4 step 2.13 -> 1.93 ms; B=4 at 3x128x128 6.71 -> 5.89 ms)
-    if (min_wgs < 0) min_wgs = dev_switch("VPX_CELL2_MIN_WGS", 64);
-    return wgs >= min_wgs;
+    return wgs >= CELL2_MIN_WGS;
 }
 
 // 16x16x32 form of the second-generation kernels (vpx_set_option(VPX_OPT_MFMA_SHAPE)): the fused cell's q-form epilogue is the
 // vectorised one only — tiles inside the image, whole 32-channel tiles
-#define VPX_MFMA_SHAPE_DEFAULT 1   // measured (tools/ab_shape.py, B=128, one process, interleaved): 1.05-1.11x per fused step, every block shape
 static inline bool cell2_q_applicable(const vpx_convlstm_desc* d) {
-    return mfma_shape() == 1 && (d->H & 15) == 0 && (d->W & 15) == 0 && (d->Ch & 31) == 0;   // (H % 32 == 16: the half tile only)
+    return g_mfma_shape == 1 && (d->H & 15) == 0 && (d->W & 15) == 0 && (d->Ch & 31) == 0;   // (H % 32 == 16: the half tile only)
 }
 
 struct ConvLSTMLayout {  // derived sizes shared by workspace query, fwd and bwd
@@ -151,11 +137,9 @@ struct ConvLSTMLayout {  // derived sizes shared by workspace query, fwd and bwd
 
 // Blocks whose FORWARD did not run on the operand-format kernel (16x16 maps, small grids) still take the wgrad2 weight gradient:
 // the backward converts x, the output sequence and h0 to the split format itself (small tensors there) and the gate-backward
-// kernel writes dG in both forms. VPX_WGRAD2_WSP=0 disables.
+// kernel writes dG in both forms.
 static inline bool wgrad2_wsp(const vpx_convlstm_desc* d, const ConvLSTMLayout& L) {
-    static int env = -1;
-    if (env < 0) env = dev_switch("VPX_WGRAD2_WSP", 1);
-    return env && !L.v2 && d->precision == VPX_PREC_BF16X3 && d->kh == 3 && d->kw == 3 && (d->Cin & 7) == 0 && (d->Ch & 7) == 0;
+    return !L.v2 && d->precision == VPX_PREC_BF16X3 && d->kh == 3 && d->kw == 3 && (d->Cin & 7) == 0 && (d->Ch & 7) == 0;
 }
 
 static inline int convlstm_layout(const vpx_convlstm_desc* d, ConvLSTMLayout& L) {
@@ -181,11 +165,9 @@ static inline int convlstm_layout(const vpx_convlstm_desc* d, ConvLSTMLayout& L)
         const long long m_tiles = (long long)d->B * ((d->H + TILE_H - 1) / TILE_H) * ((d->W + TILE_W - 1) / TILE_W);
         // the fused launch would leave CUs idle (small batches / maps). Measured on MI355X, bf16x3, (96,96,16x16):
         // B=4 (24 workgroups fused) 20 -> 39 TF with the split; B=32 (192 workgroups) 155 -> 164 TF with 2 splits
-        static int bar = -1;  // VPX_SPLIT_BAR: experiment override of the workgroup-count bar below
-        if (bar < 0) bar = dev_switch("VPX_SPLIT_BAR", 256);
-        static int bar3 = -1;  // VPX_CELL3_BAR: workgroup count of the fused launch below which cell3.hip takes the step (where it applies)
-        if (bar3 < 0) bar3 = dev_switch("VPX_CELL3_BAR", 256);
-        const bool force2 = cell2_mode() == 2 && cell2_applicable(d);   // "wherever the shape allows": also on small grids (tests, A/B)
+        constexpr int bar = 256;   // workgroup count of the fused launch below which the step is split
+        constexpr int bar3 = 256;  // ... below which cell3.hip takes the step (where it applies)
+        const bool force2 = g_cell2_mode == 2 && cell2_applicable(d);   // "wherever the shape allows": also on small grids (tests, A/B)
         const bool want3 = !force2 && m_tiles * L.n_tiles < bar3 && cell3_applicable(d);
         if (!force2 && (m_tiles * L.n_tiles < bar || want3)) {
             const int ng = plain_groups(4 * d->Ch);
@@ -198,9 +180,7 @@ static inline int convlstm_layout(const vpx_convlstm_desc* d, ConvLSTMLayout& L)
             const int ks = (L.s_nstage > 0 && m_tiles * L.n_tiles < bar) ? pick_ksplit(m_tiles * tiles, L.s_nstage) : 1;
             if (ks > 1) { L.split = ks; L.s_ng = ng; L.s_tiles = tiles; }
             L.hoist = 0;
-            static int hoist_on = -1;  // VPX_HOIST=0 disables (experiments)
-            if (hoist_on < 0) hoist_on = dev_switch("VPX_HOIST", 1);
-            if (L.split && d->T > 1 && hoist_on) {
+            if (L.split && d->T > 1) {
                 const int sx[1] = {d->Cin}, sh[1] = {d->Ch};
                 L.hx_nstage = build_stages(L.hx_stage, &L.hx_chunks, sx, 1, L.taps, pick_stage_channels(sx, 1, d->kh, d->kw, ng, d->precision), d->precision);
                 L.hh_nstage = build_stages(L.hh_stage, &L.hh_chunks, sh, 1, L.taps, cs, d->precision);
@@ -247,7 +227,7 @@ static inline int convlstm_layout(const vpx_convlstm_desc* d, ConvLSTMLayout& L)
         const int out_tiles = ((N4 + 63) / 64) * L.n_ctiles * ((L.taps + 8) / 9);
         // rounded DOWN: the launch runs one workgroup per CU in rounds of 256, and 1032 workgroups (86 slices x 12 tiles) took
         // five rounds where 1008 take four (measured: training step 144.8 -> 140.2 ms)
-        long long ns = wgrad_target_wgs() / out_tiles;
+        long long ns = WGRAD_TARGET_WGS / out_tiles;
         if (ns > items) ns = items;
         if (ns > 256) ns = 256;
         if (ns < 1) ns = 1;
@@ -257,7 +237,7 @@ static inline int convlstm_layout(const vpx_convlstm_desc* d, ConvLSTMLayout& L)
         L.n_slices2 = 0;
         if (L.v2 || wgrad2_wsp(d, L)) {
             const bool half_tail = L.ct[L.n_ctiles - 1].h[1].cn == 0;
-            long long ns2 = wgrad2_slices(wgrad2_target_wgs(), (N4 + 127) / 128, L.n_ctiles, half_tail);
+            long long ns2 = wgrad2_slices(WGRAD2_TARGET_WGS, (N4 + 127) / 128, L.n_ctiles, half_tail);
             if (ns2 > items) ns2 = items;
             if (ns2 < 1) ns2 = 1;
             L.n_slices2 = (int)ns2;
@@ -377,7 +357,7 @@ static inline int wgrad_slices_for(int N, int H, int W, int Co, int Ci, int kh, 
 // slices actually launched: enough for ~1024 workgroups (each slice costs a slab write + a reduce read of all of dW)
 static inline int wgrad_pick_slices(int cap, int rows, int n_ctiles, int taps) {
     const int out_tiles = ((rows + 63) / 64) * n_ctiles * ((taps + 8) / 9);
-    int ns = wgrad_target_wgs() / out_tiles;   // rounded down: whole rounds of 256 workgroups (see convlstm_layout)
+    int ns = WGRAD_TARGET_WGS / out_tiles;   // rounded down: whole rounds of 256 workgroups (see convlstm_layout)
     if (ns > cap) ns = cap;
     return ns < 1 ? 1 : ns;
 }

@@ -51,7 +51,6 @@ struct ConvPlan {
     int grid_m, grid_n;   // set by the launcher: pixel tiles / N tiles of the flattened, XCD-aware 1-D grid (grid_n = 0: 2-D grid)
     int qpc;              // k-steps per weight chunk the weights were packed with (0/2: two; 3: three, bf16 modes only)
     int ksplit;           // > 1: the stage list is split over blockIdx.z (plain epilogue only; partial sums via atomics)
-    int dbg;              // ablation bits for profiling (VPX_DBG): 1 skip MFMAs, 2 skip activation loads, 4 skip weight loads, 8 skip epilogue
     // generalised geometry (all 0 = the stride-1 "same" convolution every recurrent cell uses):
     int stride;           // input step per output pixel (0/1 or 2)
     int use_org;          // 1: the halo origin of output pixel (0,0) is (org_y, org_x) instead of (-kh/2, -kw/2)
@@ -213,18 +212,10 @@ hipError_t launch_split_convert(const float* src, void* dst, long long npix, int
 hipError_t launch_cell2_pack(const Cell2Pack& pk, void* dst, hipStream_t s);
 size_t cell2_packed_bytes(int n_tiles, int chunks_total);   // 32x32x16 form: chunks of 24 KiB (3 per stage)
 size_t cell2_packed_bytes_q(int n_tiles, int S);             // q form: cell2_qchunks(S) chunks of 16 KiB
-// Developer switches (VPX_* kernel-selection experiments of rounds 1-3, listed in DESIGN.md). The PRODUCT library never reads the
-// process environment: dev_switch() yields the default there, so kernel selection depends on the descriptor and on
-// vpx_set_option / vpx_set_deterministic only. The developer build (`make -C vp-suite_amd/csrc ablate`, -DVPX_DEV_SWITCHES; loaded
-// through VPX_LIB by the scripts under tools/) reads the variable of that name.
-#ifdef VPX_DEV_SWITCHES
-static inline int dev_switch(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-#else
-static inline int dev_switch(const char*, int dflt) { return dflt; }
-#endif
+// The library never reads the process environment: kernel selection depends on the descriptor and on vpx_set_option /
+// vpx_set_deterministic only. The tuning values of the selection rules are constants next to the rules they feed.
 extern int g_experiment;   // vpx_api.hip: bits of kernel experiments in flight (vpx_set_option(VPX_OPT_EXPERIMENT)); 0 in the product
-extern int g_mfma_shape;   // vpx_api.hip: -1 = not yet read from the environment (VPX_MFMA_SHAPE), else 0 / 1 (vpx_set_option)
-int mfma_shape();
+extern int g_mfma_shape;   // vpx_api.hip: 0 / 1 (vpx_set_option(VPX_OPT_MFMA_SHAPE)), default 1
 hipError_t launch_cell2(const Cell2Plan& plan, const ConvLSTMStepArgs& ea, void* h_sp, long long h_sp_bstride, hipStream_t s);
 // the same step on the eight-wave half tile (cell2x.hip, round 6: 64-register wave tiles, four waves per SIMD); plan.qform launches only
 // (maps in whole 16x16 tiles, whole 32-channel N tiles), tiles_y / grid_m set for 16-row tiles. VPX_OPT_EXPERIMENT bit 15 selects it
@@ -270,7 +261,6 @@ struct ConvQPlan {
     int n_groups, gpt;         // 32-column output groups in total / per N tile
     int S, SP, nsub, nchunk_total, pro_stage1;   // stages; stages per pass of the schedule; its entries; weight chunks; copy stage 1 in the prologue
     int oy, ox, nseg;
-    int dbg, _pd;              // timing ablations (VPX_CQ_DBG, experiments): 1 no MFMAs, 2 no stage copies, 4 no weight copies, 8 no epilogue
     CQSeg seg[4];
     const char* wpk;           // [n_tile][chunk][16 KiB]
     unsigned long long sched[64];   // per step; only a chunk's FIRST entry is decoded in full (its events)
@@ -311,8 +301,7 @@ struct Cell3Args {
     char* h_sp_out; long long h_sp_out_bstride;   // split h_t for the next step (or null), BYTES
     ConvLSTMStepArgs ea;
 };
-extern int g_cell3_mode;   // vpx_api.hip: -1 = not yet read from the environment (VPX_CELL3), else 0 / 1 (vpx_set_option)
-int cell3_mode();
+extern int g_cell3_mode;   // vpx_api.hip: 0 / 1 (vpx_set_option(VPX_OPT_CELL3)), default 1
 bool cell3_applicable(const vpx_convlstm_desc* d);
 size_t cell3_packed_bytes(int Ch);
 hipError_t launch_cell3_pack(const Cell3Pack& pk, void* dst, hipStream_t s);
@@ -460,15 +449,14 @@ struct WgradArgs {
     int a_Hs, a_Ws;           // valid rows / columns of the sub-image
     int a_Wfull;              // pixels per row of the full image (the batch stride is x_bstride)
     int use_org, org_y, org_x;  // tap (0,0) reads activation pixel (y + org_y, x + org_x) instead of (y - kh/2, x - kw/2)
-    int dbg;                    // timing ablations, -DVPX_ABLATE builds only (VPX_WG_DBG: 1 = no multiply, 2 = stage the first item only)
     // activation operand pre-split (ConvLSTM block after a cell2 forward): x, h_{t-1} and h_0 again in the split-bf16 operand
     // format (cell2.hip); the tap-group kernel then stages the halo tile by LDS-DMA instead of load + split + store
     int a_split;
+    int vec_all;                // set by launch_wgrad: every operand allows 16-byte vector loads (bf16 forms: unconditional load issue)
     const char* x_sp; long long x_sp_bstride, x_sp_tstride;    // BYTES
     const char* h_sp; long long h_sp_bstride, h_sp_tstride;    // h_t of step t at h_sp + t * tstride (time-major slots), BYTES
     const char* h0_sp;                                         // [B][HW][Ch] or null
     const char* g_sp;           // dG again in split format [T][B][HW][N4] (gate-backward kernel), or null: with a_split, selects wgrad2.hip
-    int vec_all;                // set by launch_wgrad: every operand allows 16-byte vector loads (bf16 forms: unconditional load issue)
     int grid_x, grid_slices;    // set by launch_wgrad: logical grid (row tile x column tile, K slice) behind the XCD-aware 1-D launch
     int w2_nh, w2_ns_half;      // set by launch_wgrad2: row tiles of a half-empty last column tile (0 = none) and their slice count
 };
@@ -485,7 +473,7 @@ hipError_t launch_wgrad_small(const float* dy, const float* x, int N, int H, int
                               float* dw, hipStream_t s);
 // wgrad2.hip: both operands pre-split (3x3, bf16x3); writes slabs [used_slices][9][N4][Ct] like launch_wgrad
 bool wgrad2_applicable(const WgradArgs& a);
-int wgrad2_target_wgs();   // workgroups a wgrad2 launch aims at (512 = two rounds of one-per-CU workgroups; VPX_WGRAD2_WGS overrides)
+constexpr int WGRAD2_TARGET_WGS = 512;   // workgroups a wgrad2 launch aims at (two rounds of one-per-CU workgroups)
 // K slices of a wgrad2 launch over `rows128` row tiles x n_ctiles column tiles (the last one half-empty or not), before the caps
 // by the caller's slab space and the item count. One rule for the launch (launch_wgrad2) and the slab sizing (convlstm_layout).
 static inline int wgrad2_slices(int target, int rows128, int n_ctiles, bool half_tail) {
@@ -561,8 +549,7 @@ struct C5Plan {
     int B, H, W, tiles_x, tiles_y, m_tiles;
     C5Src src[4];
     int ks;                                  // kernel size of every job: 0 | 5 = 5x5 (ST-LSTM step), 3 = 3x3 (ConvLSTM step on small grids)
-    unsigned long long* stamps; int stamp_block;   // developer timing stamps (null in the product; vpx_dbg_c5_stamps)
-    int ablate, order;                       // ablate: developer build only (VPX_C5_ABLATE). order: 0 = the N tiles of a pixel tile adjacent in an XCD's dispatch order, 1 = the pixel tiles of an N tile adjacent
+    int order;                               // 0 = the N tiles of a pixel tile adjacent in an XCD's dispatch order, 1 = the pixel tiles of an N tile adjacent
     int njobs; C5Job job[C5_MAX_JOBS];
 };
 static_assert(sizeof(C5Plan) <= 4096, "C5Plan travels as a kernel argument (4 KiB)");
@@ -589,7 +576,6 @@ struct STWArgs {
     STWPair pair[STW_MAX_PAIRS];
     float* slabs;                // [n_slices][npairs][25][128][64]
     size_t slab_stride;          // floats per slice
-    unsigned long long* stamps; int stamp_block, _spad;   // developer timing stamps (null in the product; vpx_dbg_stw_stamps)
 };
 struct STWOut { float* dW[5]; int Ct[5]; int ntaps[5]; signed char blockmap[5][8]; };   // Wx, Wh, Wm, Wo, Wlast
 int stw_build(STWArgs& a, STWOut& o, int B, int H, int W, int Cin, int Ch);   // fills the pair table; returns npairs (-1: too many)

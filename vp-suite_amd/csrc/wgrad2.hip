@@ -58,13 +58,6 @@ __device__ __forceinline__ void w2_dma16(const char* g, char* lds_wave_base) {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#ifdef VPX_DEV_SWITCHES
-// developer build: per WORKGROUP start / end of the item loop (s_memtime), HW_ID | XCC_ID << 32, and what it worked on (stw_kernel: pass | slice << 8 |
-// pair << 24; wgrad2_kernel: 4 | half-tail << 3 | slice << 8 | tile << 24) — how a launch's workgroups were dealt to XCDs and CUs and how long each
-// ran (tools/trace_stw.py; vpx_dbg_stw_trace reads it back). Only times of ONE CU may be compared: the counter's base differs between shader engines.
-__device__ unsigned long long stw_trace[8192 * 4];
-#endif
-
 // QF: the same kernel on v_mfma_f32_16x16x32_bf16 (vpx_set_option(VPX_OPT_MFMA_SHAPE, 1)): a K = 32 step is two tile rows of the
 // item, a wave's 64 gate rows x 32 channels x tap group are 4 x 2 accumulator tiles of 16x16 per tap (the same 160 registers),
 // the same fragment bytes per MFMA cycle.
@@ -102,16 +95,6 @@ __global__ __launch_bounds__(512, 2) void wgrad2_kernel(const WgradArgs a) {
         bx = fi >= 0 ? (fi / n_ctf) * a.n_ctiles + fi % n_ctf : (-1 - fi) * a.n_ctiles + (a.n_ctiles - 1);
         slice = __builtin_amdgcn_readfirstlane(slice); bx = __builtin_amdgcn_readfirstlane(bx); ns = __builtin_amdgcn_readfirstlane(ns);
     }
-#ifdef VPX_DEV_SWITCHES
-    if (threadIdx.x == 0 && blockIdx.x < 8192) {
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        stw_trace[blockIdx.x * 4 + 0] = __builtin_amdgcn_s_memtime();
-        stw_trace[blockIdx.x * 4 + 2] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
-        stw_trace[blockIdx.x * 4 + 3] = 4ull | (ns != a.grid_slices ? 8ull : 0ull) | ((unsigned long long)slice << 8) | ((unsigned long long)bx << 24);
-    }
-#endif
     const int n_ct = a.n_ctiles;
     const int ct_id = __builtin_amdgcn_readfirstlane(bx % n_ct);
     const WgradCHalf ch0 = a.ct[ct_id].h[0], ch1 = a.ct[ct_id].h[1];
@@ -361,9 +344,6 @@ __global__ __launch_bounds__(512, 2) void wgrad2_kernel(const WgradArgs a) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         cur = nxt; advance(nxt); bsel ^= 1;
     }
-#ifdef VPX_DEV_SWITCHES
-    if (threadIdx.x == 0 && blockIdx.x < 8192) stw_trace[blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memtime();
-#endif
 
     if (ksplit) {
         // pair reduction (once per workgroup): the wc = 1 wave of each (tap group, row half) pair parks its accumulators in LDS,
@@ -450,21 +430,13 @@ __global__ __launch_bounds__(512, 2) void wgrad2_kernel(const WgradArgs a) {
 
 // Applies when launch_wgrad would pick the pre-split tap-group kernel AND dG is available in split format: 3x3, bf16x3.
 bool wgrad2_applicable(const WgradArgs& a) {
-    static int env = -1;   // VPX_WGRAD2=0: keep wgrad_tg_kernel (experiments)
-    if (env < 0) env = dev_switch("VPX_WGRAD2", 1);
-    if (!env || !a.a_split || !a.g_sp || a.kh != 3 || a.kw != 3 || a.prec != VPX_PREC_BF16X3) return false;
+    if (!a.a_split || !a.g_sp || a.kh != 3 || a.kw != 3 || a.prec != VPX_PREC_BF16X3) return false;
     if (a.a_sub || a.use_org || a.blk || (a.n_out && a.n_out != a.N4) || (a.N4 & 7) || (a.Cin & 7) || (a.Ch & 7)) return false;
     const long long items = (long long)a.T * a.B * ((a.W + 15) / 16) * ((a.H + W2_TH - 1) / W2_TH);
     return items + 4096 < (1ll << 31);
 }
 
-int wgrad2_target_wgs() {
-    static int target = -1;
-    if (target < 0) target = dev_switch("VPX_WGRAD2_WGS", 512);
-    return target;
-}
-
-// slices: whole rounds of 256 one-per-CU workgroups (two rounds by default, VPX_WGRAD2_WGS overrides), at most max_slices
+// slices: whole rounds of 256 one-per-CU workgroups (two rounds: WGRAD2_TARGET_WGS), at most max_slices
 hipError_t launch_wgrad2(const WgradArgs& a_in, int max_slices, int* used_slices, int* tail_col0, int* tail_slices, hipStream_t s) {
     static bool attr_set = false;
     if (!attr_set) {
@@ -474,7 +446,7 @@ hipError_t launch_wgrad2(const WgradArgs& a_in, int max_slices, int* used_slices
         if (e != hipSuccess) return e;
         attr_set = !g_dry_run;
     }
-    const int target = wgrad2_target_wgs();
+    const int target = WGRAD2_TARGET_WGS;
     WgradArgs a = a_in;
     const int rows = (a.N4 + 127) / 128;
     a.grid_x = rows * a.n_ctiles;
@@ -497,7 +469,7 @@ hipError_t launch_wgrad2(const WgradArgs& a_in, int max_slices, int* used_slices
     *tail_slices = half_tail ? a.w2_ns_half : ns;
     const long long total = (long long)nf * ns + (long long)a.w2_nh * a.w2_ns_half;
     if (!ws_write_ok(a.slabs, (size_t)ns * 9 * a.N4 * a.Ct * sizeof(float), "weight-gradient slabs (wgrad2_kernel)")) return hipErrorInvalidValue;
-    if (mfma_shape() == 1) VPX_LAUNCH(wgrad2_kernel<true>, dim3((unsigned)(8 * ((total + 7) / 8))), dim3(512), W2_LDS, s, a);
+    if (g_mfma_shape == 1) VPX_LAUNCH(wgrad2_kernel<true>, dim3((unsigned)(8 * ((total + 7) / 8))), dim3(512), W2_LDS, s, a);
     else VPX_LAUNCH(wgrad2_kernel<false>, dim3((unsigned)(8 * ((total + 7) / 8))), dim3(512), W2_LDS, s, a);
     return vpx_hip_last_error();
 }
@@ -505,7 +477,7 @@ hipError_t launch_wgrad2(const WgradArgs& a_in, int max_slices, int* used_slices
 // ---- glue form (wgrad2_kernel<true, true>): one stride residue of a stage-glue layer's weight gradient, both operands pre-split ----
 bool wgrad2g_applicable(const WgradArgs& a) {
     if (g_experiment & (1 << 29)) return false;   // VPX_OPT_EXPERIMENT bit 29: the tap-group kernel on fp32 operands (A/B runs, tests)
-    if (mfma_shape() != 1 || a.prec != VPX_PREC_BF16X3 || !a.g_sp || !a.x_sp || a.T != 1) return false;
+    if (g_mfma_shape != 1 || a.prec != VPX_PREC_BF16X3 || !a.g_sp || !a.x_sp || a.T != 1) return false;
     const int taps = a.kh * a.kw;
     if (taps < 2 || a.kh > 3 || a.kw > 3) return false;
     if (a.blk || (a.n_out && a.n_out != a.N4) || (a.N4 & 7) || (a.Cin & 7) || a.Ct != a.Cin) return false;
@@ -535,7 +507,7 @@ hipError_t launch_wgrad2g(const WgradArgs& a_in, int max_slices, int* used_slice
     a.grid_x = rows * a.n_ctiles;
     const bool half_tail = a.ct[a.n_ctiles - 1].h[1].cn == 0;
     a.w2_nh = half_tail ? rows : 0;
-    int ns = wgrad2_target_wgs() / a.grid_x;
+    int ns = WGRAD2_TARGET_WGS / a.grid_x;
     if (ns > max_slices) ns = max_slices;
     const long long items = (long long)a.B * ((a.W + 15) / 16) * ((a.H + W2_TH - 1) / W2_TH);
     if (ns > items) ns = (int)items;
@@ -611,16 +583,6 @@ __global__ __launch_bounds__(512, 2) void stw_kernel(const STWArgs a) {
         }
         slice = __builtin_amdgcn_readfirstlane(slice); pair_i = __builtin_amdgcn_readfirstlane(pair_i); pass = __builtin_amdgcn_readfirstlane(pass);
     }
-#ifdef VPX_DEV_SWITCHES
-    if (threadIdx.x == 0 && blockIdx.x < 8192) {
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        stw_trace[blockIdx.x * 4 + 0] = __builtin_amdgcn_s_memtime();
-        stw_trace[blockIdx.x * 4 + 2] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
-        stw_trace[blockIdx.x * 4 + 3] = (unsigned long long)pass | ((unsigned long long)slice << 8) | ((unsigned long long)pair_i << 24);
-    }
-#endif
     const STWPair pr = a.pair[pair_i];
     const STWHalf ch0 = pr.h[0], ch1 = pr.h[1];
     const int n0 = pr.n0;
@@ -675,7 +637,7 @@ __global__ __launch_bounds__(512, 2) void stw_kernel(const STWArgs a) {
     }
     // An item = (sample b, tile row ty, tile column tx); a workgroup's items lie n_slices apart: the next one is found by carrying, not by
     // dividing (two scalar divisions per item were a fifth of the 250 instructions a wave spent requesting an item's copies — as long as
-    // a quarter of its products, in-kernel stamps), and the two sources' base addresses stay in vector registers (the kernel is at the
+    // a quarter of its products, in-kernel clock readings), and the two sources' base addresses stay in vector registers (the kernel is at the
     // SGPR limit: as scalars they were reloaded from the kernel arguments for every item, s_waitcnt lgkmcnt(0) included).
     struct SItem { int w, b, ty, tx; };
     const int it_db = a.n_slices / tiles, it_dty = (a.n_slices % tiles) / tiles_x, it_dtx = (a.n_slices % tiles) % tiles_x;
@@ -771,39 +733,14 @@ __global__ __launch_bounds__(512, 2) void stw_kernel(const STWArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     int bsel = 0;
-#ifdef VPX_DEV_SWITCHES
-    // developer timing stamps: shader cycles of one workgroup's waves spent requesting copies / multiplying / at the item's sync point
-    const bool stamp = a.stamps != nullptr && (int)blockIdx.x == a.stamp_block;
-    unsigned long long t_dma = 0, t_mul = 0, t_sync = 0, n_it = 0;
-#endif
     while (cur.w < n_items) {
         char* bcur = smem + bsel * W5_BUF;
         char* bnxt = smem + (bsel ^ 1) * W5_BUF;
-#ifdef VPX_DEV_SWITCHES
-        const unsigned long long t0 = stamp ? __builtin_amdgcn_s_memtime() : 0;
-#endif
         if (nxt.w < n_items) dma_item(nxt, bnxt);
-#ifdef VPX_DEV_SWITCHES
-        const unsigned long long t1 = stamp ? __builtin_amdgcn_s_memtime() : 0;
-#endif
         if (active) multiply(bcur);
-#ifdef VPX_DEV_SWITCHES
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const unsigned long long t2 = stamp ? __builtin_amdgcn_s_memtime() : 0;
-#endif
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#ifdef VPX_DEV_SWITCHES
-        if (stamp) { const unsigned long long t3 = __builtin_amdgcn_s_memtime(); t_dma += t1 - t0; t_mul += t2 - t1; t_sync += t3 - t2; ++n_it; }
-#endif
         cur = nxt; advance(nxt); bsel ^= 1;
     }
-#ifdef VPX_DEV_SWITCHES
-    if (threadIdx.x == 0 && blockIdx.x < 8192) stw_trace[blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memtime();
-    if (stamp && lane == 0) {
-        a.stamps[wave * 8 + 0] = t_dma; a.stamps[wave * 8 + 1] = t_mul; a.stamps[wave * 8 + 2] = t_sync; a.stamps[wave * 8 + 3] = n_it;
-        a.stamps[wave * 8 + 4] = (unsigned long long)pass; a.stamps[wave * 8 + 5] = (unsigned long long)pair_i;
-    }
-#endif
 
     if (ksplit || tsplit) {
         // pair reduction: the second wave of each pair parks its accumulators in LDS, the first adds them (two row tiles at a time:
@@ -945,37 +882,17 @@ int stw_slices(int npairs, long long items) {   // npairs: the k x k tensors' pa
     int ns = (480 + npairs * 3 / 2) / (npairs * 3);
     // round 5: whole slices per XCD (stw_kernel's block decode) wherever a slice keeps >= 32 items — 8, 16 or 32 of them as the item list grows
     // (the deferred weight gradients of a whole pass: 19 456 items at B = 128): finer workgroups fill the last dispatch round of every XCD, a
-    // slab costs 0.8 MB per pair. Measured, PredRNN-V2 training step (A/B builds -DVPX_STW_NS_FIXED=n, one box): B = 128 round-4 rule (4 slices,
+    // slab costs 0.8 MB per pair. Measured, PredRNN-V2 training step (A/B builds with a fixed slice count, one box): B = 128 round-4 rule (4 slices,
     // contiguous ranges) 307.8 / 308.8 ms, 8 slices 297.8, 16 291.0, 32 288.1 / 287.8, 48 286.5; configs[4]'s shard (2 496 items) 82.5 -> 80.1 / 79.6 / 80.1.
     if (items >= 32 * 256) ns = 32;
     else if (items >= 16 * 128) ns = 16;
     else if (items >= 8 * 32) ns = 8;
-#ifdef VPX_DEV_SWITCHES
-    ns = dev_switch("VPX_STW_NS", ns);
-#endif
-#ifdef VPX_STW_NS_FIXED
-    ns = VPX_STW_NS_FIXED ? VPX_STW_NS_FIXED : (480 + npairs * 3 / 2) / (npairs * 3);   // A/B builds (0: the round-4 rule)
-#endif
     if (ns > items / 8) ns = (int)(items / 8);
     return ns < 1 ? 1 : ns;
 }
 
-#ifdef VPX_DEV_SWITCHES
-static unsigned long long* g_stw_stamps = nullptr;
-static int g_stw_stamp_block = 0;
-extern "C" int vpx_dbg_stw_stamps(unsigned long long* dev_buf, int block) { g_stw_stamps = dev_buf; g_stw_stamp_block = block; return 0; }
-extern "C" int vpx_dbg_stw_trace(unsigned long long* out32768) {
-    return (int)hipMemcpyFromSymbol(out32768, HIP_SYMBOL(vpx::stw_trace), sizeof(unsigned long long) * 8192 * 4);
-}
-#endif
-
 hipError_t launch_stw(const STWArgs& a_in, const STWOut& o, hipStream_t s) {
     STWArgs a = a_in;
-#ifdef VPX_DEV_SWITCHES
-    a.stamps = g_stw_stamps; a.stamp_block = g_stw_stamp_block;
-#else
-    a.stamps = nullptr; a.stamp_block = 0;
-#endif
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = vpx_func_attr(reinterpret_cast<const void*>(&stw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, W5_LDS);
