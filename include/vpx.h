@@ -27,6 +27,8 @@
  * vpx_phycell_correct_fwd / _bwd   PhyCell_Cell prediction-correction       vp_suite/model_blocks/phydnet.py (PhyCell_Cell.forward)
  * vpx_moment_loss_fwd / _bwd       K2M + moment regularisation loss         vp_suite/models/phydnet.py (PhyDNet.forward)
  * vpx_sigmoid_head_fwd / _bwd      sigmoid output + stack of frames         vp_suite/models/phydnet.py (encoder_fwd, forward)
+ * vpx_rconv_fwd / _bwd             Conv2d / Conv3d, padding_mode='replicate'; time3ds  vp_suite/model_blocks/conv.py:9-55, models/unet3d.py:45
+ * vpx_bn_relu_fwd / _bwd           BatchNorm + ReLU (+ MaxPool3d (1,2,2))   vp_suite/model_blocks/conv.py:22-27, models/unet3d.py:29
  * vpx_nchw_to_nhwc / nhwc_to_nchw  (layout adaptors at the boundary; the reference is NCHW throughout)
  *
  * Layouts. VPX_LAYOUT_NHWC ("channels last", the library's native layout):
@@ -479,6 +481,39 @@ int vpx_merge1x1_fwd(const float* a, const float* b, const float* w, const float
 size_t vpx_merge1x1_bwd_workspace_bytes(int N, int H, int W, int Cs, int Cp, int Co);
 int vpx_merge1x1_bwd(const float* a, const float* b, const float* w, const float* dy, float* da, float* db, float* dw, float* dbias, int N,
                      int H, int W, int Cs, int Cp, int Co, int precision, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- UNet-3D (models/unet3d.py, model_blocks/conv.py DoubleConv2d / DoubleConv3d) --------------------------------------------------- *
+ * Activations are channels-last per frame: [B][T][H][W][C]; a 2-D layer is T = 1, kt = 1. Weights keep the reference's layout
+ * [Co][Ca+Cb][kt][ks][ks]. VPX_RCONV_REPLICATE: 3x3 in space, kt in {1, 3} taps in time, frame and pixel index clamped (padding 1,
+ * padding_mode 'replicate'), no bias. VPX_RCONV_COLLAPSE: Conv3d(C -> Co, (T,1,1)) + squeeze: kt == T, one output frame [B][1][H][W][Co].
+ * The input may be two channel-concatenated sources a [..][Ca] and b [..][Cb] (Cb = 0, b = NULL: one source). fp32 FMA, every sum in a
+ * fixed order (bit-reproducible in every mode).
+ * Epilogues of the forward: PLAIN writes y (+ gamma_or_bias as a bias, nullable). EVAL writes relu((y - running_mean) / sqrt(running_var +
+ * eps) * gamma + beta). STATS writes the raw y, stats [2][Co] = (batch mean, 1 / sqrt(biased batch variance + eps)) and, when the running
+ * statistics are given, running = (1 - momentum) * running + momentum * (mean, UNBIASED variance); it needs more than one value per
+ * channel. The backward is that of the PLAIN / raw output: da, db, dw, dbias (each nullable) are OVERWRITTEN. */
+enum { VPX_RCONV_REPLICATE = 0, VPX_RCONV_COLLAPSE = 1 };
+enum { VPX_RCONV_EPI_PLAIN = 0, VPX_RCONV_EPI_EVAL = 1, VPX_RCONV_EPI_STATS = 2 };
+typedef struct vpx_rconv_desc {
+    int32_t B, T, H, W, Ca, Cb, Co, kt, mode;
+} vpx_rconv_desc;
+size_t vpx_rconv_workspace_bytes(const vpx_rconv_desc* d, int epilogue);
+int vpx_rconv_fwd(const vpx_rconv_desc* d, int epilogue, const float* a, const float* b, const float* w, const float* gamma_or_bias,
+                  const float* beta, float* running_mean, float* running_var, float eps, float momentum, float* y, float* stats,
+                  void* workspace, size_t workspace_bytes, void* stream);
+size_t vpx_rconv_bwd_workspace_bytes(const vpx_rconv_desc* d);
+int vpx_rconv_bwd(const vpx_rconv_desc* d, const float* a, const float* b, const float* w, const float* dy, float* da, float* db, float* dw,
+                  float* dbias, void* workspace, size_t workspace_bytes, void* stream);
+/* BatchNorm + ReLU on the raw output x [N][H][W][C] (N = B*T) with the statistics of the STATS epilogue: act = relu((x - mean) / std *
+ * gamma + beta); `pooled` (nullable; even H, W) also receives the 2x2 max-pool of act, [N][H/2][W/2][C], in the same pass. stats == NULL:
+ * x already is an activation and only `pooled` is written (act == NULL). The backward takes the gradients of act and of pooled (either
+ * nullable), routes the pooled one to the first maximum of its window in row-major order, reads ReLU' off act (zero at 0) and writes dx,
+ * dgamma, dbeta (the last two nullable, OVERWRITTEN): a reduction pass over per-block partials added in block order, then an apply pass. */
+int vpx_bn_relu_fwd(const float* x, const float* stats, const float* gamma, const float* beta, float* act, float* pooled, long long N, int H,
+                    int W, int C, void* stream);
+size_t vpx_bn_relu_bwd_workspace_bytes(long long N, int H, int W, int C);
+int vpx_bn_relu_bwd(const float* x, const float* act, const float* stats, const float* gamma, const float* dact, const float* dpool, float* dx,
+                    float* dgamma, float* dbeta, long long N, int H, int W, int C, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- layout adaptors: src [N,C,H,W] <-> dst [N,H,W,C] -------------------------------------------------------- */
 int vpx_nchw_to_nhwc(const float* src, float* dst, int N, int C, int H, int W, void* stream);

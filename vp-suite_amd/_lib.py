@@ -15,6 +15,8 @@ GATE_IFGO, GATE_IFOG = 0, 1
 LAYOUT_NHWC, LAYOUT_NCHW = 0, 1
 PREC_F32, PREC_BF16X3, PREC_BF16 = 0, 1, 2
 ACT_NONE, ACT_RELU = 0, 1
+RCONV_REPLICATE, RCONV_COLLAPSE = 0, 1
+RCONV_EPI_PLAIN, RCONV_EPI_EVAL, RCONV_EPI_STATS = 0, 1, 2
 FLAG_SAVE_FOR_BWD = 1
 FLAG_WEIGHTS_PACKED = 2
 FLAG_X_SPLIT = 4
@@ -50,6 +52,10 @@ class TrajGRUDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("B", "T", "Cin", "C", "H", "W", "L", "k_i2h", "precision", "flags")] + [("slope", ctypes.c_float)]
 
 
+class RConvDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "T", "H", "W", "Ca", "Cb", "Co", "kt", "mode")]
+
+
 class STLSTMShadows(ctypes.Structure):
     """vpx_stlstm_shadows: split-format copies of (x, h, m, c_new, m_new) handed in, buffers for (h_new, c_new, m_new) handed out."""
     _fields_ = [("inp", ctypes.c_void_p * 5), ("out", ctypes.c_void_p * 3), ("dg8_out", ctypes.c_void_p)]
@@ -63,6 +69,7 @@ class VpxError(RuntimeError):
 #      tests/test_host_logic.py holds every entry's argument count against the header's prototype. ----
 vp, sz, ci, ll, fl, dbl = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_double
 _clstm, _stlstm, _conv, _acst, _traj = (ctypes.POINTER(D) for D in (ConvLSTMDesc, STLSTMDesc, ConvDesc, ACSTLSTMDesc, TrajGRUDesc))
+_rconv = ctypes.POINTER(RConvDesc)
 _int_p = ctypes.POINTER(ci)
 _ws = [vp, sz, vp]           # void* workspace, size_t workspace_bytes, void* stream
 _rs_ws = [vp, sz] + _ws      # void* reserve, size_t reserve_bytes, then the workspace and the stream
@@ -164,6 +171,14 @@ SIGNATURES = {
     "vpx_merge1x1_fwd": (ci, [vp] * 5 + [ci] * 7 + _ws),
     "vpx_merge1x1_bwd_workspace_bytes": (sz, [ci] * 6),
     "vpx_merge1x1_bwd": (ci, [vp] * 8 + [ci] * 7 + _ws),
+    # UNet-3D
+    "vpx_rconv_workspace_bytes": (sz, [_rconv, ci]),
+    "vpx_rconv_fwd": (ci, [_rconv, ci] + [vp] * 7 + [fl, fl] + [vp, vp] + _ws),      # a b w gamma|bias beta rmean rvar | eps momentum | y stats
+    "vpx_rconv_bwd_workspace_bytes": (sz, [_rconv]),
+    "vpx_rconv_bwd": (ci, [_rconv] + [vp] * 8 + _ws),                                # a b w dy | da db dw dbias
+    "vpx_bn_relu_fwd": (ci, [vp] * 6 + [ll, ci, ci, ci, vp]),
+    "vpx_bn_relu_bwd_workspace_bytes": (sz, [ll, ci, ci, ci]),
+    "vpx_bn_relu_bwd": (ci, [vp] * 9 + [ll, ci, ci, ci] + _ws),
     # layout adaptors
     "vpx_nchw_to_nhwc": (ci, [vp, vp] + [ci] * 4 + [vp]),
     "vpx_nhwc_to_nchw": (ci, [vp, vp] + [ci] * 4 + [vp]),

@@ -4,6 +4,7 @@ from .ef_traj_gru import EF_TrajGRU  # noqa: F401
 from .phydnet import PhyDNet  # noqa: F401
 from .predrnn_v2 import PredRNN_V2  # noqa: F401
 from .st_phy import STPhy  # noqa: F401
+from .unet3d import UNet3D  # noqa: F401
 
 MODEL_CLASSES = {
     "convlstm-shi": EF_ConvLSTM,
@@ -11,5 +12,6 @@ MODEL_CLASSES = {
     "trajgru": EF_TrajGRU,
     "phy": PhyDNet,
     "st-phy": STPhy,
+    "unet-3d": UNet3D,
 }
 AVAILABLE_MODELS = MODEL_CLASSES.keys()
