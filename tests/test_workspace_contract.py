@@ -265,9 +265,12 @@ def test_trajgru_sequence(L):
     """vpx_trajgru_seq_fwd / _bwd over the default EF-TrajGRU blocks (ef_traj_gru.py:31-75) and small / ragged shapes, every operand mode."""
     from vp_suite_amd._lib import TrajGRUDesc
     blocks = [(16, 64, 64, 64, 13), (64, 96, 32, 32, 13), (96, 96, 16, 16, 13), (96, 96, 32, 32, 13), (96, 64, 64, 64, 13), (4, 8, 16, 16, 3), (6, 12, 9, 11, 5)]
+    # 1-wide and tiny maps (tests/test_gpu_trajgru_warp.py runs these on the GPU: here first, every launch's writes against its slot)
+    narrow = [(3, 8, 1, 7, 3), (3, 8, 6, 1, 3), (3, 8, 1, 1, 3), (3, 8, 2, 2, 3)]
     for det in (0, 1):
         L.vpx_set_deterministic(det)
-        for (Cin, C, H, W, nl), B, T, prec, save in itertools.product(blocks, (1, 2, 8), (1, 4), (0, 1, 2), (0, 1)):
+        for (Cin, C, H, W, nl), B, T, prec, save in itertools.chain(itertools.product(blocks, (1, 2, 8), (1, 4), (0, 1, 2), (0, 1)),
+                                                                    itertools.product(narrow, (2,), (2,), (0, 1), (0, 1))):
             d = TrajGRUDesc(B, T, Cin, C, H, W, nl, 3, prec, _lib.FLAG_SAVE_FOR_BWD if save else 0, 0.2)
             nb, rs = L.vpx_trajgru_workspace_bytes(ctypes.byref(d)), L.vpx_trajgru_reserve_bytes(ctypes.byref(d))
             assert nb > 0 and (rs > 0) == bool(save)

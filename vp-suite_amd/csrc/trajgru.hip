@@ -19,7 +19,9 @@ __device__ __forceinline__ void warp_coords(const WarpGeo& g, int x, int y, floa
     const float sx = ((float)x - fx) * g.kx - 0.5f;
     const float sy = ((float)y - fy) * g.ky - 0.5f;
     const float flx = floorf(sx), fly = floorf(sy);
-    x0 = (int)flx; y0 = (int)fly;
+    // clamped before the conversion (a float outside the int range has no defined int value, and flows are network outputs): at -2
+    // and at W both taps are out, as they are for everything beyond; values in [-1, W-1] are untouched
+    x0 = (int)fminf(fmaxf(flx, -2.0f), (float)g.W); y0 = (int)fminf(fmaxf(fly, -2.0f), (float)g.H);
     ax = sx - flx; ay = sy - fly;
 }
 

@@ -46,7 +46,10 @@ class _TrajGRUSeqFn(torch.autograd.Function):
         params = [t.contiguous() for t in (i2h_w, i2h_b, i2f_w, i2f_b, h2f_w, h2f_b, fl_w, fl_b, ret_w, ret_b)]
         d = _lib.TrajGRUDesc(B, T, Cin, C, H, W, int(L), int(i2h_w.shape[-1]), precision, _lib.FLAG_SAVE_FOR_BWD if need_grad else 0, float(slope))
         Lb = _lib.lib()
-        ws, ws_bytes = workspace(dev, Lb.vpx_trajgru_workspace_bytes, ctypes.byref(d), unsupported=b"must be")
+        ws_bytes = Lb.vpx_trajgru_workspace_bytes(ctypes.byref(d))
+        if ws_bytes == 0:   # the query's refusal of the descriptor (e.g. C % 4 != 0): raised here, ahead of every allocation and launch
+            raise _lib.VpxError(f"trajgru_seq: {Lb.vpx_last_error().decode(errors='replace')}")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         reserve, rs_bytes = reserve_buffer(dev, Lb.vpx_trajgru_reserve_bytes, d)
         h_init = _nhwc(h0) if h0 is not None else None
         hs = torch.empty(T, B, H, W, C, device=dev, dtype=torch.float32)   # h_1 .. h_T, time-major
