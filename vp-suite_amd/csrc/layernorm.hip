@@ -136,7 +136,13 @@ __global__ void ln_bwd_apply_kernel(const LNBwdArgs a) {
         const float xh = a.xhat[(size_t)b * n + i];
         dg += dy * xh;
         db += dy;
-        a.du[(size_t)b * n + i] = a.stats[2 * b + 1] * (dy * g - a.sums[2 * b] - xh * a.sums[2 * b + 1]);
+        float dxh;
+        {   // rounded on its own, as in ln_bwd_partial_kernel, whose mean is taken off it: contracted into an fma below, the product's
+            // rounding error stays in dx (rstd * 6e-8 |dy g|, where a one-element sample has dx = 0)
+            #pragma clang fp contract(off)
+            dxh = dy * g;
+        }
+        a.du[(size_t)b * n + i] = a.stats[2 * b + 1] * (dxh - a.sums[2 * b] - xh * a.sums[2 * b + 1]);
     }
     a.dgamma[i] = dg;
     a.dbeta[i] = db;

@@ -1189,7 +1189,7 @@ class _LayerNormCHWFn(torch.autograd.Function):
     (predrnn.py:105-135)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, need):
         require_gpu(x, "layer_norm_chw")
         xs = to_channels_last(x)
         B, C, H, Wd = xs.shape
@@ -1199,7 +1199,6 @@ class _LayerNormCHWFn(torch.autograd.Function):
         L = _lib.lib()
         ws, ws_bytes = workspace(x.device, L.vpx_layernorm_workspace_bytes, B)
         y = new_channels_last((B, C, H, Wd), x.device)
-        need = any(ctx.needs_input_grad)
         xhat = new_channels_last((B, C, H, Wd), x.device) if need else None
         stats = torch.empty(B, 2, device=x.device)
         check(L.vpx_layernorm_fwd(ptr(xs), ptr(g), ptr(b), ptr(y), ptr(xhat), ptr(stats), B, C * H * Wd, ptr(ws), ws_bytes, stream()),
@@ -1222,14 +1221,17 @@ class _LayerNormCHWFn(torch.autograd.Function):
         db = new_channels_last((1, C, H, Wd), dy.device)
         check(L.vpx_layernorm_bwd(ptr(dys), ptr(xhat), ptr(stats), ptr(g), ptr(dx), ptr(dg), ptr(db), B, H * Wd, C, ptr(ws), ws_bytes,
                                   stream()), "vpx_layernorm_bwd")
-        return dx, dg.reshape(ctx.wshape), db.reshape(ctx.wshape)
+        return dx, dg.reshape(ctx.wshape), db.reshape(ctx.wshape), None
 
 
 def layer_norm_chw(x, weight, bias, eps=1e-5):
-    """F.layer_norm(x, [C,H,W], weight, bias, eps) for a [B,C,H,W] tensor, on the library's kernels (eps is fixed at 1e-5)."""
+    """F.layer_norm(x, [C,H,W], weight, bias, eps) for a [B,C,H,W] tensor, on the library's kernels (eps is fixed at 1e-5). No model
+    calls it (the cells normalise inside their own library calls): it is the public form of vpx_layernorm_fwd/_bwd, covered by
+    tests/test_gpu_norms.py. Whether x̂ is kept for a backward is decided here, where grad mode is visible: under torch.no_grad(), or
+    when no operand requires a gradient, the forward writes no x̂ (the library's `xhat == NULL` form)."""
     if abs(float(eps) - 1e-5) > 1e-12:
         raise ValueError("layer_norm_chw: the library's LayerNorm kernels use eps = 1e-5 (nn.LayerNorm's default)")
-    return _LayerNormCHWFn.apply(x, weight, bias)
+    return _LayerNormCHWFn.apply(x, weight, bias, needs_grad(x, weight, bias))
 
 
 class _ACSTStepFn(torch.autograd.Function):
