@@ -1265,6 +1265,7 @@ class _ACSTStepFn(torch.autograd.Function):
         if need:
             ctx.save_for_backward(xs, hs, cs, ms, as_, reserve, *prm, *lnc)
             ctx.desc, ctx.rs_bytes = d, rs_bytes
+            ctx.set_materialize_grads(False)   # (an output the loss does not reach hands the backward None: NULL to the library, no zeros to read)
         return tuple(outs)
 
     @staticmethod
