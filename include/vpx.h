@@ -29,6 +29,7 @@
  * vpx_sigmoid_head_fwd / _bwd      sigmoid output + stack of frames         vp_suite/models/phydnet.py (encoder_fwd, forward)
  * vpx_rconv_fwd / _bwd             Conv2d / Conv3d, padding_mode='replicate'; time3ds  vp_suite/model_blocks/conv.py:9-55, models/unet3d.py:45
  * vpx_bn_relu_fwd / _bwd           BatchNorm + ReLU (+ MaxPool3d (1,2,2))   vp_suite/model_blocks/conv.py:22-27, models/unet3d.py:29
+ * vpx_mmnist_frames                MovingMNISTOnTheFly.__getitem__ (a batch) vp_suite/datasets/mmnist_on_the_fly.py:78-104,133-147
  * vpx_nchw_to_nhwc / nhwc_to_nchw  (layout adaptors at the boundary; the reference is NCHW throughout)
  *
  * Layouts. VPX_LAYOUT_NHWC ("channels last", the library's native layout):
@@ -514,6 +515,19 @@ int vpx_bn_relu_fwd(const float* x, const float* stats, const float* gamma, cons
 size_t vpx_bn_relu_bwd_workspace_bytes(long long N, int H, int W, int C);
 int vpx_bn_relu_bwd(const float* x, const float* act, const float* stats, const float* gamma, const float* dact, const float* dpool, float* dx,
                     float* dgamma, float* dbeta, long long N, int H, int W, int C, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Moving MNIST generated on the device (vp_suite/datasets/mmnist_on_the_fly.py) ------------------------------
+ * out [B, n_frames, C, S, S] (dense fp32, the reference's layout) from digits [n_glyphs, glyph_size, glyph_size] (bytes) and
+ * params [B, D, 5] (int32): per sample and digit (glyph index, y0, x0, vy, vx). Per axis and frame: p += v; if p + glyph_size > S then
+ * p = S - glyph_size, v = -v; else if p < 0 then p = -p, v = -v. Frame i shows the positions after i + 1 moves. A pixel is, in float64,
+ * a = sum over the digits in order of double(g) / 255.0 where the digit's box holds it; a = min(max(a, 0), 1); a = a * 255.0 / 255.0
+ * (two operations); x = float(a); then only if (lo, hi) != (0, 1): x = x * float(hi - lo), x = x + float(lo), each rounded to fp32 on
+ * its own. All C channels carry x. One launch, no workspace, no atomics: the same bits in either determinism mode.
+ * VPX_ERR_ARG: a NULL pointer, C not 1 or 3, glyph_size >= S, D < 1, a size < 1. VPX_ERR_UNSUPPORTED: D > 16, D * glyph_size^2 > 48 KiB, S > 16384, n_frames > 65536,
+ * more workgroups than one launch holds. `params` lives on the device, so the CALLER checks it: a glyph index outside [0, n_glyphs) draws
+ * nothing and a position or speed that leaves the image is drawn clipped, but neither reads or writes out of bounds. */
+int vpx_mmnist_frames(const unsigned char* digits, int n_glyphs, int glyph_size, const int* params, int B, int D, int n_frames, int C, int S,
+                      double lo, double hi, float* out, void* stream);
 
 /* ---- layout adaptors: src [N,C,H,W] <-> dst [N,H,W,C] -------------------------------------------------------- */
 int vpx_nchw_to_nhwc(const float* src, float* dst, int N, int C, int H, int W, void* stream);

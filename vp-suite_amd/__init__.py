@@ -5,5 +5,6 @@ HIP kernels for gfx950 behind the C ABI of include/vpx.h (libvpx_hip.so). No CPU
 from . import _lib  # noqa: F401
 from ._lib import VpxError, build as build_extension  # noqa: F401
 from . import ops  # noqa: F401
+from .datasets import AVAILABLE_DATASETS, DATASET_CLASSES  # noqa: F401
 
 __version__ = "0.1.0"

@@ -179,6 +179,8 @@ SIGNATURES = {
     "vpx_bn_relu_fwd": (ci, [vp] * 6 + [ll, ci, ci, ci, vp]),
     "vpx_bn_relu_bwd_workspace_bytes": (sz, [ll, ci, ci, ci]),
     "vpx_bn_relu_bwd": (ci, [vp] * 9 + [ll, ci, ci, ci] + _ws),
+    # Moving MNIST generated on the device
+    "vpx_mmnist_frames": (ci, [vp, ci, ci, vp] + [ci] * 5 + [dbl, dbl, vp, vp]),     # digits N s | params B D F C S | lo hi | out
     # layout adaptors
     "vpx_nchw_to_nhwc": (ci, [vp, vp] + [ci] * 4 + [vp]),
     "vpx_nhwc_to_nchw": (ci, [vp, vp] + [ci] * 4 + [vp]),
