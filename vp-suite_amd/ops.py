@@ -898,6 +898,14 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), ep
     for t in (param, grad, exp_avg, exp_avg_sq):
         if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == param.numel()):
             raise ValueError("adam_step: buckets must be contiguous float32 GPU tensors of equal size")
+    # The shapes and values are fine here (check() keeps ValueError for those, as the reference does): the caller broke the op's contract
+    # — a view the kernel's four-float moves cannot address, a step counter that was never advanced — which this package reports as
+    # VpxError (cf. require_gpu). Asked here so that the type does not depend on the library's one code for every bad argument; the
+    # library keeps its own check for callers of the C ABI.
+    if any(t.data_ptr() & 15 for t in (param, grad, exp_avg, exp_avg_sq)):
+        raise _lib.VpxError("adam_step: buckets must be 16-byte aligned (the kernel moves four floats at a time)")
+    if int(step) < 1:
+        raise _lib.VpxError(f"adam_step: step counts from 1 (got {step}): the bias corrections divide by 1 - beta^step")
     rc = _lib.lib().vpx_adam_step(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), float(lr),
                                   float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
                                   float(grad_scale), stream())
