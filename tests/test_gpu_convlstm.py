@@ -114,6 +114,8 @@ def test_real_block_shapes_vs_oracle(vpx, dev, Cin, Ch, H, W):
 
 
 def test_conv2d_same_vs_torch(vpx, dev):
+    """ops.conv2d_same forward, f32, three shapes. (The whole family against fp64 — gradients, bf16x3, tilings, K split, fwd_ex's
+    options, rectangular kernels, map edges: tests/test_gpu_conv_same.py.)"""
     for (Ci, Co, k, H, W) in [(128, 16, 1, 16, 16), (24, 40, 3, 9, 21), (7, 130, 5, 12, 10)]:
         x = seeded_randn((3, Ci, H, W), name_seed(f"c2d.x{Ci}{k}"))
         w = seeded_randn((Co, Ci, k, k), name_seed(f"c2d.w{Ci}{k}"), 1.0 / np.sqrt(Ci * k * k))

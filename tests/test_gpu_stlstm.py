@@ -450,7 +450,8 @@ def test_stlstm_split_shadows_change_nothing(vpx, B):
 def test_single_tile_weight_gradients_with_many_k_slices(vpx, prec):
     """Layers whose whole dW is one output tile (the decoupling adapter, a 1x1 / 3x3 head with <= 64 channels) cut their pixel sum into up to
     256 K slices (round 5: 32 left most of the chip idle). At sizes where more than 32 slices are launched: the adapter gradient against the
-    oracle's restatement of predrnn_v2.py:197-206 under autograd, conv2d's against torch."""
+    oracle's restatement of predrnn_v2.py:197-206 under autograd, conv2d's against torch.
+    (Both slice caps, ragged tiles and rectangular kernels of conv2d's gradients against fp64: tests/test_gpu_conv_same.py.)"""
     from golden_util import seeded_randn
     from oracle import torch_ref as tr
     B, Ch, H, W = 48, 64, 16, 32     # 192 work items -> 192 slices
@@ -481,7 +482,8 @@ def test_single_tile_weight_gradients_with_many_k_slices(vpx, prec):
 
 
 def test_decouple_and_conv2d_vs_golden_and_autograd(vpx):
-    """K4 (vpx_decouple_fwd/_bwd) against the reference-generated pin; K5-style conv2d fwd/bwd against torch autograd."""
+    """K4 (vpx_decouple_fwd/_bwd) against the reference-generated pin; K5-style conv2d fwd/bwd against torch autograd.
+    (conv2d's forward and gradients against fp64 over tilings, K split, kernels and map edges: tests/test_gpu_conv_same.py.)"""
     from golden_util import seeded_randn
     g = load_golden("decouple_tiny")
     B, Ch, H, W = [int(v) for v in g["shape"]]
