@@ -30,6 +30,8 @@
  * vpx_rconv_fwd / _bwd             Conv2d / Conv3d, padding_mode='replicate'; time3ds  vp_suite/model_blocks/conv.py:9-55, models/unet3d.py:45
  * vpx_bn_relu_fwd / _bwd           BatchNorm + ReLU (+ MaxPool3d (1,2,2))   vp_suite/model_blocks/conv.py:22-27, models/unet3d.py:29
  * vpx_mmnist_frames                MovingMNISTOnTheFly.__getitem__ (a batch) vp_suite/datasets/mmnist_on_the_fly.py:78-104,133-147
+ * vpx_frames_preprocess            VPDataset.preprocess (a batch of stored sequences)  vp_suite/base/base_dataset.py:233-273, datasets/mmnist.py:56-57
+ * vpx_frames_postprocess           VPDataset.postprocess                    vp_suite/base/base_dataset.py:286-297
  * vpx_nchw_to_nhwc / nhwc_to_nchw  (layout adaptors at the boundary; the reference is NCHW throughout)
  *
  * Layouts. VPX_LAYOUT_NHWC ("channels last", the library's native layout):
@@ -528,6 +530,28 @@ int vpx_bn_relu_bwd(const float* x, const float* act, const float* stats, const 
  * nothing and a position or speed that leaves the image is drawn clipped, but neither reads or writes out of bounds. */
 int vpx_mmnist_frames(const unsigned char* digits, int n_glyphs, int glyph_size, const int* params, int B, int D, int n_frames, int C, int S,
                       double lo, double hi, float* out, void* stream);
+
+/* ---- stored frames to a model-ready batch and back (vp_suite/base/base_dataset.py preprocess / postprocess) ----------------
+ * Preprocess: src [N, T', H, W, Cs] holds raw stored sequences, channels last as the files hold them (a gray [T', H, W] file is Cs = 1),
+ * of element type VPX_FRAMES_U8 / _U16 / _F32; table [B, 4] (int32, on the device) holds per output sample (sequence index, crop y0,
+ * crop x0, flip bits: bit 0 horizontal, bit 1 vertical); out [B, n_frames, C_out, oh, ow] is dense fp32. Output frame f is stored frame
+ * f * seq_step; the crop box is ch x cw at (y0, x0); C_out = Cs, or 3 from Cs = 1 (the gray repeat). One launch, no workspace, no
+ * atomics; source offsets are 64-bit. Per element, each step one correctly rounded fp32 operation, never a fused multiply-add:
+ *   v = float(raw) / 255.0f (U16: / 65535.0f, F32: v = raw); only if (lo, hi) != (0, 1): v = v * float(hi - lo), then v = v + float(lo).
+ * ch == oh and cw == ow: that is the output, bit-exact against numpy. Otherwise a bilinear resize with align_corners = False and no
+ * antialiasing follows, per axis in fp32: s = float(in) / float(out); src = max(s * (d + 0.5f) - 0.5f, 0); i0 = int(src);
+ * i1 = min(i0 + 1, in - 1); l = src - i0; r = v0 * (1 - l) + v1 * l, horizontally first, then vertically (held to a bound, not to bits).
+ * Flips act on the output index after the resize.
+ * VPX_ERR_ARG: a NULL pointer, an unknown element type, a size < 1, (n_frames - 1) * seq_step >= T', a crop box larger than the frame,
+ * C_out neither Cs nor 3 from 1, hi == lo. VPX_ERR_UNSUPPORTED: Cs > 4, a side beyond 32768, more workgroups than one launch holds.
+ * `table` lives on the device, so the CALLER checks it: a row whose sequence index is outside [0, N) or whose box leaves the frame
+ * yields zeros and reads nothing out of bounds.
+ * Postprocess: x [N, C, h, w] fp32 (only read) -> out [N, h, w, C] bytes; in fp32 v = ((x - float(lo)) / float(hi - lo)) * 255.0f,
+ * clamped to [0, 255], truncated toward zero; NaN gives 0. VPX_ERR_ARG: a NULL pointer, a size < 1, hi == lo. */
+enum { VPX_FRAMES_U8 = 0, VPX_FRAMES_U16 = 1, VPX_FRAMES_F32 = 2 };
+int vpx_frames_preprocess(const void* src, int dtype, long long N, int Tp, int H, int W, int Cs, const int* table, int B, int n_frames,
+                          int seq_step, int ch, int cw, int oh, int ow, int C_out, double lo, double hi, float* out, void* stream);
+int vpx_frames_postprocess(const float* x, long long N, int C, int h, int w, double lo, double hi, unsigned char* out, void* stream);
 
 /* ---- layout adaptors: src [N,C,H,W] <-> dst [N,H,W,C] -------------------------------------------------------- */
 int vpx_nchw_to_nhwc(const float* src, float* dst, int N, int C, int H, int W, void* stream);

@@ -21,6 +21,7 @@ FLAG_SAVE_FOR_BWD = 1
 FLAG_WEIGHTS_PACKED = 2
 FLAG_X_SPLIT = 4
 FLAG_OUT_SPLIT = 8
+FRAMES_U8, FRAMES_U16, FRAMES_F32 = 0, 1, 2
 
 OPT_CELL2 = 1
 OPT_CELL3 = 2
@@ -181,6 +182,9 @@ SIGNATURES = {
     "vpx_bn_relu_bwd": (ci, [vp] * 9 + [ll, ci, ci, ci] + _ws),
     # Moving MNIST generated on the device
     "vpx_mmnist_frames": (ci, [vp, ci, ci, vp] + [ci] * 5 + [dbl, dbl, vp, vp]),     # digits N s | params B D F C S | lo hi | out
+    # stored frames to a model-ready batch and back
+    "vpx_frames_preprocess": (ci, [vp, ci, ll] + [ci] * 4 + [vp] + [ci] * 8 + [dbl, dbl, vp, vp]),   # src dtype N T' H W Cs | table B F step ch cw oh ow C_out | lo hi | out
+    "vpx_frames_postprocess": (ci, [vp, ll] + [ci] * 3 + [dbl, dbl, vp, vp]),                       # x N C h w | lo hi | out
     # layout adaptors
     "vpx_nchw_to_nhwc": (ci, [vp, vp] + [ci] * 4 + [vp]),
     "vpx_nhwc_to_nchw": (ci, [vp, vp] + [ci] * 4 + [vp]),

@@ -1,0 +1,278 @@
+// Stored frames to a model-ready batch and back (vp_suite/base/base_dataset.py:233-273 preprocess, :293-297 postprocess; the gray
+// repeat of vp_suite/datasets/mmnist.py:56), one launch each.
+//   vpx_frames_preprocess    src [N][T'][H][W][Cs] (uint8 / uint16 / float32, channels last as the files hold them) and a device table
+//                            int32 [B][4] = (sequence, crop y0, crop x0, flip bits) -> out float32 [B][F][C_out][oh][ow]
+//   vpx_frames_postprocess   x float32 [N][C][h][w] -> out uint8 [N][h][w][C]; x is only read
+// Streaming kernels: a thread owns four neighbouring output pixels of one row in every channel, so a channel plane receives one 16-byte
+// store per thread where the rows allow it, and on the path without resize every source element is read exactly once (for Cs = 3 the
+// thread's four pixels are 12 contiguous bytes). The resize path gathers four taps per pixel and channel from the same family.
+//
+// Pixel contract of the preprocess (tests/frames_ref.py restates it), every step ONE correctly rounded float32 operation:
+//   v = float(raw) / 255.0f (uint16: / 65535.0f; float32 passes through);
+//   only if (lo, hi) != (0, 1):  v = v * float(hi - lo), then v = v + float(lo)   (the difference formed in double by the caller's language);
+//   without resize (crop size == output size) that is the output: bit-exact against numpy and the reference.
+//   With resize (bilinear, align_corners = False, no antialiasing — ATen's upsample_bilinear2d), per axis, in float32:
+//     s = float(in) / float(out);  src = max(s * (d + 0.5f) - 0.5f, 0);  i0 = int(src);  i1 = min(i0 + 1, in - 1);  l = src - i0;
+//   the taps are the scaled values v; horizontally first, r = v0 * (1 - l) + v1 * l, then the same vertically. Held to a bound, not bits.
+//   Flips act on the OUTPUT index, after the resize: out[y][x] = r[oh - 1 - y if bit 1 else y][ow - 1 - x if bit 0 else x].
+// Postprocess, in float32: v = ((x - float(lo)) / float(hi - lo)) * 255.0f, clamped to [0, 255], truncated toward zero; NaN gives 0.
+#include <hip/hip_runtime.h>
+#include "vpx_internal.h"
+#include "vpx_host.h"
+
+// Every operation of this file is rounded on its own (see mmnist.hip): no a * b + c becomes a fused multiply-add.
+#pragma clang fp contract(off)
+
+namespace vpx {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int FR_THREADS = 256;
+constexpr int FR_MAX_CS = 4;          // source channels a thread keeps in registers (gray, gray + alpha, RGB, RGBA)
+constexpr int FR_MAX_SIDE = 32768;    // frame, crop and output sides: coordinates and their float32 images stay exact
+
+struct FramesArgs {
+    const void* src;                   // [N][Tp][H][W][Cs]
+    const int* table;                  // [B][4] = (sequence, crop y0, crop x0, flip bits)
+    float* out;                        // [B][F][C_out][oh][ow]
+    long long N;
+    long long items;                   // B * F * oh * Q: one thread each
+    int Tp, H, W, Cs, B, F, step, ch, cw, oh, ow, Cout;
+    int Q;                             // groups of four pixels per output row (the last one partial if ow % 4)
+    int vec;                           // 1: ow % 4 == 0 and `out` 16-byte aligned — every group is one 16-byte store per plane
+    int scaled;                        // 1: (lo, hi) != (0, 1)
+    float scale, lo;                   // float(hi - lo), float(lo)
+    float sy, sx;                      // float(ch) / float(oh), float(cw) / float(ow)
+};
+
+template <typename T> __device__ __forceinline__ float fr_unit(T raw);
+template <> __device__ __forceinline__ float fr_unit<unsigned char>(unsigned char raw) { return (float)raw / 255.0f; }
+template <> __device__ __forceinline__ float fr_unit<unsigned short>(unsigned short raw) { return (float)raw / 65535.0f; }
+template <> __device__ __forceinline__ float fr_unit<float>(float raw) { return raw; }
+
+template <typename T> __device__ __forceinline__ float fr_value(const FramesArgs& a, T raw) {
+    float v = fr_unit<T>(raw);
+    if (a.scaled) {
+        v = v * a.scale;
+        v = v + a.lo;
+    }
+    return v;
+}
+
+// ATen's source coordinate of destination index d (area_pixel_compute_source_index, align_corners = False): the first tap, the second
+// one and the weight of the second. i0 is clamped to the box for memory safety only: src < in holds for every d < out.
+__device__ __forceinline__ void fr_coord(float s, int d, int in, int& i0, int& i1, float& l) {
+    float src = s * ((float)d + 0.5f) - 0.5f;
+    src = src < 0.0f ? 0.0f : src;
+    i0 = (int)src;
+    i0 = i0 > in - 1 ? in - 1 : i0;
+    i1 = i0 + 1 > in - 1 ? in - 1 : i0 + 1;
+    l = src - (float)i0;
+}
+
+// thread = (sample b, frame f, output row y, group of four output pixels). RESIZE = 0: crop size == output size.
+template <typename T, int RESIZE>
+__global__ __launch_bounds__(FR_THREADS) void frames_preprocess_kernel(FramesArgs a) {
+    const long long item = (long long)blockIdx.x * FR_THREADS + threadIdx.x;
+    if (item >= a.items) return;
+    const int q = (int)(item % a.Q);
+    long long r = item / a.Q;
+    const int y = (int)(r % a.oh);
+    r /= a.oh;
+    const int f = (int)(r % a.F);
+    const int b = (int)(r / a.F);
+    const int x0 = q << 2;
+    const int* row = a.table + (size_t)b * 4;
+    const long long seq = row[0];
+    const int cy = row[1], cx = row[2], flip = row[3];
+    // a row the caller did not check (the table lives on the device) reads nothing out of bounds: it yields zeros
+    const bool valid = seq >= 0 && seq < a.N && cy >= 0 && cx >= 0 && (long long)cy + a.ch <= a.H && (long long)cx + a.cw <= a.W;
+    const T* frame = (const T*)a.src + ((size_t)(valid ? seq : 0) * a.Tp + (size_t)f * a.step) * ((size_t)a.H * a.W * a.Cs);   // 64-bit offsets throughout
+    const int yr = (flip & 2) ? a.oh - 1 - y : y;
+    float v[FR_MAX_CS][4];
+#pragma unroll
+    for (int c = 0; c < FR_MAX_CS; ++c)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[c][k] = 0.0f;
+    if (valid) {
+        if (!RESIZE) {
+            const T* line = frame + (size_t)(cy + yr) * a.W * a.Cs;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int x = x0 + k;
+                if (x >= a.ow) break;
+                const int xr = (flip & 1) ? a.ow - 1 - x : x;
+                const T* px = line + (size_t)(cx + xr) * a.Cs;
+#pragma unroll
+                for (int c = 0; c < FR_MAX_CS; ++c)
+                    if (c < a.Cs) v[c][k] = fr_value<T>(a, px[c]);
+            }
+        } else {
+            int iy0, iy1;
+            float ly;
+            fr_coord(a.sy, yr, a.ch, iy0, iy1, ly);
+            const T* top = frame + (size_t)(cy + iy0) * a.W * a.Cs;
+            const T* bot = frame + (size_t)(cy + iy1) * a.W * a.Cs;
+            const float wy = 1.0f - ly;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int x = x0 + k;
+                if (x >= a.ow) break;
+                const int xr = (flip & 1) ? a.ow - 1 - x : x;
+                int ix0, ix1;
+                float lx;
+                fr_coord(a.sx, xr, a.cw, ix0, ix1, lx);
+                const float wx = 1.0f - lx;
+                const size_t o0 = (size_t)(cx + ix0) * a.Cs, o1 = (size_t)(cx + ix1) * a.Cs;
+#pragma unroll
+                for (int c = 0; c < FR_MAX_CS; ++c) {
+                    if (c < a.Cs) {
+                        const float t = fr_value<T>(a, top[o0 + c]) * wx + fr_value<T>(a, top[o1 + c]) * lx;
+                        const float u = fr_value<T>(a, bot[o0 + c]) * wx + fr_value<T>(a, bot[o1 + c]) * lx;
+                        v[c][k] = t * wy + u * ly;
+                    }
+                }
+            }
+        }
+    }
+    const size_t plane = (size_t)a.oh * a.ow;
+    float* dst = a.out + ((size_t)b * a.F + f) * a.Cout * plane + (size_t)y * a.ow + x0;
+#pragma unroll
+    for (int c = 0; c < FR_MAX_CS; ++c) {
+        if (c >= a.Cout) break;
+        const int cs = a.Cs == 1 ? 0 : c;                              // the gray repeat: every plane carries channel 0
+        f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = cs == 0 ? v[0][k] : (cs == 1 ? v[1][k] : (cs == 2 ? v[2][k] : v[3][k]));
+        if (a.vec) *reinterpret_cast<f32x4*>(dst) = o;
+        else
+            for (int k = 0; k < 4 && x0 + k < a.ow; ++k) dst[k] = o[k];
+        dst += plane;
+    }
+}
+
+struct PostArgs {
+    const float* x;                    // [N][C][h][w]
+    unsigned char* out;                // [N][h][w][C]
+    long long items;                   // N * h * Q
+    int C, h, w, Q;
+    int vec;                           // 1: w % 4 == 0, C <= 4 and `out` 4-byte aligned — a thread's 4 * C bytes leave as C 32-bit stores
+    float scale, lo;                   // float(hi - lo), float(lo)
+};
+
+__device__ __forceinline__ unsigned fr_byte(const PostArgs& a, float x) {
+    float v = x - a.lo;
+    v = v / a.scale;
+    v = v * 255.0f;
+    if (!(v == v)) return 0u;                                          // NaN: 0 by definition (the reference's conversion is undefined)
+    v = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);
+    return (unsigned)v;                                                // truncation toward zero
+}
+
+// thread = (image n, row y, group of four pixels): reads its four pixels of every plane, writes their 4 * C interleaved bytes
+__global__ __launch_bounds__(FR_THREADS) void frames_postprocess_kernel(PostArgs a) {
+    const long long item = (long long)blockIdx.x * FR_THREADS + threadIdx.x;
+    if (item >= a.items) return;
+    const int q = (int)(item % a.Q);
+    const long long r = item / a.Q;
+    const int y = (int)(r % a.h);
+    const long long n = r / a.h;
+    const int x0 = q << 2;
+    const size_t plane = (size_t)a.h * a.w;
+    const float* src = a.x + (size_t)n * a.C * plane + (size_t)y * a.w + x0;
+    unsigned char* dst = a.out + ((size_t)n * plane + (size_t)y * a.w + x0) * a.C;
+    if (a.vec) {
+        unsigned words[4] = {0u, 0u, 0u, 0u};                          // 4 * C <= 16 bytes, little endian: byte j = pixel j / C, channel j % C
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (c >= a.C) break;
+            const f32x4 p = *reinterpret_cast<const f32x4*>(src + (size_t)c * plane);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = k * a.C + c;
+                const unsigned byte = fr_byte(a, p[k]) << ((j & 3) * 8);
+#pragma unroll
+                for (int wd = 0; wd < 4; ++wd)
+                    if ((j >> 2) == wd) words[wd] |= byte;
+            }
+        }
+#pragma unroll
+        for (int wd = 0; wd < 4; ++wd)
+            if (wd < a.C) reinterpret_cast<unsigned*>(dst)[wd] = words[wd];
+    } else {
+        for (int k = 0; k < 4 && x0 + k < a.w; ++k)
+            for (int c = 0; c < a.C; ++c) dst[k * a.C + c] = (unsigned char)fr_byte(a, src[(size_t)c * plane + k]);
+    }
+}
+
+template <typename T>
+static void launch_preprocess(const FramesArgs& a, int resize, unsigned blocks, hipStream_t stream) {
+    if (resize) VPX_LAUNCH((frames_preprocess_kernel<T, 1>), dim3(blocks), dim3(FR_THREADS), 0, stream, a);
+    else VPX_LAUNCH((frames_preprocess_kernel<T, 0>), dim3(blocks), dim3(FR_THREADS), 0, stream, a);
+}
+
+}  // namespace vpx
+
+using namespace vpx;
+
+extern "C" {
+
+int vpx_frames_preprocess(const void* src, int dtype, long long N, int Tp, int H, int W, int Cs, const int* table, int B, int n_frames,
+                          int seq_step, int ch, int cw, int oh, int ow, int C_out, double lo, double hi, float* out, void* stream) {
+    const char* who = "vpx_frames_preprocess";
+    if (!src || !table || !out) { set_error("%s: NULL tensor argument", who); return VPX_ERR_ARG; }
+    if (dtype != VPX_FRAMES_U8 && dtype != VPX_FRAMES_U16 && dtype != VPX_FRAMES_F32) { set_error("%s: unknown element type %d (uint8, uint16 and float32 are stored)", who, dtype); return VPX_ERR_ARG; }
+    if (N < 1 || Tp < 1 || H < 1 || W < 1 || Cs < 1) { set_error("%s: every source size must be >= 1 (got N=%lld T'=%d H=%d W=%d Cs=%d)", who, N, Tp, H, W, Cs); return VPX_ERR_ARG; }
+    if (B < 1 || n_frames < 1 || seq_step < 1) { set_error("%s: B, n_frames and seq_step must be >= 1 (got %d, %d, %d)", who, B, n_frames, seq_step); return VPX_ERR_ARG; }
+    if (ch < 1 || cw < 1 || oh < 1 || ow < 1) { set_error("%s: crop and output sizes must be >= 1 (got crop %dx%d, output %dx%d)", who, ch, cw, oh, ow); return VPX_ERR_ARG; }
+    if ((long long)(n_frames - 1) * seq_step >= Tp) { set_error("%s: frame %d at step %d lies past the %d stored frames", who, n_frames - 1, seq_step, Tp); return VPX_ERR_ARG; }
+    if (ch > H || cw > W) { set_error("%s: the %dx%d crop box lies outside the %dx%d frame (there is no padding)", who, ch, cw, H, W); return VPX_ERR_ARG; }
+    if (C_out != Cs && !(Cs == 1 && C_out == 3)) { set_error("%s: %d output channels from %d stored ones (equal, or 3 from 1)", who, C_out, Cs); return VPX_ERR_ARG; }
+    if (hi == lo) { set_error("%s: empty value range [%g, %g]", who, lo, hi); return VPX_ERR_ARG; }
+    if (Cs > FR_MAX_CS) { set_error("%s: %d stored channels exceed the kernel's %d", who, Cs, FR_MAX_CS); return VPX_ERR_UNSUPPORTED; }
+    if (H > FR_MAX_SIDE || W > FR_MAX_SIDE || oh > FR_MAX_SIDE || ow > FR_MAX_SIDE) { set_error("%s: a side beyond %d (frame %dx%d, output %dx%d)", who, FR_MAX_SIDE, H, W, oh, ow); return VPX_ERR_UNSUPPORTED; }
+    const int Q = (ow + 3) / 4;
+    const double items_d = (double)B * n_frames * oh * Q;
+    if (items_d / FR_THREADS + 1.0 > 2147483647.0) { set_error("%s: %d samples of %d %dx%d frames exceed one launch", who, B, n_frames, oh, ow); return VPX_ERR_UNSUPPORTED; }
+    FramesArgs a;
+    a.src = src; a.table = table; a.out = out;
+    a.N = N; a.Tp = Tp; a.H = H; a.W = W; a.Cs = Cs; a.B = B; a.F = n_frames; a.step = seq_step;
+    a.ch = ch; a.cw = cw; a.oh = oh; a.ow = ow; a.Cout = C_out; a.Q = Q;
+    a.items = (long long)B * n_frames * oh * Q;
+    a.vec = (ow % 4 == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
+    a.scaled = (lo != 0.0 || hi != 1.0) ? 1 : 0;
+    a.scale = (float)(hi - lo);
+    a.lo = (float)lo;
+    a.sy = (float)ch / (float)oh;
+    a.sx = (float)cw / (float)ow;
+    const int resize = (ch != oh || cw != ow) ? 1 : 0;
+    const unsigned blocks = (unsigned)((a.items + FR_THREADS - 1) / FR_THREADS);
+    if (dtype == VPX_FRAMES_U8) launch_preprocess<unsigned char>(a, resize, blocks, (hipStream_t)stream);
+    else if (dtype == VPX_FRAMES_U16) launch_preprocess<unsigned short>(a, resize, blocks, (hipStream_t)stream);
+    else launch_preprocess<float>(a, resize, blocks, (hipStream_t)stream);
+    VPX_CHECK_HIP(vpx_hip_last_error());
+    return VPX_OK;
+}
+
+int vpx_frames_postprocess(const float* x, long long N, int C, int h, int w, double lo, double hi, unsigned char* out, void* stream) {
+    const char* who = "vpx_frames_postprocess";
+    if (!x || !out) { set_error("%s: NULL tensor argument", who); return VPX_ERR_ARG; }
+    if (N < 1 || C < 1 || h < 1 || w < 1) { set_error("%s: every size must be >= 1 (got N=%lld C=%d h=%d w=%d)", who, N, C, h, w); return VPX_ERR_ARG; }
+    if (hi == lo) { set_error("%s: empty value range [%g, %g]", who, lo, hi); return VPX_ERR_ARG; }
+    if (h > FR_MAX_SIDE || w > FR_MAX_SIDE) { set_error("%s: a side beyond %d (%dx%d)", who, FR_MAX_SIDE, h, w); return VPX_ERR_UNSUPPORTED; }
+    const int Q = (w + 3) / 4;
+    const double items_d = (double)N * h * Q;
+    if (items_d / FR_THREADS + 1.0 > 2147483647.0) { set_error("%s: %lld images of %dx%d exceed one launch", who, N, h, w); return VPX_ERR_UNSUPPORTED; }
+    PostArgs a;
+    a.x = x; a.out = out; a.C = C; a.h = h; a.w = w; a.Q = Q;
+    a.items = N * h * Q;
+    a.vec = (w % 4 == 0 && C <= 4 && ((uintptr_t)out & 3) == 0 && ((uintptr_t)x & 15) == 0) ? 1 : 0;
+    a.scale = (float)(hi - lo);
+    a.lo = (float)lo;
+    const unsigned blocks = (unsigned)((a.items + FR_THREADS - 1) / FR_THREADS);
+    VPX_LAUNCH(frames_postprocess_kernel, dim3(blocks), dim3(FR_THREADS), 0, (hipStream_t)stream, a);
+    VPX_CHECK_HIP(vpx_hip_last_error());
+    return VPX_OK;
+}
+
+}  // extern "C"

@@ -1,8 +1,33 @@
 """Dataset registry with the reference's keys (vp_suite/datasets/__init__.py) for the datasets this build generates or reads."""
-from .base import VPDataset  # noqa: F401
+from .base import StoredSubset, StoredVPDataset, VPDataset  # noqa: F401
+from .mmnist import MovingMNISTDataset  # noqa: F401
 from .mmnist_on_the_fly import MovingMNISTOnTheFly, generate_frames, procedural_digits, read_idx_images  # noqa: F401
 
-DATASET_CLASSES = {
+
+class DatasetRegistry(dict):
+    """The registry in two tiers. LISTED datasets — what iteration, len() and AVAILABLE_DATASETS show — are the ones that produce their
+    own frames and so run without a prepared directory. STORED datasets read files a user has to bring (data_dir=); they exist only
+    then, so they are not listed, but they are registered: DATASET_CLASSES[key], `key in DATASET_CLASSES` and .get(key) find them."""
+
+    def __init__(self, listed, stored):
+        super().__init__(listed)
+        self.stored = dict(stored)
+
+    def __missing__(self, key):
+        return self.stored[key]
+
+    def __contains__(self, key):
+        return super().__contains__(key) or key in self.stored
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+
+GENERATED_DATASET_CLASSES = {
     "MMF": MovingMNISTOnTheFly,
 }
+STORED_DATASET_CLASSES = {
+    "MM": MovingMNISTDataset,
+}
+DATASET_CLASSES = DatasetRegistry(GENERATED_DATASET_CLASSES, STORED_DATASET_CLASSES)
 AVAILABLE_DATASETS = DATASET_CLASSES.keys()

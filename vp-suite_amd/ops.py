@@ -1303,3 +1303,81 @@ class _ACSTStepFn(torch.autograd.Function):
 def acstlstm_step(x, h, c, m, a, params, ln=(), precision="f32", forget_bias=1.0):
     """One step of the action-conditional ST-LSTM cell; `params`: the 12 convolution tensors, `ln`: () or the 10 LayerNorm tensors."""
     return _ACSTStepFn.apply(x, h, c, m, a, PRECISIONS[precision], float(forget_bias), *params, *ln)
+
+
+# ---- stored frames to a model-ready batch and back (csrc/frames.hip) ----
+FRAME_DTYPES = {torch.uint8: _lib.FRAMES_U8, torch.uint16: _lib.FRAMES_U16, torch.float32: _lib.FRAMES_F32}
+
+
+def check_frames_table(table, n_seqs, frame_hw, crop_hw):
+    """The table a preprocess launch is handed, checked where it can be read (the host): int32 [B, 4] rows (sequence index, crop y0,
+    crop x0, flip bits) with the index inside [0, n_seqs), the box inside the frame (there is no padding) and flip bits in 0 ... 3."""
+    import numpy as np
+    t = table.cpu().numpy() if torch.is_tensor(table) else np.asarray(table)
+    if t.ndim != 2 or t.shape[1] != 4 or t.shape[0] < 1 or not np.issubdtype(t.dtype, np.integer):
+        raise ValueError(f"table must be an integer table [B, 4] (got {t.dtype} {t.shape})")
+    (H, W), (ch, cw) = frame_hw, crop_hw
+    if t[:, 0].min() < 0 or t[:, 0].max() >= n_seqs:
+        raise ValueError(f"sequence index outside [0, {n_seqs})")
+    if t[:, 1].min() < 0 or t[:, 2].min() < 0 or t[:, 1].max() + ch > H or t[:, 2].max() + cw > W:
+        raise ValueError(f"a {ch}x{cw} crop box leaves the {H}x{W} frame (there is no padding)")
+    if t[:, 3].min() < 0 or t[:, 3].max() > 3:
+        raise ValueError("flip bits outside 0 ... 3 (bit 0 horizontal, bit 1 vertical)")
+    return np.ascontiguousarray(t, dtype=np.int32)
+
+
+def frames_preprocess(src, table, n_frames, seq_step=1, crop_size=None, out_size=None, c_out=None, value_range=(0.0, 1.0), out=None):
+    """float32 [B, n_frames, C_out, oh, ow] from raw stored sequences `src` [N, T', H, W(, Cs)] (a uint8 / uint16 / float32 GPU tensor,
+    channels last) in ONE launch: scale, crop, bilinear resize (align_corners=False, no antialiasing), flip — see include/vpx.h.
+    `table`: host rows [B, 4] = (sequence index, crop y0, crop x0, flip bits), checked here, copied to the device once. crop_size defaults
+    to the frame, out_size to the crop, c_out to Cs. `out`: an optional destination of that shape (any 4-byte alignment)."""
+    if not (torch.is_tensor(src) and src.is_cuda):
+        raise _lib.VpxError("frames_preprocess: src must be a GPU tensor; frames are converted by a HIP kernel, there is no CPU fallback")
+    if src.dtype not in FRAME_DTYPES:
+        raise ValueError(f"frames_preprocess: stored element type {src.dtype} is unknown (uint8, uint16 and float32 are)")
+    if src.ndim not in (4, 5):
+        raise ValueError(f"frames_preprocess: src must be [N, T', H, W] or [N, T', H, W, C] (got {tuple(src.shape)})")
+    src = src.contiguous()
+    N, Tp, H, W = (int(s) for s in src.shape[:4])
+    Cs = int(src.shape[4]) if src.ndim == 5 else 1
+    ch, cw = (H, W) if crop_size is None else (int(s) for s in crop_size)
+    oh, ow = (ch, cw) if out_size is None else (int(s) for s in out_size)
+    c_out = Cs if c_out is None else int(c_out)
+    if min(ch, cw, oh, ow, n_frames, seq_step) < 1:
+        raise ValueError(f"frames_preprocess: every size must be >= 1 (crop {ch}x{cw}, output {oh}x{ow}, {n_frames} frames, step {seq_step})")
+    host = check_frames_table(table, N, (H, W), (ch, cw))
+    B = host.shape[0]
+    lo, hi = float(value_range[0]), float(value_range[1])
+    shape = (B, int(n_frames), c_out, oh, ow)
+    if out is None:
+        if min(shape) < 1:
+            raise ValueError(f"frames_preprocess: empty output {shape}")
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+        raise ValueError(f"frames_preprocess: out must be a contiguous float32 GPU tensor {shape}")
+    dev_table = torch.from_numpy(host).to(src.device)
+    with torch.cuda.device(src.device):
+        check(_lib.lib().vpx_frames_preprocess(ptr(src), FRAME_DTYPES[src.dtype], N, Tp, H, W, Cs, ptr(dev_table), B, int(n_frames), int(seq_step),
+                                               ch, cw, oh, ow, c_out, lo, hi, ptr(out), stream()), "vpx_frames_preprocess")
+    return out
+
+
+def frames_postprocess(x, lo=0.0, hi=1.0):
+    """uint8 [..., h, w, C] on the GPU from float32 [..., C, h, w] in one launch: ((x - lo) / (hi - lo)) * 255 in float32, clamped to
+    [0, 255], truncated; NaN gives 0. `x` is left as it is (the reference subtracts in place)."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise _lib.VpxError("frames_postprocess: x must be a GPU tensor; there is no CPU fallback")
+    if x.dtype != torch.float32:
+        raise ValueError(f"frames_postprocess: expected float32, got {x.dtype}")
+    if x.ndim < 3:
+        raise ValueError("expected at least three dimensions for input image")
+    xc = x.contiguous()
+    C, h, w = (int(s) for s in x.shape[-3:])
+    lead = tuple(int(s) for s in x.shape[:-3])
+    N = 1
+    for s in lead:
+        N *= s
+    out = torch.empty(lead + (h, w, C), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        check(_lib.lib().vpx_frames_postprocess(ptr(xc), N, C, h, w, float(lo), float(hi), ptr(out), stream()), "vpx_frames_postprocess")
+    return out
