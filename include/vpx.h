@@ -32,6 +32,7 @@
  * vpx_mmnist_frames                MovingMNISTOnTheFly.__getitem__ (a batch) vp_suite/datasets/mmnist_on_the_fly.py:78-104,133-147
  * vpx_frames_preprocess            VPDataset.preprocess (a batch of stored sequences)  vp_suite/base/base_dataset.py:233-273, datasets/mmnist.py:56-57
  * vpx_frames_postprocess           VPDataset.postprocess                    vp_suite/base/base_dataset.py:286-297
+ * vpx_frames_adapt                 ScaleToModel / ScaleToTest + TF.Resize   vp_suite/utils/compatibility.py:31-50, utils/models.py:7-64
  * vpx_nchw_to_nhwc / nhwc_to_nchw  (layout adaptors at the boundary; the reference is NCHW throughout)
  *
  * Layouts. VPX_LAYOUT_NHWC ("channels last", the library's native layout):
@@ -552,6 +553,17 @@ enum { VPX_FRAMES_U8 = 0, VPX_FRAMES_U16 = 1, VPX_FRAMES_F32 = 2 };
 int vpx_frames_preprocess(const void* src, int dtype, long long N, int Tp, int H, int W, int Cs, const int* table, int B, int n_frames,
                           int seq_step, int ch, int cw, int oh, int ow, int C_out, double lo, double hi, float* out, void* stream);
 int vpx_frames_postprocess(const float* x, long long N, int C, int h, int w, double lo, double hi, unsigned char* out, void* stream);
+
+/* ---- frame adapter between a model and a test set (vp_suite/utils/compatibility.py: ScaleToModel / ScaleToTest, then TF.Resize) ----
+ * x [N, C, H, W] planar fp32 (only read) -> out [N, C, oh, ow], one launch, no workspace, no atomics, 64-bit element offsets. Forward
+ * only. Per element, each step one correctly rounded fp32 operation, never a fused multiply-add, scale first and resize second as in the
+ * reference: only if (src_lo, src_hi) != (dst_lo, dst_hi): v = v - float(src_lo); v = v / float(src_hi - src_lo);
+ * v = v * float(dst_hi - dst_lo); v = v + float(dst_lo) (the differences formed in double). Only if (oh, ow) != (H, W): the bilinear resize
+ * of vpx_frames_preprocess over the scaled taps (align_corners = False, no antialiasing, the same fp32 source coordinates, horizontally
+ * first; held to a bound, not to bits). Equal sizes: the affine map alone; equal ranges: no arithmetic on the taps; both: a copy.
+ * VPX_ERR_ARG: a NULL pointer, a size < 1, src_hi == src_lo. VPX_ERR_UNSUPPORTED: a side beyond 32768, more workgroups than one launch holds. */
+int vpx_frames_adapt(const float* x, long long N, int C, int H, int W, int oh, int ow, double src_lo, double src_hi, double dst_lo,
+                     double dst_hi, float* out, void* stream);
 
 /* ---- layout adaptors: src [N,C,H,W] <-> dst [N,H,W,C] -------------------------------------------------------- */
 int vpx_nchw_to_nhwc(const float* src, float* dst, int N, int C, int H, int W, void* stream);

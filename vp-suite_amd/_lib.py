@@ -185,6 +185,8 @@ SIGNATURES = {
     # stored frames to a model-ready batch and back
     "vpx_frames_preprocess": (ci, [vp, ci, ll] + [ci] * 4 + [vp] + [ci] * 8 + [dbl, dbl, vp, vp]),   # src dtype N T' H W Cs | table B F step ch cw oh ow C_out | lo hi | out
     "vpx_frames_postprocess": (ci, [vp, ll] + [ci] * 3 + [dbl, dbl, vp, vp]),                       # x N C h w | lo hi | out
+    # frame adapter between a model and a test set
+    "vpx_frames_adapt": (ci, [vp, ll] + [ci] * 5 + [dbl] * 4 + [vp, vp]),                            # x N C H W oh ow | src lo hi, dst lo hi | out
     # layout adaptors
     "vpx_nchw_to_nhwc": (ci, [vp, vp] + [ci] * 4 + [vp]),
     "vpx_nhwc_to_nchw": (ci, [vp, vp] + [ci] * 4 + [vp]),

@@ -23,6 +23,8 @@
 // Every operation of this file is rounded on its own (see mmnist.hip): no a * b + c becomes a fused multiply-add.
 #pragma clang fp contract(off)
 
+#include "frames_coord.h"
+
 namespace vpx {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -59,16 +61,8 @@ template <typename T> __device__ __forceinline__ float fr_value(const FramesArgs
     return v;
 }
 
-// ATen's source coordinate of destination index d (area_pixel_compute_source_index, align_corners = False): the first tap, the second
-// one and the weight of the second. i0 is clamped to the box for memory safety only: src < in holds for every d < out.
-__device__ __forceinline__ void fr_coord(float s, int d, int in, int& i0, int& i1, float& l) {
-    float src = s * ((float)d + 0.5f) - 0.5f;
-    src = src < 0.0f ? 0.0f : src;
-    i0 = (int)src;
-    i0 = i0 > in - 1 ? in - 1 : i0;
-    i1 = i0 + 1 > in - 1 ? in - 1 : i0 + 1;
-    l = src - (float)i0;
-}
+// fr_coord(): ATen's source coordinate of destination index d (area_pixel_compute_source_index, align_corners = False) — frames_coord.h,
+// shared with adapt.hip.
 
 // thread = (sample b, frame f, output row y, group of four output pixels). RESIZE = 0: crop size == output size.
 template <typename T, int RESIZE>

@@ -76,6 +76,18 @@ class VPDataset(Dataset):
     def reset_rng(self):
         pass
 
+    @classmethod
+    def get_train_val(cls, **dataset_kwargs):
+        """(training, validation) datasets of a class with a split of its own for each (base_dataset.py:333-358). A class with
+        ["train", "test"] only splits its training samples by index: StoredVPDataset does."""
+        if cls.VALID_SPLITS != ["train", "val", "test"]:
+            raise NotImplementedError(f"dataset class '{cls.__name__}' has no 'val' split and no samples that could be split by index")
+        return cls("train", **dataset_kwargs), cls("val", **dataset_kwargs)
+
+    @classmethod
+    def get_test(cls, **dataset_kwargs):
+        return cls("test", **dataset_kwargs)
+
     def __len__(self) -> int:
         raise NotImplementedError
 

@@ -227,6 +227,7 @@ class MovingMNISTOnTheFly(VPDataset):
         data = self.batch(1)
         return {"frames": data["frames"][0], "actions": data["actions"][0], "origin": data["origin"][0]}
 
-    def loader(self, batch_size, drop_last=True):
-        """An iterable of len(self) // batch_size batches: what VPModel.train_iter / eval_iter take as `loader`."""
+    def loader(self, batch_size, drop_last=True, shuffle=False, seed=None):
+        """An iterable of len(self) // batch_size batches: what VPModel.train_iter / eval_iter take as `loader`. `shuffle` and `seed` are
+        taken for the stored datasets' signature and change nothing: every sample is drawn when it is asked for, whatever its index."""
         return _BatchLoader(self, batch_size, drop_last)

@@ -1,4 +1,5 @@
-"""Model registry with the reference's keys (vp_suite/models/__init__.py:14-26) for the models on the hot path."""
+"""Model registry with the reference's keys (vp_suite/models/__init__.py:14-26) for the models on the hot path, and the copy baseline."""
+from .copy_last_frame import CopyLastFrame  # noqa: F401
 from .ef_conv_lstm import EF_ConvLSTM, Encoder_Forecaster  # noqa: F401
 from .ef_traj_gru import EF_TrajGRU  # noqa: F401
 from .phydnet import PhyDNet  # noqa: F401
@@ -13,5 +14,6 @@ MODEL_CLASSES = {
     "phy": PhyDNet,
     "st-phy": STPhy,
     "unet-3d": UNet3D,
+    "copy": CopyLastFrame,
 }
 AVAILABLE_MODELS = MODEL_CLASSES.keys()

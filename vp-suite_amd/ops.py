@@ -1381,3 +1381,36 @@ def frames_postprocess(x, lo=0.0, hi=1.0):
     with torch.cuda.device(x.device):
         check(_lib.lib().vpx_frames_postprocess(ptr(xc), N, C, h, w, float(lo), float(hi), ptr(out), stream()), "vpx_frames_postprocess")
     return out
+
+
+# ---- frame adapter between a model and a test set (csrc/adapt.hip) ----
+def frames_adapt(x, out_hw=None, src_range=(0.0, 1.0), dst_range=(0.0, 1.0)):
+    """float32 [..., C, oh, ow] on the GPU from planar float32 frames x [N, C, H, W] or [b, t, C, H, W] in ONE launch: every value mapped
+    from src_range to dst_range (((v - src_lo) / (src_hi - src_lo)) * (dst_hi - dst_lo) + dst_lo; skipped for equal ranges), then resized
+    bilinearly (align_corners=False, no antialiasing; skipped for out_hw None or (H, W)) — the reference's ScaleToModel / ScaleToTest and
+    TF.Resize in their order, see include/vpx.h. Forward only: an input that needs a gradient is refused. A non-contiguous `x` (the halves
+    VPModel.unpack_data splits) is read through one dense copy; `x` itself is left as it is."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise _lib.VpxError("frames_adapt: x must be a GPU tensor; frames are adapted by a HIP kernel, there is no CPU fallback")
+    if x.dtype != torch.float32:
+        raise ValueError(f"frames_adapt: expected float32, got {x.dtype}")
+    if x.ndim not in (4, 5):
+        raise ValueError(f"frames_adapt: x must be [N, C, H, W] or [b, t, C, H, W] (got {tuple(x.shape)})")
+    if needs_grad(x):
+        raise _lib.VpxError("frames_adapt: the adapter is forward only (testing runs under no_grad); x requires a gradient")
+    if len(src_range) != 2 or len(dst_range) != 2:
+        raise ValueError("frames_adapt: src_range and dst_range are (lo, hi) pairs")
+    lead = tuple(int(s) for s in x.shape[:-3])
+    C, H, W = (int(s) for s in x.shape[-3:])
+    oh, ow = (H, W) if out_hw is None else (int(s) for s in out_hw)
+    N = 1
+    for s in lead:
+        N *= s
+    if min(N, C, H, W) < 1:
+        raise ValueError(f"frames_adapt: empty input {tuple(x.shape)}")
+    xc = x.detach().contiguous()
+    out = torch.empty(lead + (C, max(oh, 0), max(ow, 0)), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        check(_lib.lib().vpx_frames_adapt(ptr(xc), N, C, H, W, oh, ow, float(src_range[0]), float(src_range[1]), float(dst_range[0]),
+                                          float(dst_range[1]), ptr(out), stream()), "vpx_frames_adapt")
+    return out
