@@ -21,6 +21,8 @@
  * vpx_conv2d_ex_fwd / _bwd         Conv2d / ConvTranspose2d + LeakyReLU     vp_suite/models/precipitation_nowcasting/ef_blocks.py:15-49
  * vpx_mse_loss                     MSE measure + loss provider              vp_suite/base/base_measure.py:55-57, measure/loss_provider.py:48-51
  * vpx_adam_step                    torch.optim.Adam(model.parameters(), lr)  vp_suite/vpsuite.py:353, base/base_model.py:174-176
+ * vpx_grad_stats                   total_norm of torch.nn.utils.clip_grad_norm_, max |g|, non-finite count   (new: the reference never clips)
+ * vpx_adam_step_clipped            clip_grad_norm_ / clip_grad_value_ + Adam step, optional skip of a non-finite step   (new)
  * vpx_pixel_measures_fwd / _bwd    MSE, L1, SmoothL1, PSNR per frame         vp_suite/measure/image_wise.py:19-71
  * vpx_ssim_fwd / _bwd              SSIM per frame (piqa defaults)           vp_suite/measure/image_wise.py:99-117
  * vpx_groupnorm_fwd / _bwd         GroupNorm + LeakyReLU (DCGAN layers)     vp_suite/model_blocks/conv.py, model_blocks/phydnet.py
@@ -259,6 +261,40 @@ int vpx_mse_loss(const float* pred, const float* target, long long n_elements, l
  * forms them in Python floats, and rounded to fp32 once. */
 int vpx_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, double lr,
                   double beta1, double beta2, double eps, double weight_decay, int step, double grad_scale, void* stream);
+/* Gradient clipping and a non-finite step guard, fused into the update (no host round trip, no further pass over the gradient).
+ * vpx_grad_stats: one streaming pass over grad[n] (16-byte loads where grad is 16-byte aligned, scalar otherwise) into a
+ * device-resident double stats[4] (8-byte aligned):
+ *   stats[0] = || grad_scale * grad ||_2: the squares are summed exactly in double (a float x float product is exact there),
+ *              grad_scale is applied in double to the sum, then one sqrt. Not finite (inf or NaN) when an element is not.
+ *   stats[1] = max | grad_scale * grad | over the FINITE elements (0 if there are none)
+ *   stats[2] = number of non-finite elements (NaN, +-inf)
+ *   stats[3]   not touched here: the number of steps vpx_adam_step_clipped skipped (the caller zeroes it once).
+ * Double per-thread accumulators, per-block partials in the workspace, a one-wave final kernel with a fixed summation order and no
+ * floating-point atomics: bit-reproducible run to run whatever vpx_set_deterministic says.
+ * VPX_ERR_ARG: grad or stats NULL, n < 1, stats not 8-byte aligned, grad_scale negative or NaN. VPX_ERR_WORKSPACE: workspace NULL or
+ * smaller than vpx_grad_stats_workspace_bytes().
+ *
+ * vpx_adam_step_clipped: vpx_adam_step with, in this order,
+ *   1. the per-launch factor s = (float)(grad_scale * c), c = max_norm > 0 ? min(1, max_norm / (stats[0] + 1e-6)) : 1 formed in
+ *      double from the device value (torch.nn.utils.clip_grad_norm_'s coefficient; a NaN norm gives NaN, as there):
+ *      g = grad[k] * s is the one float multiply vpx_adam_step spends on grad_scale;
+ *   2. clip_value > 0: g = min(max(g, -clip_value), clip_value), NaN stays NaN (torch.clamp; clip_grad_value_);
+ *   then weight decay and the update as in vpx_adam_step, from the same host-prepared scalars.
+ *   3. skip_nonfinite != 0 and stats[2] > 0: nothing is written to param / exp_avg / exp_avg_sq (bit-unchanged) and stats[3] is
+ *      incremented by one. A SKIPPED STEP STILL ADVANCES THE STEP COUNT: the bias corrections are host scalars of `step`, and
+ *      holding the count back would take a host sync or a device-side pow; the caller passes step + 1 to the next call either way.
+ * With c = 1 (max_norm = 0, or the norm below it), clip_value = 0 and nothing skipped, s == (float)grad_scale and param / exp_avg /
+ * exp_avg_sq come out bit-identical to vpx_adam_step's. stats is read on the device when the kernel runs (enqueue vpx_grad_stats
+ * on the same stream before it); stats == NULL is allowed with max_norm == 0 and skip_nonfinite == 0 (value clipping alone needs
+ * no reduction).
+ * VPX_ERR_ARG: what vpx_adam_step refuses (a NULL bucket, n < 1, step < 1, buckets not 16-byte aligned), stats not 8-byte aligned,
+ * grad_scale / max_norm / clip_value negative or NaN, stats == NULL with max_norm > 0 or skip_nonfinite. */
+size_t vpx_grad_stats_workspace_bytes(void);
+int vpx_grad_stats(const float* grad, long long n, double grad_scale, double* stats, void* workspace, size_t workspace_bytes,
+                   void* stream);
+int vpx_adam_step_clipped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, double lr,
+                          double beta1, double beta2, double eps, double weight_decay, int step, double grad_scale,
+                          const double* stats, double max_norm, double clip_value, int skip_nonfinite, void* stream);
 
 /* ---- image-wise measures (vp_suite/measure/image_wise.py): per-frame tables that serve every reduction ------------
  * All of them: double partial sums, fixed-order final reduction, no atomics (bit-reproducible in either determinism mode).

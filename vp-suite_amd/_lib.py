@@ -110,6 +110,9 @@ SIGNATURES = {
     "vpx_mse_loss_workspace_bytes": (sz, []),
     "vpx_mse_loss": (ci, [vp, vp, ll, ll, fl, vp, vp] + _ws),
     "vpx_adam_step": (ci, [vp] * 4 + [ll] + [dbl] * 5 + [ci, dbl, vp]),
+    "vpx_grad_stats_workspace_bytes": (sz, []),
+    "vpx_grad_stats": (ci, [vp, ll, dbl, vp] + _ws),
+    "vpx_adam_step_clipped": (ci, [vp] * 4 + [ll] + [dbl] * 5 + [ci, dbl, vp, dbl, dbl, ci, vp]),   # ... step grad_scale | stats max_norm clip_value skip_nonfinite
     # image-wise measures
     "vpx_pixel_measures_workspace_bytes": (sz, [ll, ll]),
     "vpx_pixel_measures_fwd": (ci, [vp, vp, ll, ll, vp] + _ws),

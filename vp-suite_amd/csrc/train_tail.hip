@@ -5,6 +5,11 @@
 //                     scaled and summed by PredictionLossProvider.get_losses (measure/loss_provider.py:48-51)
 //   vpx_adam_step     torch.optim.Adam(params, lr) as constructed in vp_suite/vpsuite.py:353 (betas 0.9/0.999, eps 1e-8,
 //                     no weight decay, no amsgrad), called once per iteration at base_model.py:176
+//   vpx_grad_stats / vpx_adam_step_clipped   no counterpart in the reference: norm / max / non-finite count of the flat gradient in
+//                     one deterministic pass, and the same Adam update reading that result on the device — norm clipping
+//                     (torch.nn.utils.clip_grad_norm_'s coefficient), value clipping (clip_grad_value_) and an optional skip of a
+//                     non-finite step, without a host round trip or another pass over the gradient. A skipped step still
+//                     advances the caller's step count: the bias corrections are host scalars of that count.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "vpx_internal.h"
@@ -62,6 +67,66 @@ __global__ void mse_final_kernel(const double* __restrict__ partial, int nblocks
     if (threadIdx.x == 0) *loss = (float)(acc * mult);
 }
 
+constexpr int GS_THREADS = 256;
+constexpr int GS_MAX_BLOCKS = 1024;
+
+static __device__ __forceinline__ bool gs_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
+// partial[3 b .. 3 b + 2] = sum g^2 (a float x float product is exact in double), max |g| over the finite elements, number of
+// non-finite elements — of block b's share of grad. A non-finite element goes into the sum as it is: the sum is then inf or NaN.
+__global__ __launch_bounds__(GS_THREADS) void grad_stats_partial_kernel(const float* __restrict__ grad, long long n,
+                                                                        double* __restrict__ partial) {
+    __shared__ double red[3][GS_THREADS / 64];
+    double acc = 0.0, bad = 0.0;
+    float mx = 0.0f;
+    const long long stride = (long long)gridDim.x * GS_THREADS * 4;
+    const bool vec = ((uintptr_t)grad & 15) == 0;
+    for (long long e = ((long long)blockIdx.x * GS_THREADS + threadIdx.x) * 4; e < n; e += stride) {
+        if (vec && e + 3 < n) {
+            const f32x4 g = *reinterpret_cast<const f32x4*>(grad + e);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                acc += (double)g[k] * g[k];
+                if (gs_finite(g[k])) mx = fmaxf(mx, fabsf(g[k])); else bad += 1.0;
+            }
+        } else {
+            for (long long k = e; k < n && k < e + 4; ++k) {
+                const float g = grad[k];
+                acc += (double)g * g;
+                if (gs_finite(g)) mx = fmaxf(mx, fabsf(g)); else bad += 1.0;
+            }
+        }
+    }
+    double dmx = (double)mx;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        acc += __shfl_down(acc, off, 64);
+        bad += __shfl_down(bad, off, 64);
+        dmx = fmax(dmx, __shfl_down(dmx, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = acc; red[1][threadIdx.x >> 6] = dmx; red[2][threadIdx.x >> 6] = bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0, m = 0.0, c = 0.0;
+        for (int w = 0; w < GS_THREADS / 64; ++w) { s += red[0][w]; m = fmax(m, red[1][w]); c += red[2][w]; }
+        partial[3 * blockIdx.x] = s; partial[3 * blockIdx.x + 1] = m; partial[3 * blockIdx.x + 2] = c;
+    }
+}
+
+// stats[0] = sqrt(grad_scale^2 * sum), stats[1] = grad_scale * max, stats[2] = count: one wave, fixed order (deterministic).
+// stats[3] (the skipped-step count of adam_kernel) is left alone.
+__global__ void grad_stats_final_kernel(const double* __restrict__ partial, int nblocks, double grad_scale, double* __restrict__ stats) {
+    double acc = 0.0, mx = 0.0, bad = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += 64) { acc += partial[3 * i]; mx = fmax(mx, partial[3 * i + 1]); bad += partial[3 * i + 2]; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        acc += __shfl_down(acc, off, 64);
+        bad += __shfl_down(bad, off, 64);
+        mx = fmax(mx, __shfl_down(mx, off, 64));
+    }
+    if (threadIdx.x == 0) { stats[0] = sqrt(acc * (grad_scale * grad_scale)); stats[1] = grad_scale * mx; stats[2] = bad; }
+}
+
 struct AdamArgs {
     float* p; const float* g; float* m; float* v;
     long long n;
@@ -71,11 +136,42 @@ struct AdamArgs {
     float weight_decay, grad_scale;
 };
 
+// What vpx_adam_step_clipped adds to the update; read on the device, so the caller never waits for the statistics.
+struct ClipArgs {
+    double* stats;            // vpx_grad_stats's result (nullable: value clipping alone needs none); [3] counts the skipped steps
+    double grad_scale, max_norm;
+    float clip_value;
+    int skip_nonfinite;
+};
+
 // torch.optim.Adam single-tensor update (torch/optim/adam.py _single_tensor_adam, amsgrad = False, maximize = False):
 //   g += wd * p ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
-__global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
+// MODE 0: vpx_adam_step, g = grad * grad_scale. MODE 1: the factor is s = (float)(grad_scale * c) with clip_grad_norm_'s coefficient
+// c = min(1, max_norm / (stats[0] + 1e-6)) formed in double from the device value (1 without max_norm), and a step whose gradient
+// holds a non-finite element (stats[2] > 0) is left out on request: every thread returns before its first store and one thread
+// counts the step in stats[3]. MODE 2: additionally g is clamped to +-clip_value (NaN stays NaN, as torch.clamp) before the weight
+// decay. With c = 1 and nothing skipped, s == (float)grad_scale and MODE 1 runs MODE 0's arithmetic on MODE 0's values: same bits.
+template <int MODE>
+__global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a, const ClipArgs c) {
     const long long stride = (long long)gridDim.x * 256 * 4;
     const float step_size = a.step_size;
+    float gs = a.grad_scale;
+    if constexpr (MODE != 0) {
+        if (c.stats) {
+            if (c.skip_nonfinite && c.stats[2] > 0.0) {
+                if (blockIdx.x == 0 && threadIdx.x == 0) c.stats[3] = c.stats[3] + 1.0;
+                return;
+            }
+            if (c.max_norm > 0.0) {
+                const double r = c.max_norm / (c.stats[0] + 1e-6);
+                gs = (float)(c.grad_scale * (r > 1.0 ? 1.0 : r));   // (a NaN norm gives a NaN factor, as torch.clamp(max=1) does)
+            }
+        }
+    }
+    auto clamp = [&](float g) -> float {
+        if constexpr (MODE == 2) return g > c.clip_value ? c.clip_value : (g < -c.clip_value ? -c.clip_value : g);
+        else return g;
+    };
     for (long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; e < a.n; e += stride) {
         if (e + 3 < a.n) {  // the buckets are 256-byte aligned allocations: vector path
             f32x4 p = *reinterpret_cast<const f32x4*>(a.p + e);
@@ -84,7 +180,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
             f32x4 v = *reinterpret_cast<const f32x4*>(a.v + e);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                float g = g4[k] * a.grad_scale;
+                float g = clamp(g4[k] * gs);
                 if (a.weight_decay != 0.0f) g += a.weight_decay * p[k];
                 m[k] = a.beta1 * m[k] + a.omb1 * g;
                 v[k] = a.beta2 * v[k] + a.omb2 * g * g;
@@ -96,7 +192,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
             *reinterpret_cast<f32x4*>(a.v + e) = v;
         } else {
             for (long long k = e; k < a.n; ++k) {
-                float g = a.g[k] * a.grad_scale;
+                float g = clamp(a.g[k] * gs);
                 if (a.weight_decay != 0.0f) g += a.weight_decay * a.p[k];
                 const float m = a.beta1 * a.m[k] + a.omb1 * g;
                 const float v = a.beta2 * a.v[k] + a.omb2 * g * g;
@@ -105,6 +201,25 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
             }
         }
     }
+}
+
+// the arguments both Adam entry points refuse, and the scalars of the update as torch forms them
+static int adam_prepare(const char* who, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, double lr,
+                        double beta1, double beta2, double eps, double weight_decay, int step, double grad_scale, AdamArgs& a) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || n < 1 || step < 1) { set_error("%s: bad argument", who); return VPX_ERR_ARG; }
+    if ((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) != 0) {
+        set_error("%s: buckets must be 16-byte aligned", who);
+        return VPX_ERR_ARG;
+    }
+    a = AdamArgs{param, grad, exp_avg, exp_avg_sq, n, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
+                 (float)(lr / (1.0 - pow(beta1, step))), (float)sqrt(1.0 - pow(beta2, step)), (float)eps,
+                 (float)weight_decay, (float)grad_scale};
+    return VPX_OK;
+}
+
+static unsigned adam_blocks(long long n) {
+    long long blocks = (n + 1023) / 1024;
+    return (unsigned)(blocks > 2048 ? 2048 : blocks);
 }
 
 }  // namespace vpx
@@ -134,17 +249,49 @@ int vpx_mse_loss(const float* pred, const float* target, long long n_elements, l
 
 int vpx_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, double lr, double beta1,
                   double beta2, double eps, double weight_decay, int step, double grad_scale, void* stream_) {
-    if (!param || !grad || !exp_avg || !exp_avg_sq || n < 1 || step < 1) { set_error("vpx_adam_step: bad argument"); return VPX_ERR_ARG; }
-    if ((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) != 0) {
-        set_error("vpx_adam_step: buckets must be 16-byte aligned");
+    AdamArgs a;
+    if (int rc = adam_prepare("vpx_adam_step", param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, a)) return rc;
+    VPX_LAUNCH(adam_kernel<0>, dim3(adam_blocks(n)), dim3(256), 0, (hipStream_t)stream_, a, ClipArgs{});
+    VPX_CHECK_HIP(vpx_hip_last_error());
+    return VPX_OK;
+}
+
+size_t vpx_grad_stats_workspace_bytes(void) { return GS_MAX_BLOCKS * 3 * sizeof(double) + 256; }
+
+int vpx_grad_stats(const float* grad, long long n, double grad_scale, double* stats, void* workspace, size_t workspace_bytes,
+                   void* stream_) {
+    if (!grad || !stats || n < 1) { set_error("vpx_grad_stats: bad argument"); return VPX_ERR_ARG; }
+    if (((uintptr_t)grad & 3) != 0 || ((uintptr_t)stats & 7) != 0) { set_error("vpx_grad_stats: grad must be 4-byte, stats 8-byte aligned"); return VPX_ERR_ARG; }
+    if (!(grad_scale >= 0.0)) { set_error("vpx_grad_stats: grad_scale must not be negative or NaN"); return VPX_ERR_ARG; }
+    if (!workspace || workspace_bytes < vpx_grad_stats_workspace_bytes()) { set_error("vpx_grad_stats: workspace too small"); return VPX_ERR_WORKSPACE; }
+    hipStream_t stream = (hipStream_t)stream_;
+    long long blocks = (n + GS_THREADS * 4 - 1) / (GS_THREADS * 4);
+    if (blocks > GS_MAX_BLOCKS) blocks = GS_MAX_BLOCKS;
+    Carver ws(workspace, workspace_bytes);
+    double* partial = reinterpret_cast<double*>(ws.take((size_t)blocks * 3 * 2));
+    VPX_CHECK_CARVE(ws, "vpx_grad_stats");
+    VPX_LAUNCH(grad_stats_partial_kernel, dim3((unsigned)blocks), dim3(GS_THREADS), 0, stream, grad, n, partial);
+    VPX_CHECK_HIP(vpx_hip_last_error());
+    VPX_LAUNCH(grad_stats_final_kernel, dim3(1), dim3(64), 0, stream, partial, (int)blocks, grad_scale, stats);
+    VPX_CHECK_HIP(vpx_hip_last_error());
+    return VPX_OK;
+}
+
+int vpx_adam_step_clipped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, double lr, double beta1,
+                          double beta2, double eps, double weight_decay, int step, double grad_scale, const double* stats,
+                          double max_norm, double clip_value, int skip_nonfinite, void* stream_) {
+    AdamArgs a;
+    if (int rc = adam_prepare("vpx_adam_step_clipped", param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, a)) return rc;
+    if (!(grad_scale >= 0.0) || !(max_norm >= 0.0) || !(clip_value >= 0.0)) {
+        set_error("vpx_adam_step_clipped: grad_scale, max_norm and clip_value must not be negative or NaN");
         return VPX_ERR_ARG;
     }
-    AdamArgs a{param, grad, exp_avg, exp_avg_sq, n, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
-               (float)(lr / (1.0 - pow(beta1, step))), (float)sqrt(1.0 - pow(beta2, step)), (float)eps,
-               (float)weight_decay, (float)grad_scale};
-    long long blocks = (n + 1023) / 1024;
-    if (blocks > 2048) blocks = 2048;
-    VPX_LAUNCH(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, a);
+    if (!stats && (max_norm > 0.0 || skip_nonfinite)) { set_error("vpx_adam_step_clipped: max_norm and skip_nonfinite need stats"); return VPX_ERR_ARG; }
+    if (((uintptr_t)stats & 7) != 0) { set_error("vpx_adam_step_clipped: stats must be 8-byte aligned"); return VPX_ERR_ARG; }
+    // (stats is const for the caller's reading of it: the one element the update writes is its own skipped-step count)
+    const ClipArgs c{const_cast<double*>(stats), grad_scale, max_norm, (float)clip_value, skip_nonfinite};
+    if (clip_value > 0.0) VPX_LAUNCH(adam_kernel<2>, dim3(adam_blocks(n)), dim3(256), 0, (hipStream_t)stream_, a, c);
+    else VPX_LAUNCH(adam_kernel<1>, dim3(adam_blocks(n)), dim3(256), 0, (hipStream_t)stream_, a, c);
     VPX_CHECK_HIP(vpx_hip_last_error());
     return VPX_OK;
 }

@@ -912,6 +912,61 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), ep
     check(rc, "vpx_adam_step")
 
 
+_grad_stats_ws = {}   # (device, stream) -> the partial sums' workspace: a few KB, kept so that a training step allocates nothing
+
+
+def grad_stats(grad, grad_scale=1.0, out=None):
+    """Norm, largest magnitude and non-finite count of `grad_scale * grad` in one deterministic pass: a float64 GPU tensor of 4
+    elements (include/vpx.h: vpx_grad_stats), `out` if given (element 3, adam_step_clipped's skipped-step count, is left alone; a new
+    tensor starts it at 0). Nothing is read back: looking at the result is the caller's host sync."""
+    require_gpu(grad, "grad_stats")
+    if not (grad.is_contiguous() and grad.numel() > 0):
+        raise ValueError("grad_stats: the gradient must be a contiguous, non-empty float32 GPU tensor")
+    if not float(grad_scale) >= 0.0:
+        raise ValueError(f"grad_stats: grad_scale must not be negative or NaN (got {grad_scale})")
+    if out is None:
+        out = torch.zeros(4, dtype=torch.float64, device=grad.device)
+    elif not (out.is_cuda and out.device == grad.device and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == 4):
+        raise ValueError("grad_stats: out must be a contiguous float64 tensor of 4 elements on the gradient's device")
+    L = _lib.lib()
+    s = stream()
+    ws = _grad_stats_ws.get((grad.device, s.value))
+    if ws is None:
+        ws = _grad_stats_ws[(grad.device, s.value)] = workspace(grad.device, L.vpx_grad_stats_workspace_bytes)
+    check(L.vpx_grad_stats(ptr(grad), grad.numel(), float(grad_scale), ptr(out), ptr(ws[0]), ws[1], s), "vpx_grad_stats")
+    return out
+
+
+def adam_step_clipped(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0,
+                      stats=None, max_norm=0.0, clip_value=0.0, skip_nonfinite=False):
+    """adam_step with the gradient clipped on the way in: by norm (clip_grad_norm_'s coefficient from `stats`, grad_stats's result of
+    the SAME grad_scale, read on the device), then by value (clip_grad_value_), and the whole step left out when `skip_nonfinite` and
+    the statistics count a non-finite element (stats[3] counts those steps; the caller's step count advances all the same).
+    `stats` may be None for value clipping alone. include/vpx.h: vpx_adam_step_clipped."""
+    require_gpu(param, "adam_step_clipped")
+    for t in (param, grad, exp_avg, exp_avg_sq):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == param.numel()):
+            raise ValueError("adam_step_clipped: buckets must be contiguous float32 GPU tensors of equal size")
+    for name, val in (("max_norm", max_norm), ("clip_value", clip_value), ("grad_scale", grad_scale)):
+        if not float(val) >= 0.0:
+            raise ValueError(f"adam_step_clipped: {name} must not be negative or NaN (got {val})")
+    if stats is None:
+        if float(max_norm) > 0.0 or skip_nonfinite:
+            raise ValueError("adam_step_clipped: max_norm and skip_nonfinite read the gradient statistics: pass stats=grad_stats(grad, grad_scale)")
+    elif not (stats.is_cuda and stats.device == param.device and stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() == 4):
+        raise ValueError("adam_step_clipped: stats must be grad_stats's float64 tensor of 4 elements on the buckets' device")
+    # (the contract breaches adam_step reports as VpxError, for the same reason)
+    if any(t.data_ptr() & 15 for t in (param, grad, exp_avg, exp_avg_sq)):
+        raise _lib.VpxError("adam_step_clipped: buckets must be 16-byte aligned (the kernel moves four floats at a time)")
+    if int(step) < 1:
+        raise _lib.VpxError(f"adam_step_clipped: step counts from 1 (got {step}): the bias corrections divide by 1 - beta^step")
+    rc = _lib.lib().vpx_adam_step_clipped(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), float(lr),
+                                          float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
+                                          float(grad_scale), ptr(stats), float(max_norm), float(clip_value), int(bool(skip_nonfinite)),
+                                          stream())
+    check(rc, "vpx_adam_step_clipped")
+
+
 class STWorkspace:
     """Per-cell workspace that lets consecutive steps of one forward pass skip the weight repack
     (VPX_FLAG_WEIGHTS_PACKED): valid while the weights' version counters and the problem shape are unchanged."""

@@ -60,18 +60,44 @@ class FlatAdam(torch.optim.Optimizer):
     of the gradient bucket and takes a zero-gradient Adam step (its moments decay, remaining momentum still moves it, weight
     decay applies). All parameters of the shipped models receive a gradient in every iteration, so the trajectories coincide
     (tests/test_gpu_models.py pins them against torch.optim.Adam); a model with a branch that is unused in some iterations
-    should freeze that branch (requires_grad = False) or use torch.optim.Adam."""
+    should freeze that branch (requires_grad = False) or use torch.optim.Adam.
 
-    def __init__(self, params, flat_param, flat_grad, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    Gradient clipping and a non-finite step guard, fused into the update (all off by default: `step()` is then the plain kernel):
+      max_grad_norm    torch.nn.utils.clip_grad_norm_(params, max_grad_norm) on the (grad_scale-d) gradient of the whole bucket
+      clip_grad_value  torch.nn.utils.clip_grad_value_(params, clip_grad_value), applied after the norm clipping
+      skip_nonfinite   a step whose gradient holds a NaN or an inf changes neither parameters nor moments
+    One reduction kernel leaves norm, largest magnitude, non-finite count and the number of skipped steps in `grad_stats` (float64[4]
+    on the device, valid after a step) and the update reads them there: `step()` never waits for the device. Reading `grad_stats`, or
+    the conveniences `last_grad_norm` / `skipped_steps`, is the caller's sync. A SKIPPED STEP STILL ADVANCES THE STEP COUNT (`steps`,
+    hence the bias corrections of the following updates): holding it back would take a host sync per step. The three settings live
+    in `param_groups[0]`, so they travel with `state_dict()` as `lr` does; the skipped-step count travels in its "flat_adam" entry."""
+
+    def __init__(self, params, flat_param, flat_grad, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 max_grad_norm=None, clip_grad_value=None, skip_nonfinite=False):
         params = list(params)
         if params and isinstance(params[0], dict):
             raise ValueError("FlatAdam: a single parameter group only (the flat buckets carry one set of hyper-parameters)")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        for name, val in (("max_grad_norm", max_grad_norm), ("clip_grad_value", clip_grad_value)):
+            if val is not None and not float(val) >= 0.0:
+                raise ValueError(f"FlatAdam: {name} must not be negative or NaN (got {val}); None or 0 switches it off")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                                      clip_grad_value=clip_grad_value, skip_nonfinite=bool(skip_nonfinite)))
         self.flat_param, self.flat_grad = flat_param, flat_grad
         self.exp_avg = torch.zeros_like(flat_param)
         self.exp_avg_sq = torch.zeros_like(flat_param)
         self.steps = 0
         self.grad_scale = 1.0
+        self.grad_stats = torch.zeros(4, dtype=torch.float64, device=flat_param.device)   # norm, max |g|, non-finite count, skipped steps
+
+    @property
+    def last_grad_norm(self) -> float:
+        """Norm of the last step's (grad_scale-d, unclipped) gradient; waits for the device. Needs max_grad_norm or skip_nonfinite."""
+        return float(self.grad_stats[0].item())
+
+    @property
+    def skipped_steps(self) -> int:
+        """Number of steps the non-finite guard left out; waits for the device."""
+        return int(self.grad_stats[3].item())
 
     @classmethod
     def from_module(cls, module, lr=1e-3, **kw):
@@ -126,8 +152,19 @@ class FlatAdam(torch.optim.Optimizer):
         self._relink()
         g = self.param_groups[0]
         self.steps += 1
-        ops.adam_step(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.steps, g["lr"], g["betas"],
-                      g["eps"], g["weight_decay"], self.grad_scale)
+        max_norm, clip_value, skip = float(g.get("max_grad_norm") or 0.0), float(g.get("clip_grad_value") or 0.0), bool(g.get("skip_nonfinite"))
+        if not (max_norm >= 0.0 and clip_value >= 0.0):   # (a scheduler or the user may have written to the group since)
+            raise ValueError(f"FlatAdam: max_grad_norm / clip_grad_value must not be negative or NaN (got {max_norm}, {clip_value})")
+        if max_norm == 0.0 and clip_value == 0.0 and not skip:
+            ops.adam_step(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.steps, g["lr"], g["betas"],
+                          g["eps"], g["weight_decay"], self.grad_scale)
+        else:
+            stats = None
+            if max_norm > 0.0 or skip:   # (value clipping alone needs no reduction)
+                stats = ops.grad_stats(self.flat_grad, self.grad_scale, out=self.grad_stats)
+            ops.adam_step_clipped(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.steps, g["lr"], g["betas"],
+                                  g["eps"], g["weight_decay"], self.grad_scale, stats=stats, max_norm=max_norm,
+                                  clip_value=clip_value, skip_nonfinite=skip)
         # the kernel wrote the parameters behind autograd's back: bump their version counters so that everything keyed
         # on (data_ptr, _version) — packed-weight and layout caches of the cells — sees new values
         torch.autograd.graph.increment_version(g["params"])
@@ -138,17 +175,22 @@ class FlatAdam(torch.optim.Optimizer):
 
     def state_dict(self):
         sd = super().state_dict()
-        sd["flat_adam"] = {"exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(), "steps": self.steps}
+        sd["flat_adam"] = {"exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(), "steps": self.steps,
+                           "skipped_steps": self.skipped_steps}
         return sd
 
     def load_state_dict(self, state_dict):
         state_dict = dict(state_dict)
         fa = state_dict.pop("flat_adam", None)
+        clip = {k: self.param_groups[0][k] for k in ("max_grad_norm", "clip_grad_value", "skip_nonfinite")}
         super().load_state_dict(state_dict)
+        for k, val in clip.items():   # a state dict from before these settings existed: this optimizer keeps its own
+            self.param_groups[0].setdefault(k, val)
         if fa is not None:
             self.exp_avg.copy_(fa["exp_avg"])
             self.exp_avg_sq.copy_(fa["exp_avg_sq"])
             self.steps = int(fa["steps"])
+            self.grad_stats[3] = float(fa.get("skipped_steps", 0))
 
 
 class DataParallelTrainer:
@@ -157,7 +199,7 @@ class DataParallelTrainer:
 
     def __init__(self, model, lr: float = 1e-4, world_size: int = None, losses_and_scales=None, device=None,
                  force_collectives: bool = False, all_reduce=None, broadcast=None, bucketed: bool = True,
-                 seed: int = None, rank: int = None):
+                 seed: int = None, rank: int = None, max_grad_norm=None, clip_grad_value=None, skip_nonfinite: bool = False):
         self.model = model
         self.rank = rank if rank is not None else (dist.get_rank() if dist.is_initialized() else 0)
         self.world = world_size if world_size is not None else (dist.get_world_size() if dist.is_initialized() else 1)
@@ -205,7 +247,17 @@ class DataParallelTrainer:
             _link_views(self.params, self.flat_param, "data")
         if self.collectives:
             self.broadcast_parameters()
-        self.optimizer = FlatAdam(self.params, self.flat_param, self.flat_grad, lr=lr) if self.fused \
+        # Clipping acts on the AVERAGED gradient (after reduce_gradients, grad_scale = 1 / world), identical on every rank: fused into
+        # FlatAdam's update on the GPU, torch.nn.utils.clip_grad_* in front of torch.optim.Adam on the CPU path — the same meaning.
+        for name, val in (("max_grad_norm", max_grad_norm), ("clip_grad_value", clip_grad_value)):
+            if val is not None and not float(val) >= 0.0:
+                raise ValueError(f"DataParallelTrainer: {name} must not be negative or NaN (got {val})")
+        if skip_nonfinite and not self.fused:
+            raise ValueError("DataParallelTrainer: skip_nonfinite is part of the fused GPU update (train.FlatAdam); the CPU path "
+                             "steps with torch.optim.Adam, which has no such guard")
+        self.max_grad_norm, self.clip_grad_value = max_grad_norm or None, clip_grad_value or None
+        self.optimizer = FlatAdam(self.params, self.flat_param, self.flat_grad, lr=lr, max_grad_norm=max_grad_norm,
+                                  clip_grad_value=clip_grad_value, skip_nonfinite=skip_nonfinite) if self.fused \
             else torch.optim.Adam(self.params, lr=lr)
         self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, patience=5, factor=0.2, min_lr=1e-6)
         if seed is not None:
@@ -312,6 +364,11 @@ class DataParallelTrainer:
         """One optimisation step on this rank's shard. Returns the local loss tensor (no host sync)."""
         total = self.backward_shard(x, target, pred_frames, **fwd_kwargs)
         self.reduce_gradients()
+        if not self.fused:   # (fused: FlatAdam clips inside its update)
+            if self.max_grad_norm:
+                torch.nn.utils.clip_grad_norm_(self.params, self.max_grad_norm)
+            if self.clip_grad_value:
+                torch.nn.utils.clip_grad_value_(self.params, self.clip_grad_value)
         self.optimizer.step()
         return total
 

@@ -15,6 +15,8 @@ DEFAULT_RUN_CONFIG is the reference's DefaultRunConfig (defaults.py:37-64) key f
   * One added key, test_batch_size = 1: test() may evaluate several datapoints per launch. Per-horizon means stay means over
     DATAPOINTS (batch means weighted by batch size), so a ragged last batch changes nothing.
   * One added key, flat_adam = False: True trains with train.FlatAdam (one HIP kernel over flat buckets) instead of torch.optim.Adam.
+    FlatAdam's gradient clipping (max_grad_norm, clip_grad_value, skip_nonfinite) has NO run-config key: train() builds the optimizer
+    without it; a loop that wants it calls model.train_iter with its own FlatAdam.
   * Batches come from the datasets' own loader() — GPU batches made in this process. There are no DataLoader worker processes (the
     reference's num_workers=4 would open the card from four more processes).
   * A dataset that is generated on the fly has its generators reset before every validation pass and before every test pass, so that
