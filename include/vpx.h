@@ -34,6 +34,7 @@
  * vpx_mmnist_frames                MovingMNISTOnTheFly.__getitem__ (a batch) vp_suite/datasets/mmnist_on_the_fly.py:78-104,133-147
  * vpx_frames_preprocess            VPDataset.preprocess (a batch of stored sequences)  vp_suite/base/base_dataset.py:233-273, datasets/mmnist.py:56-57
  * vpx_frames_postprocess           VPDataset.postprocess                    vp_suite/base/base_dataset.py:286-297
+ * vpx_frames_augment               the colour and erasing entries of VPDataset's augmentation list  vp_suite/base/base_dataset.py:19-23,135-141
  * vpx_frames_adapt                 ScaleToModel / ScaleToTest + TF.Resize   vp_suite/utils/compatibility.py:31-50, utils/models.py:7-64
  * vpx_nchw_to_nhwc / nhwc_to_nchw  (layout adaptors at the boundary; the reference is NCHW throughout)
  *
@@ -589,6 +590,27 @@ enum { VPX_FRAMES_U8 = 0, VPX_FRAMES_U16 = 1, VPX_FRAMES_F32 = 2 };
 int vpx_frames_preprocess(const void* src, int dtype, long long N, int Tp, int H, int W, int Cs, const int* table, int B, int n_frames,
                           int seq_step, int ch, int cw, int oh, int ow, int C_out, double lo, double hi, float* out, void* stream);
 int vpx_frames_postprocess(const float* x, long long N, int C, int h, int w, double lo, double hi, unsigned char* out, void* stream);
+
+/* ---- photometric augmentations and erasing of a preprocessed batch, in place (torchvision's tensor transforms, restated) ----
+ * x [B, n_frames, C, h, w] dense fp32, changed in place by ONE launch; programs [B, max_ops, VPX_FRAMES_AUG_ROW] (fp32, on the device):
+ * sample b runs rows (opcode, p0 .. p7) until opcode 0 or max_ops rows, the same program on each of its frames (parameters are drawn
+ * once per sequence, on the host). Per element every step is one correctly rounded fp32 operation, never a fused multiply-add.
+ * clamp(v) = v < 0 ? 0 : (v > 1 ? 1 : v), literally, whatever value range the frames are in; gray = (0.2989f r + 0.587f g) + 0.114f b;
+ * blend(a, b) = clamp(p0 * a + p1 * b), the caller passing p0 = float(f), p1 = float(1 - f) (the difference formed in double).
+ *   1 invert        v = 1 - v                                2 solarize     v >= p0 ? 1 - v : v
+ *   3 autocontrast  per frame and channel lo / hi = min / max over h x w; hi == lo: unchanged; else clamp((v - lo) * (1 / (hi - lo)))
+ *   4 grayscale     C = 3: all planes = gray                 5 normalize    (v - p[c]) / p[4 + c]
+ *   6 brightness    blend(v, 0)                              7 contrast     blend(v, m), m = float(sum / (h w)) of gray (C = 3) or v (C = 1)
+ *   8 saturation    C = 3: blend(v, gray); C = 1: identity      over the frame, the sum formed in fp64 in a fixed tree
+ *   9 hue           C = 3: _rgb2hsv, h = (h + p0) mod 1, _hsv2rgb; C = 1: identity
+ *  10 erase         rows [p0, p0 + p2) x columns [p1, p1 + p3), clipped to the frame, = p[4 + c]
+ * One workgroup per (sample, frame) sweeps the frame 1 + (number of operations 3 and 7) times (once more, read only, when the program
+ * begins with one). No workspace, no atomics: two runs give equal bits. 64-bit element offsets.
+ * VPX_ERR_ARG: a NULL pointer, a size < 1, max_ops outside [16, 64]. VPX_ERR_UNSUPPORTED: C > 4, a side beyond 32768, B * n_frames
+ * beyond one grid. `programs` lives on the device, so the CALLER checks it: a row the kernel cannot run (an unknown opcode; 4 without
+ * three channels; 7, 8 or 9 with neither one nor three) ends the program there, and nothing is read or written outside the frames. */
+#define VPX_FRAMES_AUG_ROW 9
+int vpx_frames_augment(float* x, const float* programs, int B, int n_frames, int C, int h, int w, int max_ops, void* stream);
 
 /* ---- frame adapter between a model and a test set (vp_suite/utils/compatibility.py: ScaleToModel / ScaleToTest, then TF.Resize) ----
  * x [N, C, H, W] planar fp32 (only read) -> out [N, C, oh, ow], one launch, no workspace, no atomics, 64-bit element offsets. Forward

@@ -22,6 +22,7 @@ FLAG_WEIGHTS_PACKED = 2
 FLAG_X_SPLIT = 4
 FLAG_OUT_SPLIT = 8
 FRAMES_U8, FRAMES_U16, FRAMES_F32 = 0, 1, 2
+FRAMES_AUG_ROW, FRAMES_AUG_MIN_OPS, FRAMES_AUG_MAX_OPS = 9, 16, 64   # a program row: opcode + 8 parameters; rows per program
 
 OPT_CELL2 = 1
 OPT_CELL3 = 2
@@ -188,6 +189,7 @@ SIGNATURES = {
     # stored frames to a model-ready batch and back
     "vpx_frames_preprocess": (ci, [vp, ci, ll] + [ci] * 4 + [vp] + [ci] * 8 + [dbl, dbl, vp, vp]),   # src dtype N T' H W Cs | table B F step ch cw oh ow C_out | lo hi | out
     "vpx_frames_postprocess": (ci, [vp, ll] + [ci] * 3 + [dbl, dbl, vp, vp]),                       # x N C h w | lo hi | out
+    "vpx_frames_augment": (ci, [vp, vp] + [ci] * 6 + [vp]),                                           # x programs | B F C h w max_ops
     # frame adapter between a model and a test set
     "vpx_frames_adapt": (ci, [vp, ll] + [ci] * 5 + [dbl] * 4 + [vp, vp]),                            # x N C H W oh ow | src lo hi, dst lo hi | out
     # layout adaptors

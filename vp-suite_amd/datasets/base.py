@@ -6,7 +6,9 @@ produces its frames at their final size and value range in the generating kernel
 
 StoredVPDataset: sequences held as ONE raw tensor [N, T', H, W(, C)] — on the GPU, or in pinned host memory — and the reference's
 preprocess() / postprocess() chain (convert, permute, scale, crop, resize, flip) as one launch of csrc/frames.hip per batch and
-direction. No ATen op touches a pixel between the stored bytes and the batch a model reads."""
+direction. No ATen op touches a pixel between the stored bytes and the batch a model reads. The colour and erasing augmentations of the
+reference's list run as per-sample programs in at most one further launch (csrc/frames_aug.hip), in place on the batch."""
+import math
 import random
 
 import numpy as np
@@ -160,6 +162,161 @@ def parse_augmentations(augmentations):
     return out
 
 
+def is_flip(aug):
+    """True for the entries parse_augmentations() takes: they stay in the preprocess launch."""
+    return (isinstance(aug, (tuple, list)) and len(aug) > 0 and aug[0] in ("hflip", "vflip")) or type(aug).__name__ in ("RandomHorizontalFlip", "RandomVerticalFlip")
+
+
+# opcodes of a program row (csrc/frames_aug.hip, include/vpx.h)
+OP_INVERT, OP_SOLARIZE, OP_AUTOCONTRAST, OP_GRAY, OP_NORMALIZE, OP_BRIGHTNESS, OP_CONTRAST, OP_SATURATION, OP_HUE, OP_ERASE = range(1, 11)
+PROGRAM_ROW, PROGRAM_MIN_OPS, PROGRAM_MAX_OPS = 9, 16, 64
+
+_BYTE_ONLY = {"RandomPosterize": "posterize", "RandomEqualize": "equalize"}
+_OTHER_KERNEL = {"GaussianBlur": "blur", "RandomAdjustSharpness": "sharpness", "RandomRotation": "rotate"}
+_P_ONLY = {"RandomInvert": "invert", "RandomAutocontrast": "autocontrast", "RandomGrayscale": "grayscale"}
+
+
+def _probability(p, aug):
+    if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"augmentation {aug!r}: probability outside [0, 1]")
+    return float(p)
+
+
+def _numbers(v, aug, what):
+    """A tuple of floats from one number or a sequence of numbers."""
+    seq = list(v) if isinstance(v, (tuple, list, np.ndarray)) else [v]
+    if not seq or not all(isinstance(e, (int, float, np.integer, np.floating)) and not isinstance(e, bool) and math.isfinite(float(e)) for e in seq):
+        raise ValueError(f"augmentation {aug!r}: {what} must be a number or a sequence of numbers")
+    return tuple(float(e) for e in seq)
+
+
+def _jitter_range(value, name, center, bound, aug, clip_first_on_zero=True):
+    """torchvision's ColorJitter._check_input: None, or the (min, max) a factor is drawn from; None when that is (center, center)."""
+    if value is None:
+        return None
+    if isinstance(value, (int, float, np.integer, np.floating)) and not isinstance(value, bool):
+        if value < 0:
+            raise ValueError(f"augmentation {aug!r}: if {name} is a single number, it must be non negative")
+        lo, hi = center - float(value), center + float(value)
+        if clip_first_on_zero:
+            lo = max(lo, 0.0)
+    elif isinstance(value, (tuple, list)) and len(value) == 2:
+        lo, hi = _numbers(value, aug, name)
+    else:
+        raise ValueError(f"augmentation {aug!r}: {name} should be None, a single number or a (min, max) pair")
+    if not bound[0] <= lo <= hi <= bound[1]:
+        raise ValueError(f"augmentation {aug!r}: {name} values should be between {bound} and ordered (got {(lo, hi)}; negative factors and a hue outside [-0.5, 0.5] are refused)")
+    return None if lo == hi == center else (lo, hi)
+
+
+def parse_photometric(augmentations):
+    """The colour and erasing entries of an `augmentations` list in canonical form, in their order:
+    ("invert", p) | ("solarize", threshold, p) | ("autocontrast", p) | ("grayscale", p) | ("normalize", means, stds) |
+    ("color_jitter", brightness, contrast, saturation, hue) with each None or the (min, max) its factor is drawn from |
+    ("erase", p, (scale min, max), (ratio min, max), values). Accepts those tuples (color_jitter with torchvision's argument forms: None,
+    a number x for [max(0, 1 - x), 1 + x] / [-x, x], or a pair) and objects named RandomInvert, RandomSolarize, RandomAutocontrast,
+    RandomGrayscale, Grayscale, Normalize, ColorJitter, RandomErasing carrying torchvision's attributes (read by name: torchvision is
+    never imported). What needs the frame shape is checked by check_photometric()."""
+    out = []
+    for aug in augmentations or []:
+        kind = type(aug).__name__
+        is_seq = isinstance(aug, (tuple, list)) and len(aug) > 0 and isinstance(aug[0], str)
+        tag = aug[0] if is_seq else None
+        if kind in _BYTE_ONLY or tag in _BYTE_ONLY.values():
+            raise NotImplementedError(f"augmentation {aug!r} is not part of this build: torchvision's posterize and equalize accept byte tensors only, "
+                                      f"and the reference's own chain raises on its float frames")
+        if kind in _OTHER_KERNEL or tag in _OTHER_KERNEL.values():
+            raise NotImplementedError(f"augmentation {aug!r} is not part of this build: blur, sharpness and rotation are neighbourhood and geometric "
+                                      f"operations (a different kernel), not the element-wise ones the augment launch runs")
+        if kind in _P_ONLY and hasattr(aug, "p"):
+            out.append((_P_ONLY[kind], _probability(aug.p, aug)))
+        elif is_seq and tag in _P_ONLY.values() and len(aug) == 2:
+            out.append((tag, _probability(aug[1], aug)))
+        elif kind == "Grayscale" and hasattr(aug, "num_output_channels"):
+            if aug.num_output_channels != 3:
+                raise NotImplementedError(f"augmentation {aug!r}: Grayscale(num_output_channels={aug.num_output_channels}) changes the frame shape; only 3 is part of this build")
+            out.append(("grayscale", 1.0))
+        elif (kind == "RandomSolarize" and hasattr(aug, "threshold") and hasattr(aug, "p")) or (is_seq and tag == "solarize" and len(aug) == 3):
+            thr, p = (aug.threshold, aug.p) if not is_seq else aug[1:]
+            out.append(("solarize", _numbers(thr, aug, "threshold")[0], _probability(p, aug)))
+        elif (kind == "Normalize" and hasattr(aug, "mean") and hasattr(aug, "std")) or (is_seq and tag == "normalize" and len(aug) == 3):
+            mean, std = (aug.mean, aug.std) if not is_seq else aug[1:]
+            mean, std = _numbers(mean, aug, "mean"), _numbers(std, aug, "std")
+            if any(np.float32(v) == 0 for v in std):
+                raise ValueError(f"augmentation {aug!r}: a zero std (the division would give infinities)")
+            out.append(("normalize", mean, std))
+        elif (kind == "ColorJitter" and all(hasattr(aug, a) for a in ("brightness", "contrast", "saturation", "hue"))) or (is_seq and tag == "color_jitter" and len(aug) == 5):
+            b, c, sat, hue = (aug.brightness, aug.contrast, aug.saturation, aug.hue) if not is_seq else aug[1:]
+            inf = float("inf")
+            out.append(("color_jitter", _jitter_range(b, "brightness", 1.0, (0.0, inf), aug), _jitter_range(c, "contrast", 1.0, (0.0, inf), aug),
+                        _jitter_range(sat, "saturation", 1.0, (0.0, inf), aug), _jitter_range(hue, "hue", 0.0, (-0.5, 0.5), aug, clip_first_on_zero=False)))
+        elif (kind == "RandomErasing" and all(hasattr(aug, a) for a in ("p", "scale", "ratio", "value"))) or (is_seq and tag == "erase" and len(aug) == 5):
+            p, scale, ratio, value = (aug.p, aug.scale, aug.ratio, aug.value) if not is_seq else aug[1:]
+            if value is None or isinstance(value, str):
+                raise NotImplementedError(f"augmentation {aug!r}: erasing with value='random' (noise from torch's generator) is not part of this build; give a number or one per channel")
+            scale, ratio = _numbers(scale, aug, "scale"), _numbers(ratio, aug, "ratio")
+            if len(scale) != 2 or len(ratio) != 2 or not 0.0 <= scale[0] <= scale[1] <= 1.0 or not 0.0 < ratio[0] <= ratio[1]:
+                raise ValueError(f"augmentation {aug!r}: scale must be an ordered pair in [0, 1] and ratio an ordered pair of positive numbers")
+            out.append(("erase", _probability(p, aug), scale, ratio, _numbers(value, aug, "value")))
+        else:
+            raise NotImplementedError(f"augmentation {aug!r} is not part of this build: flips, invert, solarize, autocontrast, grayscale, normalize, "
+                                      f"color_jitter and erase are")
+    return out
+
+
+def check_photometric(photometric, channels):
+    """The refusals of parse_photometric()'s result that need the channel count of a returned frame."""
+    for entry in photometric:
+        kind = entry[0]
+        if kind == "grayscale" and channels != 3:
+            raise ValueError(f"augmentation {entry!r}: grayscale needs 3-channel frames (got {channels}; on one channel there is nothing to do, "
+                             f"and torchvision refuses it)")
+        if kind == "color_jitter" and channels not in (1, 3) and any(r is not None for r in entry[2:]):
+            raise ValueError(f"augmentation {entry!r}: contrast, saturation and hue need 1 or 3 channels (got {channels})")
+        for what, values in (("mean", entry[1]), ("std", entry[2])) if kind == "normalize" else ((("value", entry[4]),) if kind == "erase" else ()):
+            if len(values) not in (1, channels):
+                raise ValueError(f"augmentation {entry!r}: {len(values)} {what} entries for {channels} channels (one, or one per channel)")
+
+
+def _row(op, *params):
+    return (float(op),) + tuple(float(np.float32(p)) for p in params) + (0.0,) * (PROGRAM_ROW - 1 - len(params))
+
+
+def _per_channel(values, channels, fill):
+    values = tuple(values) * channels if len(values) == 1 else tuple(values)
+    return values + (fill,) * (4 - len(values))
+
+
+def draw_erase_box(rng, frame_hw, scale, ratio):
+    """torchvision's RandomErasing.get_params: (y0, x0, rows, columns), or None after ten attempts that did not fit."""
+    H, W = frame_hw
+    area = H * W
+    log_ratio = (math.log(ratio[0]), math.log(ratio[1]))
+    for _ in range(10):
+        erase_area = area * float(rng.uniform(scale[0], scale[1]))
+        aspect = math.exp(float(rng.uniform(log_ratio[0], log_ratio[1])))
+        eh = int(round(math.sqrt(erase_area * aspect)))
+        ew = int(round(math.sqrt(erase_area / aspect)))
+        if not (eh < H and ew < W):
+            continue
+        y0 = int(rng.integers(0, H - eh + 1))
+        x0 = int(rng.integers(0, W - ew + 1))
+        return y0, x0, eh, ew
+    return None
+
+
+def pack_programs(programs):
+    """float32 [n, max_ops, PROGRAM_ROW] from per-sample lists of rows: max_ops = the longest program, at least PROGRAM_MIN_OPS; opcode 0 ends one."""
+    longest = max(len(rows) for rows in programs)
+    if longest > PROGRAM_MAX_OPS:
+        raise ValueError(f"an augmentation program of {longest} operations exceeds the launch's {PROGRAM_MAX_OPS}")
+    out = np.zeros((len(programs), max(longest, PROGRAM_MIN_OPS), PROGRAM_ROW), dtype=np.float32)
+    for k, rows in enumerate(programs):
+        if rows:
+            out[k, :len(rows)] = np.array(rows, dtype=np.float32)
+    return out
+
+
 def center_offset(full, size):
     """torchvision's CenterCrop offset: int(round((full - size) / 2.0)) with Python's round (half to even)."""
     return int(round((full - size) / 2.0))
@@ -221,8 +378,17 @@ class StoredVPDataset(VPDataset):
     even when a crop without resize returns less). The resize is bilinear with align_corners=False and NO antialiasing: what the
     reference's pinned torchvision does to tensors; newer torchvision antialiases by default.
     crop: ("center", h, w) | ("random", h, w) | ("box", y, x, h, w), or a CenterCrop / RandomCrop object. augmentations: a list of
-    ("hflip", p) | ("vflip", p), or RandomHorizontalFlip / RandomVerticalFlip objects. Random boxes and flips are drawn ONCE per sequence
-    (the reference transforms the whole [t, c, h, w] tensor at once) from a host generator seeded with transform_seed."""
+    ("hflip", p) | ("vflip", p) and the colour and erasing entries parse_photometric() lists — ("invert", p), ("solarize", threshold, p),
+    ("autocontrast", p), ("grayscale", p), ("normalize", mean, std), ("color_jitter", brightness, contrast, saturation, hue),
+    ("erase", p, scale, ratio, value) — or the torchvision objects of those names. Random boxes, flips and every photometric parameter
+    are drawn ONCE per sequence (the reference transforms the whole [t, c, h, w] tensor at once) from a host generator seeded with
+    transform_seed: per sequence box row, box column, flips, then the photometric entries in list order (one random() per probability;
+    colour jitter a permutation of its four adjustments, then one uniform per configured one; erasing torchvision's ten attempts).
+    Operations act after scale, crop, resize and flips, in list order; an erasing rectangle is mirrored through the flips that follow it
+    in the list and were drawn, so the result is the list applied in order. The flips land in `augmentations`, the rest in `photometric`.
+    The clamps of colour jitter and autocontrast are to [0, 1] literally, also under a value range such as (-1, 1): the reference
+    scales before it transforms and torchvision clamps float tensors to [0, 1], so it behaves the same way. A channel that is constant
+    over a frame is left unchanged by autocontrast."""
     NAME = "Stored sequences"
     ACTION_SIZE = 0
     SUPPORTS_TRANSFORMS = True
@@ -235,7 +401,8 @@ class StoredVPDataset(VPDataset):
     device = "cuda"
     img_size = None
     crop = None
-    augmentations = None
+    augmentations = None   # the flips [(bit, p)]
+    photometric = None     # every other entry, parse_photometric()'s form
 
     def __init__(self, split, raw=None, **dataset_kwargs):
         super().__init__(split, **dataset_kwargs)
@@ -250,7 +417,11 @@ class StoredVPDataset(VPDataset):
         self.img_size = dataset_kwargs.get("img_size", None)
         parse_img_size(self.img_size, (1, 1))                     # (refused now; the size itself needs the stored frame shape)
         self.crop = parse_crop(dataset_kwargs.get("crop", None))
-        self.augmentations = parse_augmentations(dataset_kwargs.get("augmentations", []))
+        given = list(dataset_kwargs.get("augmentations", None) or [])
+        self.augmentations = parse_augmentations([aug for aug in given if is_flip(aug)])
+        self.photometric = parse_photometric([aug for aug in given if not is_flip(aug)])
+        flips_before = np.cumsum([is_flip(aug) for aug in given]).tolist()
+        self._flips_before = [n for n, aug in zip(flips_before, given) if not is_flip(aug)]   # per photometric entry: flips ahead of it in the list
         self._raw = self._raw_host = self._staging = self._staging_event = None
         self.reset_rng()
         if raw is not None:
@@ -280,6 +451,7 @@ class StoredVPDataset(VPDataset):
         want = parse_img_size(self.img_size, (H, W))
         self._out_hw = tuple(int(v) for v in (want if want != (H, W) else self._crop_hw))   # the reference appends Resize only then
         self.img_shape = (int(c_out),) + self._out_hw
+        check_photometric(self.photometric, int(c_out))
 
     def _stored(self):
         """The raw tensor where the storage mode keeps it (made at the first use: building a dataset needs no GPU)."""
@@ -311,8 +483,8 @@ class StoredVPDataset(VPDataset):
     def reset_rng(self):
         self.transform_rng = np.random.default_rng(self.transform_seed)
 
-    def _draw_transform(self, frame_hw, crop, transform=True):
-        """(crop y0, crop x0, flip bits) of one sequence; random boxes and flips advance the host generator, box rows first."""
+    def _draw_geometry(self, frame_hw, crop, transform=True):
+        """(crop y0, crop x0, flip bits, the flips' draws) of one sequence; random boxes and flips advance the host generator, box rows first."""
         H, W = frame_hw
         if not transform or crop is None:
             y0 = x0 = 0
@@ -323,20 +495,83 @@ class StoredVPDataset(VPDataset):
             x0 = int(self.transform_rng.integers(0, W - crop[2] + 1))
         else:
             y0, x0 = crop[1], crop[2]
-        bits = 0
+        bits, drawn = 0, []
         for bit, p in (self.augmentations if transform else []):
-            if self.transform_rng.random() < p:
+            drawn.append(bool(self.transform_rng.random() < p))
+            if drawn[-1]:
                 bits ^= bit
-        return y0, x0, bits
+        return y0, x0, bits, drawn
+
+    def _draw_transform(self, frame_hw, crop, transform=True):
+        """(crop y0, crop x0, flip bits) of one sequence."""
+        return self._draw_geometry(frame_hw, crop, transform)[:3]
+
+    def _draw_program(self, out_chw, flips_drawn, transform=True):
+        """The photometric program of one sequence, rows (opcode, 8 parameters) in the order they act; an operation that was not drawn
+        is absent. Advances the host generator after the sequence's box and flip draws, in list order."""
+        rows = []
+        if not transform:
+            return rows
+        C, h, w = out_chw
+        rng = self.transform_rng
+        for entry, n_before in zip(self.photometric, self._flips_before):
+            kind = entry[0]
+            if kind in ("invert", "autocontrast", "grayscale", "solarize"):
+                if rng.random() < entry[-1]:
+                    rows.append(_row({"invert": OP_INVERT, "autocontrast": OP_AUTOCONTRAST, "grayscale": OP_GRAY, "solarize": OP_SOLARIZE}[kind],
+                                     *((entry[1],) if kind == "solarize" else ())))
+            elif kind == "normalize":
+                rows.append(_row(OP_NORMALIZE, *_per_channel(entry[1], C, 0.0), *_per_channel(entry[2], C, 1.0)))
+            elif kind == "color_jitter":
+                order = [int(i) for i in rng.permutation(4)]
+                factors = [None if r is None else float(rng.uniform(r[0], r[1])) for r in entry[1:]]
+                for i in order:
+                    if factors[i] is None:
+                        continue
+                    if i == 3:
+                        rows.append(_row(OP_HUE, factors[i]))
+                    else:                                             # f and 1 - f, formed in double, each rounded to float32 once
+                        rows.append(_row((OP_BRIGHTNESS, OP_CONTRAST, OP_SATURATION)[i], factors[i], 1.0 - factors[i]))
+            else:                                                     # erase
+                if rng.random() < entry[1]:
+                    box = draw_erase_box(rng, (h, w), entry[2], entry[3])
+                    if box is not None:
+                        y0, x0, eh, ew = box
+                        for (bit, _), on in list(zip(self.augmentations, flips_drawn))[n_before:]:   # the flips that follow it mirror the box
+                            if on and bit == 1:
+                                x0 = w - x0 - ew
+                            elif on:
+                                y0 = h - y0 - eh
+                        rows.append(_row(OP_ERASE, y0, x0, eh, ew, *_per_channel(entry[4], C, 0.0)))
+        return rows
+
+    def draws(self, seqs, transform=True, frame_hw=None, crop="own", out_chw=None):
+        """(int32 [n, 4] rows (sequence index, crop y0, crop x0, flip bits), the n photometric programs) for the launches: one draw per
+        sequence, its box and flips first, its photometric parameters after them."""
+        frame_hw = tuple(self._raw_host.shape[2:4]) if frame_hw is None else frame_hw
+        crop = self.crop if isinstance(crop, str) else crop
+        out_chw = tuple(self.img_shape) if out_chw is None else out_chw
+        rows, programs = [], []
+        for s in seqs:
+            y0, x0, bits, drawn = self._draw_geometry(frame_hw, crop, transform)
+            rows.append((s, y0, x0, bits))
+            programs.append(self._draw_program(out_chw, drawn, transform))
+        return np.array(rows, dtype=np.int32).reshape(len(seqs), 4), programs
 
     def table(self, seqs, transform=True):
-        """int32 [n, 4] rows (sequence index, crop y0, crop x0, flip bits) for the launch: one draw per sequence."""
-        H, W = self._raw_host.shape[2:4]
-        return np.array([(s,) + self._draw_transform((H, W), self.crop, transform) for s in seqs], dtype=np.int32).reshape(len(seqs), 4)
+        """int32 [n, 4] rows (sequence index, crop y0, crop x0, flip bits) for the launch: one draw per sequence (draws() without its programs)."""
+        return self.draws(seqs, transform)[0]
+
+    def _augment(self, frames, programs):
+        """The second launch, on the same stream and without a host sync; none when every program is empty."""
+        if any(programs):
+            ops.frames_augment(frames, pack_programs(programs))
+        return frames
 
     def preprocess(self, x, transform=True):
         """The reference's preprocess() for one tensor [..., h, w(, c)] (2-D: one gray image), from one launch: float32 [..., c, h', w'] on
-        the GPU, scaled to the value range, then (transform=True) cropped, resized and flipped with ONE draw for the whole tensor. dtype
+        the GPU, scaled to the value range, then (transform=True) cropped, resized, flipped and run through the photometric entries with
+        ONE draw for the whole tensor. dtype
         rules as the reference's where the kernel has the element type: numpy uint8 / uint16 and torch uint8 are divided by their
         maximum; torch float32 passes through and torch double is converted to it (the reference's message names torch.float, its
         code refuses it); everything else raises its ValueError."""
@@ -364,10 +599,12 @@ class StoredVPDataset(VPDataset):
             raise ValueError(f"the crop {crop} does not fit the {H}x{W} frames (there is no padding)")
         want = parse_img_size(self.img_size, (H, W))
         oh, ow = want if (transform and want != tuple(self.DATASET_FRAME_SHAPE[:2])) else (ch, cw)
-        row = np.array([(0,) + self._draw_transform((H, W), crop, transform)], dtype=np.int32)
+        if transform:
+            check_photometric(self.photometric, C)
+        row, programs = self.draws([0], transform, (H, W), crop, (C, oh, ow))
         out = ops.frames_preprocess(x.reshape(1, T, H, W, C).to(self.device), row, T, 1, (ch, cw), (oh, ow), C,
                                     (self.value_range_min, self.value_range_max))
-        return out.reshape(lead + (C, oh, ow))
+        return self._augment(out, programs).reshape(lead + (C, oh, ow))
 
     def postprocess(self, x):
         """uint8 numpy [..., h, w, c] in [0, 255] from a tensor [..., c, h, w] in (about) the value range (base_dataset.py:275-298), one
@@ -386,7 +623,7 @@ class StoredVPDataset(VPDataset):
         return f"stored sequence {i}"
 
     def batch(self, indices):
-        """The reference's dict for these samples from ONE launch: frames [n, total_frames, C, h, w] on the GPU, actions zeros
+        """The reference's dict for these samples from ONE launch (two when a photometric program was drawn): frames [n, total_frames, C, h, w] on the GPU, actions zeros
         [n, total_frames, max(ACTION_SIZE, 1)], origin. Equal to the __getitem__ calls in the same order."""
         if not self.ready_for_usage:
             raise RuntimeError("Dataset is not yet ready for usage (maybe you forgot to call set_seq_len()).")
@@ -396,8 +633,10 @@ class StoredVPDataset(VPDataset):
         if min(indices) < 0 or max(indices) >= len(self):
             raise IndexError(f"sample index outside [0, {len(self)})")
         raw, seqs = self._on_device(indices)
-        frames = ops.frames_preprocess(raw, self.table(seqs), self.total_frames, self.seq_step, self._crop_hw, self._out_hw, self.img_shape[0],
+        table, programs = self.draws(seqs)
+        frames = ops.frames_preprocess(raw, table, self.total_frames, self.seq_step, self._crop_hw, self._out_hw, self.img_shape[0],
                                        (self.value_range_min, self.value_range_max))
+        self._augment(frames, programs)
         actions = torch.zeros((len(indices), self.total_frames, max(self.ACTION_SIZE, 1)), device=frames.device)
         return {"frames": frames, "actions": actions, "origin": [self.origin(i) for i in indices]}
 

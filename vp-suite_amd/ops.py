@@ -1438,6 +1438,47 @@ def frames_postprocess(x, lo=0.0, hi=1.0):
     return out
 
 
+# ---- photometric augmentations and erasing of a preprocessed batch (csrc/frames_aug.hip) ----
+def check_frames_programs(programs, n_samples):
+    """The programs an augment launch is handed, checked where they can be read (the host): float32 [B, max_ops, FRAMES_AUG_ROW] with
+    max_ops in [FRAMES_AUG_MIN_OPS, FRAMES_AUG_MAX_OPS], every opcode a whole number in 0 ... 10 and every parameter finite."""
+    import numpy as np
+    t = np.asarray(programs)
+    if t.ndim != 3 or t.shape[0] != n_samples or t.shape[2] != _lib.FRAMES_AUG_ROW or t.dtype != np.float32:
+        raise ValueError(f"programs must be a float32 table [{n_samples}, max_ops, {_lib.FRAMES_AUG_ROW}] (got {t.dtype} {t.shape})")
+    if not _lib.FRAMES_AUG_MIN_OPS <= t.shape[1] <= _lib.FRAMES_AUG_MAX_OPS:
+        raise ValueError(f"programs hold {t.shape[1]} rows per sample, outside [{_lib.FRAMES_AUG_MIN_OPS}, {_lib.FRAMES_AUG_MAX_OPS}]")
+    op = t[:, :, 0]
+    if not np.isfinite(t).all() or (op != np.floor(op)).any() or op.min() < 0 or op.max() > 10:
+        raise ValueError("programs: an opcode outside 0 ... 10 or a parameter that is not finite")
+    return np.ascontiguousarray(t)
+
+
+def frames_augment(x, programs):
+    """Runs per-sample programs of photometric operations and erasing over x [B, n_frames, C, h, w] (a contiguous float32 GPU tensor)
+    IN PLACE, in one launch, and returns x — see include/vpx.h for the operations and their float32 forms. `programs`: rows
+    [B, max_ops, 9] = (opcode, 8 parameters), opcode 0 ends a program; a host array is checked here and copied to the device once, a GPU
+    tensor is taken as it is (the kernel ends a program at a row it cannot run and writes nothing outside the frames)."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise _lib.VpxError("frames_augment: x must be a GPU tensor; frames are augmented by a HIP kernel, there is no CPU fallback")
+    if x.dtype != torch.float32:
+        raise ValueError(f"frames_augment: expected float32, got {x.dtype}")
+    if x.ndim != 5 or not x.is_contiguous():
+        raise ValueError(f"frames_augment: x must be a contiguous [B, n_frames, C, h, w] tensor, changed in place (got {tuple(x.shape)})")
+    B, F, C, h, w = (int(s) for s in x.shape)
+    if min(B, F, C, h, w) < 1:
+        raise ValueError(f"frames_augment: empty input {tuple(x.shape)}")
+    if torch.is_tensor(programs) and programs.is_cuda:
+        if programs.dtype != torch.float32 or programs.ndim != 3 or programs.shape[0] != B or programs.shape[2] != _lib.FRAMES_AUG_ROW or not programs.is_contiguous():
+            raise ValueError(f"frames_augment: programs must be a contiguous float32 table [{B}, max_ops, {_lib.FRAMES_AUG_ROW}] (got {programs.dtype} {tuple(programs.shape)})")
+        dev = programs
+    else:
+        dev = torch.from_numpy(check_frames_programs(programs.numpy() if torch.is_tensor(programs) else programs, B)).to(x.device)
+    with torch.cuda.device(x.device):
+        check(_lib.lib().vpx_frames_augment(ptr(x), ptr(dev), B, F, C, h, w, int(dev.shape[1]), stream()), "vpx_frames_augment")
+    return x
+
+
 # ---- frame adapter between a model and a test set (csrc/adapt.hip) ----
 def frames_adapt(x, out_hw=None, src_range=(0.0, 1.0), dst_range=(0.0, 1.0)):
     """float32 [..., C, oh, ow] on the GPU from planar float32 frames x [N, C, H, W] or [b, t, C, H, W] in ONE launch: every value mapped
