@@ -115,26 +115,43 @@ int vpx_set_deterministic(int on);
  *                        stage; same wave tile, same LDS traffic, the chip holds a higher clock on it). Same products, same
  *                        operand split: results differ in fp32 summation order only */
 #define VPX_OPT_MFMA_SHAPE 3
-/*   VPX_OPT_EXPERIMENT   bits of kernel variants under measurement (A/B inside one process; 0 = the product's behaviour):
- *                        1 no sync-point stagger in the 32x16-tile cell; 4 the 32x16 tile instead of the half tile (fused cell,
- *                        data gradient); 8 (+ distance << 8) diagnostic placement of a pixel tile's N tiles in the dispatch order;
- *                        16 the 32x16 tile for the stage-glue kernel (convq); 32 the hoisted input projection of the small-grid
- *                        paths on the first-generation kernel; 64 the ST-LSTM step's k x k weight gradients on the first-generation
- *                        launches instead of the one-launch split-operand kernel (stw, wgrad2.hip); 128 its k x k data gradients on the
- *                        first-generation kernel instead of the 16x16-tile job-table kernel (c5, convq.hip); 256 the same for its forward
- *                        launches (gate groups, conv_o + output gate); 512 the 1x1 layers (conv_last, its adjoint, the decoupling
- *                        tail's adapter) on the implicit-GEMM kernel instead of the streaming one (c1, conv1.hip); 1024 the c5 launches
- *                        unsplit on grids below their pixel-tile bar (48 tiles forward, 96 backward; tests); 2048 the first-generation launches instead of the
- *                        K-split c5 jobs on those grids; 4096 the half tile of the fused ConvLSTM step
- *                        instead of its narrow-tile form (c3: c5_kernel<4, 3>) on grids of at most 256 half-tile workgroups;
- *                        8192 c3 with 32-column tiles (c5_kernel<2, 3>) instead of 64-column ones; 16384 the stage glue's data
- *                        gradients on the first-generation kernel where the schedule-driven one (convq) would take them; 32768 the fused
- *                        ConvLSTM step on the eight-wave half tile (cell2_kernel_x: 64-register wave tiles, four waves per SIMD) instead of the
- *                        four-wave one, 65536 its column split instead of the row split; 1 << 27 the ST-LSTM step's conv_last (1x1) on the fp32 c_new / m_new (converted in the
- *                        kernel) instead of on the split copies its gate stage leaves; 1 << 28 3x3 layers with 16 output channels on the
- *                        first-generation kernel instead of the resident-weights one (csrc/conv16.hip); 1 << 29 the stage glue's weight
- *                        gradients on the tap-group kernel (fp32 operands) instead of wgrad2_kernel's glue form on split copies */
+/*   VPX_OPT_EXPERIMENT   bits of kernel variants under measurement (A/B inside one process; 0 = the product's behaviour): an OR of
+ *                        the VPX_EXP_* values below. Any value is stored; bits without a name select nothing. */
 #define VPX_OPT_EXPERIMENT 4
+/* Selection bits, read by the host code that chooses a launch. Each names the form it switches ON in place of the product's. */
+#define VPX_EXP_CELL2_FULL_TILE 4         /* the 32x16 tile instead of the half tile (fused cell, data gradient) */
+#define VPX_EXP_CONVQ_FULL_TILE 16        /* the 32x16 tile for the stage-glue kernel (convq) */
+#define VPX_EXP_HOIST_GEN1 32             /* the hoisted input projection of the small-grid paths on the first-generation kernel */
+#define VPX_EXP_ST_WGRAD_GEN1 64          /* the ST-LSTM step's k x k weight gradients on the first-generation launches instead of the
+                                           * one-launch split-operand kernel (stw, wgrad2.hip) */
+#define VPX_EXP_ST_DGRAD_GEN1 128         /* its k x k data gradients on the first-generation kernel instead of the 16x16-tile job-table
+                                           * kernel (c5, convq.hip) */
+#define VPX_EXP_ST_FWD_GEN1 256           /* the same for its forward launches (gate groups, conv_o + output gate) */
+#define VPX_EXP_C1_GEN1 512               /* the 1x1 layers (conv_last, its adjoint, the decoupling tail's adapter) on the implicit-GEMM
+                                           * kernel instead of the streaming one (c1, conv1.hip) */
+#define VPX_EXP_C5_UNSPLIT 1024           /* the c5 launches unsplit on grids below their pixel-tile bar (48 tiles forward, 96 backward; tests) */
+#define VPX_EXP_C5_NO_KSPLIT 2048         /* the first-generation launches instead of the K-split c5 jobs on those grids */
+#define VPX_EXP_NO_C3 4096                /* the half tile of the fused ConvLSTM step instead of its narrow-tile form (c3: c5_kernel<4, 3>)
+                                           * on grids of at most 256 half-tile workgroups */
+#define VPX_EXP_C3_NARROW 8192            /* c3 with 32-column tiles (c5_kernel<2, 3>) instead of 64-column ones */
+#define VPX_EXP_GLUE_DGRAD_GEN1 16384     /* the stage glue's data gradients on the first-generation kernel where the schedule-driven one
+                                           * (convq) would take them */
+#define VPX_EXP_CELL2X 32768              /* the fused ConvLSTM step on the eight-wave half tile (cell2_kernel_x: 64-register wave tiles,
+                                           * four waves per SIMD) instead of the four-wave one */
+#define VPX_EXP_CELL2X_COLSPLIT 65536     /* cell2_kernel_x's column split instead of its row split */
+#define VPX_EXP_ST_LAST_FP32 (1 << 27)    /* the ST-LSTM step's conv_last (1x1) on the fp32 c_new / m_new (converted in the kernel) instead
+                                           * of on the split copies its gate stage leaves */
+#define VPX_EXP_NO_C16 (1 << 28)          /* 3x3 layers with 16 output channels on the first-generation kernel instead of the
+                                           * resident-weights one (csrc/conv16.hip) */
+#define VPX_EXP_GLUE_WGRAD_TAPGROUP (1 << 29) /* the stage glue's weight gradients on the tap-group kernel (fp32 operands) instead of
+                                           * wgrad2_kernel's glue form on split copies */
+/* Diagnostics of the 16x16x32-form cell kernel (cell2_kernel_q), read inside the kernel: the launch hands it the option word masked
+ * with VPX_EXP_CELL2_DIAG_MASK and nothing else. */
+#define VPX_EXP_CELL2_NO_STAGGER 1        /* no sync-point stagger between the wave halves of the 32x16-tile cell */
+#define VPX_EXP_CELL2_PLACEMENT 8         /* the N tiles of a pixel tile D dispatch positions apart inside an XCD, D = bits 8-19 of the
+                                           * option word (value | D << 8). That field lies on top of the selection bits 256 .. 65536:
+                                           * never combine VPX_EXP_CELL2_PLACEMENT with one of them */
+#define VPX_EXP_CELL2_DIAG_MASK (VPX_EXP_CELL2_NO_STAGGER | VPX_EXP_CELL2_PLACEMENT | (0xfff << 8))
 /*   VPX_OPT_DRY_RUN      1 = every entry point does all of its host-side work (argument checks, kernel selection, workspace carving
  *                        and the bounds checks of everything it would write into the workspace) but issues no HIP call: needs no GPU
  *                        and touches none of the pointers (they only have to be non-NULL where the call requires a tensor). A sizing

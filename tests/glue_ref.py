@@ -25,7 +25,6 @@ from golden_util import name_seed, seeded_randn
 __all__ = ["BARS", "HOST_SHARE", "KINK_SHARE", "SAME_PRODUCTS", "SLOPE", "relmax"]
 
 KINK_BAR = BARS["bf16x3"][0]
-BIT_DX_GEN1, BIT_NO_C16, BIT_WGRAD_TAPGROUP = 1 << 14, 1 << 28, 1 << 29     # VPX_OPT_EXPERIMENT (include/vpx.h)
 _OPS = ((0, 0), (1, 0), (0, 1), (1, 1))
 
 

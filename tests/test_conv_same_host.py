@@ -119,9 +119,8 @@ def test_next_to_nothing_sits_on_the_kink(table, i):
 @pytest.fixture(scope="module")
 def L():
     lib = _lib.lib()
-    prev = lib.vpx_set_option(_lib.OPT_DRY_RUN, 1)
-    yield lib
-    lib.vpx_set_option(_lib.OPT_DRY_RUN, prev)
+    with _lib.option(_lib.OPT_DRY_RUN, 1):
+        yield lib
     lib.vpx_set_deterministic(0)
 
 

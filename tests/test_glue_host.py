@@ -11,7 +11,7 @@ import torch
 
 import glue_ref as R
 from vp_suite_amd import _lib
-from vp_suite_amd._lib import ConvDesc
+from vp_suite_amd._lib import ConvDesc, Exp
 
 OK, E_ARG, E_WS, E_UNSUPPORTED = 0, -1, -2, -4
 WS_BASE = 0x7F0000000000            # fake workspace address (256-byte aligned; never dereferenced in a dry run)
@@ -116,12 +116,12 @@ def wgrad_small_applicable(c):                            # csrc/lstm_bwd.hip (p
 
 def c16_applicable(c, prec, exp=0):                       # csrc/conv16.hip
     tr, N, Ci, Co, kh, kw, s, p, oph, opw, H, W = c
-    return (not exp & R.BIT_NO_C16 and prec == "bf16x3" and (kh, kw, s, p) == (3, 3, 1, 1) and Co == 16 and Ci % 16 == 0 and 16 <= Ci <= 64)
+    return (not exp & Exp.NO_C16 and prec == "bf16x3" and (kh, kw, s, p) == (3, 3, 1, 1) and Co == 16 and Ci % 16 == 0 and 16 <= Ci <= 64)
 
 
 def ex_wgrad_split(c, prec, exp=0):                       # csrc/conv_api.hip (at the default MFMA shape)
     tr, N, Ci, Co, kh, kw, s, p, oph, opw, H, W = c
-    return (not exp & R.BIT_WGRAD_TAPGROUP and prec == "bf16x3" and Ci % 8 == 0 and Co % 8 == 0 and kh <= 2 * s + 1 and kw <= 2 * s + 1
+    return (not exp & Exp.GLUE_WGRAD_TAPGROUP and prec == "bf16x3" and Ci % 8 == 0 and Co % 8 == 0 and kh <= 2 * s + 1 and kw <= 2 * s + 1
             and kh * kw > 1 and wgrad_small_applicable(c) is None)
 
 
@@ -237,7 +237,7 @@ def routes(c, prec, v, relu=False, exp=0, training=True, from_split=False):
         _gen1(c, prec, names, "fwd.")
     if not training:
         return names
-    dq = not exp & R.BIT_DX_GEN1 and Co % 8 == 0 and exq_preferred(adjoint(c), prec)
+    dq = not exp & Exp.GLUE_DGRAD_GEN1 and Co % 8 == 0 and exq_preferred(adjoint(c), prec)
     act = relu or v["slope"] != 0.0
     if act or v["bias"]:
         names.add("colsum." + ("v4" if Co % 4 == 0 else "scalar") + (".split_copy" if act and (dq or wsp) and Co % 4 == 0 else ""))
@@ -286,16 +286,13 @@ def test_tables_are_what_the_kernels_need():
                 for training in ((True, False) if table == "WAVES8" else (table != "CONVQ_FWD",)):   # (WAVES8: an inference call as well)
                     for r in routes(c, prec, v, training=training, from_split=table == "CONVQ_FWD"):
                         seen.setdefault(r, []).append(R.case_id(table, i))
-        for bit, restated in ((R.BIT_NO_C16, takes_split(c, "bf16x3", R.BIT_NO_C16)), (R.BIT_WGRAD_TAPGROUP, None)):
+        for bit, restated in ((Exp.NO_C16, takes_split(c, "bf16x3", Exp.NO_C16)), (Exp.GLUE_WGRAD_TAPGROUP, None)):
             d = _desc(c, "bf16x3", v["slope"])
-            prev = L.vpx_set_option(_lib.OPT_EXPERIMENT, bit)
-            try:
+            with _lib.experiment(bit):
                 if restated is not None:
                     assert L.vpx_conv2d_ex_takes_split(ctypes.byref(d)) == restated, R.case_id(table, i)
                 else:
                     assert L.vpx_conv2d_ex_bwd_uses_split(ctypes.byref(d)) == 0, R.case_id(table, i)
-            finally:
-                L.vpx_set_option(_lib.OPT_EXPERIMENT, prev)
         N, Co = c[1], c[3]
         assert N * Co * R.out_shape(c)[0] * R.out_shape(c)[1] <= 5e5 or (table, i) == ("WAVES8", 1), R.case_id(table, i)
     for table, i in R.ACT:
@@ -344,7 +341,7 @@ def test_tables_are_what_the_kernels_need():
         assert takes_split(c, "bf16x3") == 1 and ex_wgrad_split(c, "bf16x3") == (c[4] != 7), c
     assert {(c[2], c[3]) for c in R.SPLIT} == set(R._SPLIT_CH) and {(c[10], c[11]) for c in R.SPLIT} == {(19, 21), (9, 7)}
     assert {(c[0], c[4], c[6], c[7]) for c in R.SPLIT} == set(R._SPLIT_LAYERS) and len(R.SPLIT) == 24
-    assert all(c16_applicable(c, "bf16x3") and not c16_applicable(c, "bf16x3", R.BIT_NO_C16) for c in R.C16)
+    assert all(c16_applicable(c, "bf16x3") and not c16_applicable(c, "bf16x3", Exp.NO_C16) for c in R.C16)
     assert {(c[0], c[2]) for c in R.C16} == {(tr, ci) for tr in (0, 1) for ci in (16, 32, 48, 64)}
     # CONVQ: the smallest plain-conv grid exq_preferred takes — 256 workgroups, one frame fewer is refused
     c = R.CONVQ_FWD[0]
@@ -410,9 +407,8 @@ def test_fp32_reference_holds_a_fifth_of_the_f32_bars_and_next_to_nothing_sits_o
 @pytest.fixture(scope="module")
 def L():
     lib = _lib.lib()
-    prev = lib.vpx_set_option(_lib.OPT_DRY_RUN, 1)
-    yield lib
-    lib.vpx_set_option(_lib.OPT_DRY_RUN, prev)
+    with _lib.option(_lib.OPT_DRY_RUN, 1):
+        yield lib
     lib.vpx_set_deterministic(0)
 
 

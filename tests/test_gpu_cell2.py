@@ -16,15 +16,21 @@ pytestmark = pytest.mark.gpu
 from parity import relmax as _relmax   # max|a - b| / max|b|, recorded (tests/parity.py)
 
 
-@pytest.fixture
-def cell2_switch(vpx):
-    L = vpx._lib.lib()
-    prev = L.vpx_set_option(vpx._lib.OPT_CELL2, 1)
+def _switch(opt, initial):
+    """A fixture that holds option `opt` at `initial` for the test (vpx._lib.option puts the earlier value back) and hands the test a
+    setter for it."""
+    @pytest.fixture
+    def switch(vpx):
+        opt_id = getattr(vpx._lib, opt)
+        with vpx._lib.option(opt_id, initial):
+            yield lambda v: vpx._lib.lib().vpx_set_option(opt_id, v)
+    return switch
 
-    def set_mode(v):
-        L.vpx_set_option(vpx._lib.OPT_CELL2, v)
-    yield set_mode
-    L.vpx_set_option(vpx._lib.OPT_CELL2, prev)
+
+cell2_switch = _switch("OPT_CELL2", 1)
+cell3_switch = _switch("OPT_CELL3", 1)
+shape_switch = _switch("OPT_MFMA_SHAPE", 0)
+experiment_switch = _switch("OPT_EXPERIMENT", 0)   # values: vpx._lib.Exp
 
 
 CASES = {  # tag: (Cin, Ch, H, W, B, T, with_x, with_state, peephole, gate_order)
@@ -155,17 +161,6 @@ CASES3 = {  # eligible shapes: channels in 16s (<= 96), maps in whole 16x16 tile
 CASES.update(CASES3)
 
 
-@pytest.fixture
-def cell3_switch(vpx):
-    L = vpx._lib.lib()
-    prev = L.vpx_set_option(vpx._lib.OPT_CELL3, 1)
-
-    def set_mode(v):
-        L.vpx_set_option(vpx._lib.OPT_CELL3, v)
-    yield set_mode
-    L.vpx_set_option(vpx._lib.OPT_CELL3, prev)
-
-
 @pytest.mark.parametrize("tag", list(CASES3))
 def test_cell3_matches_split_path_and_oracle_and_is_reproducible(vpx, cell3_switch, tag):
     cell3_switch(0)
@@ -238,17 +233,6 @@ CASESQ = {  # full 32x16 tiles and whole 32-channel tiles for the fused step; th
 CASES.update(CASESQ)
 
 
-@pytest.fixture
-def shape_switch(vpx):
-    L = vpx._lib.lib()
-    prev = L.vpx_set_option(vpx._lib.OPT_MFMA_SHAPE, 0)
-
-    def set_mode(v):
-        L.vpx_set_option(vpx._lib.OPT_MFMA_SHAPE, v)
-    yield set_mode
-    L.vpx_set_option(vpx._lib.OPT_MFMA_SHAPE, prev)
-
-
 @pytest.mark.parametrize("tag", list(CASESQ))
 def test_mfma_16x16x32_form_matches_32x32x16_form_and_oracle(vpx, cell2_switch, shape_switch, tag):
     cell2_switch(2)
@@ -278,31 +262,20 @@ def test_mfma_16x16x32_training_path_vs_oracle(vpx, cell2_switch, shape_switch, 
 
 
 # ---- the half tile (cell2_kernel_q<.., 4>: 16x16-pixel tiles, two workgroups per CU, weight ring of two chunks in halves) ----
-@pytest.fixture
-def experiment_switch(vpx):
-    L = vpx._lib.lib()
-    prev = L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, 0)
-
-    def set_mode(v):
-        L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, v)
-    yield set_mode
-    L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, prev)
-
-
 @pytest.mark.parametrize("tag", list(CASESQ))
 def test_small_grid_32_column_tiles_match_the_half_tile(vpx, cell2_switch, shape_switch, experiment_switch, tag):
-    """c3 (c5_kernel<4, 3> — the product's choice — and c5_kernel<2, 3>, VPX_OPT_EXPERIMENT bit 13; round 4): the fused step on
+    """c3 (c5_kernel<4, 3> — the product's choice — and c5_kernel<2, 3>, VPX_EXP_C3_NARROW; round 4): the fused step on
     16x16-pixel tiles x (4 gates x 16 | 8 channels), 8-channel stages, four stage buffers — what inference runs where the half tile
     has at most 256 workgroups (every case here). Same operand split and products, other summation order: 2e-6 against the half tile
-    (bit 12), 2e-5 against the oracle, bit-identical run to run; x-only / h-only / x + h packs, both gate orders, with and without
+    (VPX_EXP_NO_C3), 2e-5 against the oracle, bit-identical run to run; x-only / h-only / x + h packs, both gate orders, with and without
     peepholes, odd stage counts."""
     cell2_switch(2)
     shape_switch(1)
     ro, rh, rc, _ = _oracle(tag)
     with torch.no_grad():
-        experiment_switch(4096)
+        experiment_switch(vpx._lib.Exp.NO_C3)
         o1, h1, c1, _ = _run(vpx, tag, grads=False)
-        for bits in (0, 8192):   # 64-column tiles, 32-column tiles
+        for bits in (0, vpx._lib.Exp.C3_NARROW):   # 64-column tiles, 32-column tiles
             experiment_switch(bits)
             o2, h2, c2, _ = _run(vpx, tag, grads=False)
             o3, _, _, _ = _run(vpx, tag, grads=False)
@@ -316,9 +289,9 @@ def test_half_tile_bit_identical_to_full_tile(vpx, cell2_switch, shape_switch, e
     """Same products in the same order per output element: the two tile forms must agree bit for bit."""
     cell2_switch(2)
     shape_switch(1)
-    experiment_switch(4)
+    experiment_switch(vpx._lib.Exp.CELL2_FULL_TILE)
     o1, h1, c1, _ = _run(vpx, tag, grads=False)
-    experiment_switch(2)
+    experiment_switch(0)
     o2, h2, c2, _ = _run(vpx, tag, grads=False)
     assert torch.equal(o2, o1) and torch.equal(c2, c1) and torch.equal(h2, h1)
     ro, rh, rc, _ = _oracle(tag)
@@ -329,9 +302,9 @@ def test_half_tile_bit_identical_to_full_tile(vpx, cell2_switch, shape_switch, e
 def test_half_tile_training_path(vpx, cell2_switch, shape_switch, experiment_switch, tag):
     cell2_switch(2)
     shape_switch(1)
-    experiment_switch(4)
+    experiment_switch(vpx._lib.Exp.CELL2_FULL_TILE)
     out1, _, _, g1 = _run(vpx, tag, grads=True)
-    experiment_switch(2)
+    experiment_switch(0)
     out2, _, _, g2 = _run(vpx, tag, grads=True)
     assert torch.equal(out1, out2)
     for k in g1:
@@ -345,9 +318,9 @@ def test_half_tile_training_path(vpx, cell2_switch, shape_switch, experiment_swi
 @pytest.mark.parametrize("tag", ["enc2_b4", "enc3_states", "t1_single_step"])
 def test_hoisted_projection_on_convq_matches_first_generation_launch(vpx, cell3_switch, experiment_switch, tag):
     """Small-grid path (cell3): W_x * x_t of all frames as one convq launch (default) against the first-generation launch
-    (VPX_OPT_EXPERIMENT bit 5): same bf16x3 products, other summation order."""
+    (VPX_EXP_HOIST_GEN1): same bf16x3 products, other summation order."""
     cell3_switch(1)
-    experiment_switch(32)
+    experiment_switch(vpx._lib.Exp.HOIST_GEN1)
     o1, h1, c1, _ = _run(vpx, tag, grads=False)
     experiment_switch(0)
     o2, h2, c2, _ = _run(vpx, tag, grads=False)
@@ -357,9 +330,11 @@ def test_hoisted_projection_on_convq_matches_first_generation_launch(vpx, cell3_
     assert _relmax(o2, ro) < 2e-5 and _relmax(c2, rc) < 2e-5
 
 
-# ---- the eight-wave half tile (csrc/cell2x.hip, round 6): 64-register wave tiles, four waves per SIMD; VPX_OPT_EXPERIMENT bit 15 selects
-#      it, bit 16 swaps its wave split (columns <-> rows) ----
-X_FORM, X_SWAP = 32768, 65536
+# ---- the eight-wave half tile (csrc/cell2x.hip, round 6): 64-register wave tiles, four waves per SIMD; VPX_EXP_CELL2X selects
+#      it, VPX_EXP_CELL2X_COLSPLIT swaps its wave split (columns <-> rows) ----
+def _x_forms(vpx):
+    E = vpx._lib.Exp
+    return E.CELL2X, E.CELL2X | E.CELL2X_COLSPLIT
 
 
 @pytest.mark.parametrize("tag", list(CASESQ) + ["plain_s14", "plain_s7_many_tiles"])
@@ -371,7 +346,7 @@ def test_x_form_bit_identical_to_half_tile(vpx, cell2_switch, shape_switch, expe
     with torch.no_grad():
         experiment_switch(0)
         o1, h1, c1, _ = _run(vpx, tag, grads=False)
-        for bits in (X_FORM, X_FORM | X_SWAP):
+        for bits in _x_forms(vpx):
             experiment_switch(bits)
             o2, h2, c2, _ = _run(vpx, tag, grads=False)
             assert torch.equal(o2, o1) and torch.equal(c2, c1) and torch.equal(h2, h1), (bits, _relmax(o2, o1), _relmax(c2, c1))
@@ -388,7 +363,7 @@ def test_x_form_plain_bf16_bit_identical_to_half_tile(vpx, cell2_switch, experim
     with torch.no_grad():
         experiment_switch(0)
         o1, h1, c1, _ = _run(vpx, tag, grads=False, precision="bf16")
-        for bits in (X_FORM, X_FORM | X_SWAP):
+        for bits in _x_forms(vpx):
             experiment_switch(bits)
             o2, h2, c2, _ = _run(vpx, tag, grads=False, precision="bf16")
             assert torch.equal(o2, o1) and torch.equal(c2, c1) and torch.equal(h2, h1), (bits, _relmax(o2, o1), _relmax(c2, c1))
@@ -400,7 +375,7 @@ def test_x_form_training_path_vs_oracle(vpx, cell2_switch, shape_switch, experim
     cell2_switch(2)
     shape_switch(1)
     ro, rh, rc, rg = _oracle(tag)
-    for bits in (X_FORM, X_FORM | X_SWAP):
+    for bits in _x_forms(vpx):
         experiment_switch(bits)
         out, hT, cT, g = _run(vpx, tag, grads=True)
         assert _relmax(out, ro) < 2e-5

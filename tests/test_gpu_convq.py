@@ -67,28 +67,24 @@ def test_glue_layer_on_split_input_vs_torch(vpx, tag):
 
 @pytest.mark.parametrize("tag", ["deconv2_t2k4", "conv3_s2k3", "conv2_s2k3_co64", "deconv3_t1k3_co16", "ragged_s2k3", "ragged_t2k4"])
 def test_half_tile_and_full_tile_agree_bit_for_bit(vpx, tag):
-    """convq on 16x16-pixel tiles (two workgroups per CU, ring of two weight chunks: the default) and on 32x16 tiles (VPX_OPT_EXPERIMENT
-    bit 4): the same products in the same order per output element."""
+    """convq on 16x16-pixel tiles (two workgroups per CU, ring of two weight chunks: the default) and on 32x16 tiles (VPX_EXP_CONVQ_FULL_TILE):
+    the same products in the same order per output element."""
     N, Ci, Co, H, W, k, s, p, tr, slope = CASES[tag]
     x = seeded_rand((N, Ci, H, W), name_seed(f"convq.{tag}.x")).cuda() - 0.3
     wshape = (Ci, Co, k, k) if tr else (Co, Ci, k, k)
     w = (seeded_randn(wshape, name_seed(f"convq.{tag}.w"), 1.0 / np.sqrt(Ci * k * k))).cuda()
     b = seeded_randn((Co,), name_seed(f"convq.{tag}.b"), 0.1).cuda()
     xbuf, _ = vpx.ops.split_convert(x)
-    L = vpx._lib.lib()
-    prev = L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, 0)
-    try:
+    with vpx._lib.experiment(0):
         y4, _, _ = vpx.ops.conv2d_ex_from_split(xbuf, (N, Ci, H, W), w, b, s, p, tr, slope, "bf16x3")
-        L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, 16)
+    with vpx._lib.experiment(vpx._lib.Exp.CONVQ_FULL_TILE):
         y8, _, _ = vpx.ops.conv2d_ex_from_split(xbuf, (N, Ci, H, W), w, b, s, p, tr, slope, "bf16x3")
-    finally:
-        L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, prev)
     assert torch.equal(y4, y8)
 
 
 @pytest.mark.parametrize("tag", ["deconv3_t1k3_co16", "c16_plain_ci32_ragged", "c16_plain_ci48_many_tiles", "c16_t_ci64_many_tiles"])
 def test_sixteen_column_kernel_vs_first_generation(vpx, tag):
-    """conv16.hip against the first-generation kernel on the same split input (VPX_OPT_EXPERIMENT bit 28): the same bf16x3 products,
+    """conv16.hip against the first-generation kernel on the same split input (VPX_EXP_NO_C16): the same bf16x3 products,
     summed in a different order — equal to fp32 rounding of the sums."""
     N, Ci, Co, H, W, k, s, p, tr, slope = CASES[tag]
     x = seeded_rand((N, Ci, H, W), name_seed(f"convq.{tag}.x")).cuda() - 0.3
@@ -96,14 +92,10 @@ def test_sixteen_column_kernel_vs_first_generation(vpx, tag):
     w = (seeded_randn(wshape, name_seed(f"convq.{tag}.w"), 1.0 / np.sqrt(Ci * k * k))).cuda()
     b = seeded_randn((Co,), name_seed(f"convq.{tag}.b"), 0.1).cuda()
     xbuf, _ = vpx.ops.split_convert(x)
-    L = vpx._lib.lib()
-    prev = L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, 0)
-    try:
+    with vpx._lib.experiment(0):
         y16, _, _ = vpx.ops.conv2d_ex_from_split(xbuf, (N, Ci, H, W), w, b, s, p, tr, slope, "bf16x3")
-        L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, 1 << 28)
+    with vpx._lib.experiment(vpx._lib.Exp.NO_C16):
         y1, _, _ = vpx.ops.conv2d_ex_from_split(xbuf, (N, Ci, H, W), w, b, s, p, tr, slope, "bf16x3")
-    finally:
-        L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, prev)
     assert _relmax(y16, y1) < 2e-6, tag
 
 

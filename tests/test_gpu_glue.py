@@ -18,11 +18,11 @@ writes at the end of a `-m gpu` session — under this file's test names); worst
                                         bf16x3: y 1.1e-5 (PHASES 2x2 p1 op 1,0), dx 1.1e-5 (FLIP 1x1), dw 1.4e-5 (SMALL 4 -> 1), db 5.4e-7
   test_conv2d_act_relu_vs_fp64          f32: y 3.0e-7, gradients 2.7e-7; bf16x3: y 5.4e-6, gradients 7.8e-6 (STRIDED 3x3 p1, dw)
   test_eight_wave_workgroups_...        y 7.2e-6 (stride 2, both calls), dx 5.3e-6, dw 4.5e-6, db 9.9e-8
-  test_split_training_call_...          y 6.6e-6, dx 7.1e-6, dw 6.8e-6 (8 -> 8 5x5 s2), db 2.3e-7; bit 29 off against on 2.7e-7 (bar 2e-5)
-  test_c16_gate_...                     y 6.9e-6, dx 6.8e-6, dw 5.2e-6; bit 28 off against on 4.0e-7
+  test_split_training_call_...          y 6.6e-6, dx 7.1e-6, dw 6.8e-6 (8 -> 8 5x5 s2), db 2.3e-7; GLUE_WGRAD_TAPGROUP off against on 2.7e-7 (bar 2e-5)
+  test_c16_gate_...                     y 6.9e-6, dx 6.8e-6, dw 5.2e-6; NO_C16 off against on 4.0e-7
   test_forward_from_split_input_...     y 6.9e-6 (C16 32 -> 16), before and after the weight update
   test_convq_forward_with_output_...    y 5.6e-6
-  test_data_gradient_on_convq_...       y 7.5e-6, dx 7.6e-6 (4x4 s2 on 9x12), dw 6.5e-6; bit 14 off against on 2.0e-7
+  test_data_gradient_on_convq_...       y 7.5e-6, dx 7.6e-6 (4x4 s2 on 9x12), dw 6.5e-6; GLUE_DGRAD_GEN1 off against on 2.0e-7
   test_deterministic_mode_...           dx 7.6e-6, dw 6.1e-6; the second run equal bit for bit
 No case needed a bar other than the table's. Not measured: nothing — every test of the file ran. 296 tests; the file takes 5.4 s."""
 import ctypes
@@ -82,19 +82,6 @@ def _hold_all(parity_log, out, ref, prec, tag=""):
     assert (out[3] is None) == (ref["db"] is None)
 
 
-class _Option:
-    """VPX_OPT_EXPERIMENT set for a block, restored in `finally`."""
-
-    def __init__(self, vpx, bits):
-        self.vpx, self.bits = vpx, bits
-
-    def __enter__(self):
-        self.prev = self.vpx._lib.lib().vpx_set_option(self.vpx._lib.OPT_EXPERIMENT, self.bits)
-
-    def __exit__(self, *exc):
-        self.vpx._lib.lib().vpx_set_option(self.vpx._lib.OPT_EXPERIMENT, self.prev)
-
-
 # ---- ops.conv2d_ex in both operand modes: phases, strides, flipped taps, the few-channel layers ------------------------------------------
 EX_CASES = [(t, i, p) for t in R.BOTH_MODES for i in range(len(R.TABLES[t])) for p in ("f32", "bf16x3")]
 
@@ -133,7 +120,7 @@ def _ab(vpx, parity_log, table, i, bit, same=("y", "dx", "dw", "db")):
     ref = R.case(table, i)[1]
     outs = {}
     for bits in (0, bit):
-        with _Option(vpx, bits):
+        with vpx._lib.experiment(bits):
             outs[bits] = _run(vpx, table, i, "bf16x3")
         _hold_all(parity_log, outs[bits], ref, "bf16x3", f".bit{bits.bit_length() - 1 if bits else 'off'}")
     for k, a, b in zip(("y", "dx", "dw", "db"), outs[0], outs[bit]):
@@ -147,15 +134,15 @@ def _ab(vpx, parity_log, table, i, bit, same=("y", "dx", "dw", "db")):
 @pytest.mark.parametrize("i", range(len(R.SPLIT)), ids=_ids([("SPLIT", i) for i in range(len(R.SPLIT))]))
 def test_split_training_call_vs_fp64_and_tap_group_kernel(vpx, parity_log, i):
     """x converted once, the forward from split input, the weight gradient per stride residue on wgrad2_kernel's glue form (k7 s2 and
-    single-tap residues: launch_wgrad) — and with VPX_OPT_EXPERIMENT bit 29 the fp32-operand tap-group weight gradient behind the plain
+    single-tap residues: launch_wgrad) — and with VPX_EXP_GLUE_WGRAD_TAPGROUP the fp32-operand tap-group weight gradient behind the plain
     forward. The same bf16x3 products both ways."""
-    _ab(vpx, parity_log, "SPLIT", i, R.BIT_WGRAD_TAPGROUP)
+    _ab(vpx, parity_log, "SPLIT", i, vpx._lib.Exp.GLUE_WGRAD_TAPGROUP)
 
 
 @pytest.mark.parametrize("i", range(len(R.C16)), ids=_ids([("C16", i) for i in range(len(R.C16))]))
 def test_c16_gate_vs_fp64_and_first_generation(vpx, parity_log, i):
-    """conv16.hip behind a training call (bit 28: the first generation on the same split input)."""
-    _ab(vpx, parity_log, "C16", i, R.BIT_NO_C16)
+    """conv16.hip behind a training call (VPX_EXP_NO_C16: the first generation on the same split input)."""
+    _ab(vpx, parity_log, "C16", i, vpx._lib.Exp.NO_C16)
 
 
 FROM_SPLIT = [("SPLIT", i) for i in range(len(R.SPLIT))] + [("C16", i) for i in range(len(R.C16))] + [("CONVQ_FWD", i) for i in R.CONVQ_FWD_PYTHON]
@@ -219,8 +206,8 @@ def test_convq_forward_with_output_padding_through_the_c_abi(vpx, parity_log, ta
 @pytest.mark.parametrize("i", range(len(R.CONVQ_BWD)), ids=_ids([("CONVQ_BWD", i) for i in range(len(R.CONVQ_BWD))]))
 def test_data_gradient_on_convq_with_a_padded_adjoint_vs_fp64_and_first_generation(vpx, parity_log, i):
     """64 -> 16 stride-2 layers whose adjoint (16 -> 64, transposed) convq takes, with the output padding made from the rows / columns the
-    forward dropped; bit 14 keeps the first-generation data gradient."""
-    _ab(vpx, parity_log, "CONVQ_BWD", i, R.BIT_DX_GEN1)
+    forward dropped; VPX_EXP_GLUE_DGRAD_GEN1 keeps the first-generation data gradient."""
+    _ab(vpx, parity_log, "CONVQ_BWD", i, vpx._lib.Exp.GLUE_DGRAD_GEN1)
 
 
 @pytest.mark.parametrize("table,i", R.DETERMINISTIC, ids=_ids(R.DETERMINISTIC))

@@ -324,6 +324,12 @@ def test_phydnet_tiny_action_conditional_vs_golden(vpx, parity_log):
 
 @pytest.mark.parametrize("precision", ["f32", "bf16x3"])
 def test_phydnet_default_model_vs_golden(vpx, precision):
+    """The default model's prediction against the golden's strided slice (FWD_TOL) and its checksum over all 40 960 elements.
+    Measured, 8 fresh models per operand mode and library build in one process, MI355X: no two predictions are bit-equal (the small-map
+    convolutions add their K-split partial sums with atomics). f32: slice 2.9e-6 .. 4.0e-6, checksum error 5e-6 .. 9.9e-5 against its
+    bound of 1.05e-3. bf16x3: slice 3.1e-5 .. 4.5e-5, checksum error 3.5e-4 .. 1.31e-3 — the bound lies INSIDE that spread (4 of 16 runs
+    above it), so the bf16x3 case fails now and then with unchanged kernels. The bound stays as it is; the prediction needs to become
+    reproducible (or more exact in bf16x3) for this case to hold on every run."""
     g = load_golden("phydnet_default")
     m = _model(PHY_DEFAULT_KW, "default", precision)
     assert sum(p.numel() for p in m.parameters()) == int(g["n_params"])

@@ -221,7 +221,7 @@ def test_training_forward_with_frozen_cells(vpx, frozen):
 @pytest.mark.parametrize("B,Ttot,slices", [(24, 12, 8), (48, 12, 16), (128, 17, 32)])
 def test_deferred_weight_gradients_on_whole_slices_per_xcd(vpx, B, Ttot, slices):
     """The one-launch ST-LSTM weight gradient (stw_kernel) over a whole pass: 8 / 16 / 32 K slices, whole slices per XCD (round 5: its
-    block decode for slice counts in 8s; `stw_slices`) — against the FIRST-GENERATION per-step weight gradients (VPX_OPT_EXPERIMENT bit 6:
+    block decode for slice counts in 8s; `stw_slices`) — against the FIRST-GENERATION per-step weight gradients (VPX_EXP_ST_WGRAD_GEN1:
     other kernels, other summation order) on the same model, same frames, same sampling masks. 8x8 maps of two items each: 2B x (Ttot - 1)
     images -> 1 056 / 2 112 / 8 192 items."""
     from vp_suite_amd.measure import PredictionLossProvider
@@ -229,19 +229,15 @@ def test_deferred_weight_gradients_on_whole_slices_per_xcd(vpx, B, Ttot, slices)
     kw = dict(img_shape=(1, 32, 32), action_size=0, tensor_value_range=[0.0, 1.0], num_layers=2, num_hidden=[16, 16], cell_precision="bf16x3")
     P = 4
     frames = seeded_rand((B, Ttot, 1, 32, 32), name_seed(f"predrnn.slices{slices}.frames")).cuda()
-    L = vpx._lib.lib()
     res = {}
     for first_generation in (False, True):
-        prev = L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, 64 if first_generation else 0)
-        try:
+        with vpx._lib.experiment(vpx._lib.Exp.ST_WGRAD_GEN1 if first_generation else 0):
             m = _predrnn("slices", kw)
             m.sampling_eta = 0.5
             torch.manual_seed(4321)
             loss = m.training_loss(frames, frames[:, Ttot - P:], P, lp)
             loss.backward()
             torch.cuda.synchronize()
-        finally:
-            L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, prev)
         named = dict(m.named_parameters())
         res[first_generation] = (float(loss.detach()), {k: named[k].grad.detach().cpu().numpy() for k in sorted(named)})
     a, b = res[False], res[True]
@@ -260,19 +256,15 @@ def test_deferred_weight_gradients_at_model_width_on_whole_slices(vpx, B, slices
     kw = dict(img_shape=(1, 64, 64), action_size=0, tensor_value_range=[0.0, 1.0], num_layers=2, num_hidden=[128, 128], cell_precision="bf16x3")
     Ttot, P = 12, 4
     frames = seeded_rand((B, Ttot, 1, 64, 64), name_seed(f"predrnn.wide{slices}.frames")).cuda()
-    L = vpx._lib.lib()
     res = {}
     for first_generation in (False, True):
-        prev = L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, 64 if first_generation else 0)
-        try:
+        with vpx._lib.experiment(vpx._lib.Exp.ST_WGRAD_GEN1 if first_generation else 0):
             m = _predrnn("wide", kw)
             m.sampling_eta = 0.5
             torch.manual_seed(777)
             loss = m.training_loss(frames, frames[:, Ttot - P:], P, lp)
             loss.backward()
             torch.cuda.synchronize()
-        finally:
-            L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, prev)
         named = dict(m.named_parameters())
         res[first_generation] = (float(loss.detach()), {k: named[k].grad.detach().cpu().numpy() for k in sorted(named)})
         del m, loss
@@ -330,15 +322,15 @@ def test_stlstm_second_generation_backward_matches_first_generation(vpx, B, Cin,
     """Round-4 kernels of the ST-LSTM step's backward against the first-generation launches — same operands, same bf16x3 split, fp32
     summation order only:
       * stw (wgrad2.hip): the four 5x5 weight gradients + conv_last's in ONE launch on split operands (pair table, three tap
-        passes, K split of tap row 4 / of the centre tap, half-empty column tiles, ragged maps and row tiles) — VPX_OPT_EXPERIMENT
-        bit 6 switches it (and everything built on its split dG8) off;
+        passes, K split of tap row 4 / of the centre tap, half-empty column tiles, ragged maps and row tiles) — VPX_EXP_ST_WGRAD_GEN1
+        switches it (and everything built on its split dG8) off;
       * c5 (convq.hip): the 5x5 data gradients (conv_o's adjoint; dx | dh | dm as the jobs of one launch) on 16x16-pixel tiles with
-        8-channel stages — bit 7 switches it off alone;
+        8-channel stages — ST_DGRAD_GEN1 switches it off alone;
       * c5 forward (channels in 32s): both gate groups as the jobs of one launch (gate-interleaved N tiles, fused gate math, c_new /
-        m_new also written in the split format), conv_o + output gate as another — bit 8 switches it off;
-      * c1 (conv1.hip): conv_last and its adjoint as a streaming kernel with register-resident weights (Ch = 128 only) — bit 9;
+        m_new also written in the split format), conv_o + output gate as another — ST_FWD_GEN1 switches it off;
+      * c1 (conv1.hip): conv_last and its adjoint as a streaming kernel with register-resident weights (Ch = 128 only) — C1_GEN1;
       * on grids below 48 (forward) / 96 (backward) pixel tiles (every shape here) the c5 launches run K-SPLIT (chunks of K as separate jobs writing partial sums,
-        st_pointwise.hip adds them): the default; bit 10 forces the unsplit forms, bit 11 the first generation."""
+        st_pointwise.hip adds them): the default; C5_UNSPLIT forces the unsplit forms, C5_NO_KSPLIT the first generation."""
     from golden_util import seeded_randn
     k = 5
     tag = f"stw.{B}.{Cin}.{Ch}.{H}.{W}"
@@ -354,28 +346,25 @@ def test_stlstm_second_generation_backward_matches_first_generation(vpx, B, Cin,
         outs = vpx.ops.stlstm_step(*a, *w, precision="bf16x3")
         sum((o * g).sum() for o, g in zip(outs, gout)).backward()
         return [o.detach() for o in outs] + [t.grad for t in a + w]
-    L = vpx._lib.lib()
+    E = vpx._lib.Exp
     labels = ["h_new", "c_new", "m_new", "delta_c", "delta_m"] + list(names) + list(shapes)
     # deterministic mode for every run: the first generation's K-split data gradients otherwise add their partial sums with
     # atomics, and two runs then see dG differing in the last bits (the comparisons below would be flaky at their 5e-6 bar)
     torch.use_deterministic_algorithms(True)
-    FORCE = 1024   # the c5 launches also below their grid bar (these test shapes are small)
-    L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, FORCE)
+    FORCE = E.C5_UNSPLIT   # the c5 launches also below their grid bar (these test shapes are small)
     try:
-        new = run()
-        res = {}
-        # 0 = the product's choice on these small grids: the K-split job forms of c5 (partial sums + pointwise stages); 2048 = the
-        # first generation there
-        # (round 6) 1 << 27: conv_last reads the fp32 c_new / m_new and converts in the kernel, instead of the split copies the gate stage leaves
-        for bits in (FORCE | 64, FORCE | 128, FORCE | 256, FORCE | 64 | 256, FORCE | 512, FORCE | (1 << 27), 0, 1 << 27, 2048, 2048 | 64):
-            prev = L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, bits)
-            try:
-                res[bits] = run()
-            finally:
-                L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, prev)
-        again = run()
+        with vpx._lib.experiment(FORCE):
+            new = run()
+            res = {}
+            # 0 = the product's choice on these small grids: the K-split job forms of c5 (partial sums + pointwise stages); C5_NO_KSPLIT =
+            # the first generation there
+            # (round 6) ST_LAST_FP32: conv_last reads the fp32 c_new / m_new and converts in the kernel, instead of the split copies the gate stage leaves
+            for bits in (FORCE | E.ST_WGRAD_GEN1, FORCE | E.ST_DGRAD_GEN1, FORCE | E.ST_FWD_GEN1, FORCE | E.ST_WGRAD_GEN1 | E.ST_FWD_GEN1,
+                         FORCE | E.C1_GEN1, FORCE | E.ST_LAST_FP32, 0, E.ST_LAST_FP32, E.C5_NO_KSPLIT, E.C5_NO_KSPLIT | E.ST_WGRAD_GEN1):
+                with vpx._lib.experiment(bits):
+                    res[bits] = run()
+            again = run()
     finally:
-        L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, 0)
         torch.use_deterministic_algorithms(False)
     for bits, old in res.items():
         for n, a, b in zip(labels, new, old):
@@ -383,7 +372,7 @@ def test_stlstm_second_generation_backward_matches_first_generation(vpx, B, Cin,
     for a, b in zip(new, again):
         assert torch.equal(a, b)   # no atomics in either kernel or in the slice reduction: bit-reproducible
     # the 1x1 layer on split sources multiplies the very same (hi, lo) pairs the in-kernel conversion makes: bit-identical h_new
-    assert torch.equal(new[0], res[FORCE | (1 << 27)][0]) and torch.equal(res[0][0], res[1 << 27][0])
+    assert torch.equal(new[0], res[FORCE | E.ST_LAST_FP32][0]) and torch.equal(res[0][0], res[E.ST_LAST_FP32][0])
 
 
 @pytest.mark.parametrize("B", [3, 100])

@@ -28,9 +28,8 @@ def _fake(i, off=0):   # distinct fake device addresses (256-byte aligned + off)
 @pytest.fixture
 def L(vpx):
     lib = vpx._lib.lib()
-    prev = lib.vpx_set_option(vpx._lib.OPT_DRY_RUN, 1)
-    yield lib
-    lib.vpx_set_option(vpx._lib.OPT_DRY_RUN, prev)
+    with vpx._lib.option(vpx._lib.OPT_DRY_RUN, 1):
+        yield lib
 
 
 # ---- the yardstick: clip_ref against torch in float64 --------------------------------------------------------------------------------

@@ -53,6 +53,117 @@ def test_binding_argument_counts_match_the_header(vpx):
         assert len(fn.argtypes) == n, f"{name}: {n} parameters in include/vpx.h, {len(fn.argtypes)} argtypes in _lib.py"
 
 
+def _header_experiments():
+    """{name: value} of every `#define VPX_EXP_<name> <value>` of include/vpx.h (a value may use the names defined before it)."""
+    code = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "vpx.h")).read(), flags=re.S)
+    table = {}
+    for name, expr in re.findall(r"^#define\s+VPX_EXP_(\w+)\s+(.+?)\s*$", code, flags=re.M):
+        assert name not in table, name
+        table[name] = eval(re.sub(r"VPX_EXP_(\w+)", lambda m: str(table[m.group(1)]), expr), {"__builtins__": {}})
+    return table
+
+
+DIAGNOSTICS = {"CELL2_NO_STAGGER", "CELL2_PLACEMENT", "CELL2_DIAG_MASK"}   # read inside cell2_kernel_q, not by the host's selection rules
+
+
+def test_experiment_names_match_the_header(vpx):
+    """The VPX_EXP_* table of include/vpx.h and _lib.Exp: the same names with the same values; every value but the diagnostic mask one
+    bit, no two alike; the mask exactly the two diagnostic bits and the placement distance (bits 8-19) — which is why
+    CELL2_PLACEMENT must not meet a selection bit of that range."""
+    hdr = _header_experiments()
+    assert len(hdr) >= 20, "VPX_EXP_* defines not parsed"
+    assert hdr == {name: int(member) for name, member in vpx._lib.Exp.__members__.items()}
+    bits = {name: v for name, v in hdr.items() if name != "CELL2_DIAG_MASK"}
+    assert all(v > 0 and v & (v - 1) == 0 for v in bits.values()), bits
+    assert len(set(bits.values())) == len(bits)
+    assert hdr["CELL2_DIAG_MASK"] == hdr["CELL2_NO_STAGGER"] | hdr["CELL2_PLACEMENT"] | 0xfff << 8
+    assert vpx._lib.exp_bits("CELL2X | CELL2X_COLSPLIT|1") == hdr["CELL2X"] | hdr["CELL2X_COLSPLIT"] | 1 and vpx._lib.exp_bits("0") == 0
+
+
+def _sources(*dirs_and_suffixes):
+    for d, suffixes in dirs_and_suffixes:
+        for dirpath, _, files in os.walk(os.path.join(ROOT, d)):
+            for f in files:
+                if f.endswith(suffixes):
+                    yield os.path.join(dirpath, f)
+
+
+def test_no_magic_experiment_masks_left():
+    """The library tests the option word through exp_on(VPX_EXP_...) alone (and hands the kernel `g_experiment & VPX_EXP_CELL2_DIAG_MASK`);
+    tests and tools name what they switch on (vp_suite_amd._lib.Exp) — no numeric literal as the value of OPT_EXPERIMENT."""
+    in_c = re.compile(r"g_experiment\s*&\s*[\d(]")
+    in_py = re.compile(r"OPT_EXPERIMENT\s*,[\s(+-]*\d|experiment(?:_switch)?\([\s(]*[1-9]")
+    assert in_c.search("(g_experiment" + " & 4096)") and in_c.search("g_experiment" + " & (1 << 27)")
+    assert in_py.search("vpx_set_option(_lib.OPT_EXPERIMENT" + ", 4096)") and in_py.search("(_lib.OPT_EXPERIMENT" + ", 1 << 28)")
+    assert in_py.search("experiment_switch" + "(4)") and in_py.search("_lib.experiment" + "(16384)")
+    found, n = [], 0
+    for path in _sources(("vp-suite_amd/csrc", (".hip", ".h")), ("tests", (".py",)), ("tools", (".py",))):
+        n += 1
+        rx = in_py if path.endswith(".py") else in_c
+        found += [f"{os.path.relpath(path, ROOT)}:{i}: {ln.strip()[:120]}" for i, ln in enumerate(open(path), 1) if rx.search(ln)]
+    assert n > 100 and not found, "\n".join(found)
+    # ... and the word itself is named where it is defined, written, read and handed to the one kernel that takes diagnostics from it
+    named = [(os.path.basename(p), ln.strip()) for p in _sources(("vp-suite_amd/csrc", (".hip", ".h"))) for ln in open(p) if "g_experiment" in ln]
+    assert sorted(f for f, _ in named) == ["cell2.hip", "vpx_api.hip", "vpx_api.hip", "vpx_api.hip", "vpx_internal.h", "vpx_internal.h"], named
+    assert [ln for f, ln in named if f == "cell2.hip"][0].startswith("p._q = g_experiment & VPX_EXP_CELL2_DIAG_MASK;")
+
+
+def test_option_restores_the_previous_value_on_exception(vpx):
+    """_lib.option / _lib.experiment: the value holds inside the block and the one from before comes back when the block raises — for all
+    five options, nested. In a dry run: nothing here needs a GPU. vpx_set_option stores any value, named or not."""
+    _lib = vpx._lib
+    L, E = _lib.lib(), _lib.Exp
+
+    def current(opt):
+        v = L.vpx_set_option(opt, 0)
+        assert L.vpx_set_option(opt, v) == 0
+        return v
+    opts = (_lib.OPT_CELL2, _lib.OPT_CELL3, _lib.OPT_MFMA_SHAPE, _lib.OPT_EXPERIMENT)
+    with _lib.option(_lib.OPT_DRY_RUN, 1):
+        assert current(_lib.OPT_DRY_RUN) == 1
+        before = [current(o) for o in opts]
+        assert before == [1, 1, 1, 0]
+        with pytest.raises(KeyError):
+            with _lib.option(_lib.OPT_CELL2, 2), _lib.option(_lib.OPT_CELL3, 0), _lib.option(_lib.OPT_MFMA_SHAPE, 0), _lib.experiment(E.NO_C3) as prev:
+                assert prev == 0 and [current(o) for o in opts] == [2, 0, 0, E.NO_C3]
+                unnamed = E.CELL2X | 1 << 20
+                with _lib.experiment(unnamed) as inner:
+                    assert inner == E.NO_C3 and current(_lib.OPT_EXPERIMENT) == unnamed
+                assert current(_lib.OPT_EXPERIMENT) == E.NO_C3
+                raise KeyError("inside the block")
+        assert [current(o) for o in opts] == before
+        epoch = L.vpx_option_epoch()
+        with _lib.experiment(0):
+            pass
+        assert L.vpx_option_epoch() == epoch + 2   # (a set and a restore: callers that cache on the epoch see both)
+    assert current(_lib.OPT_DRY_RUN) == 0
+
+
+def test_dry_run_sweeps_switch_on_every_selection_bit(vpx):
+    """Every bit the host's selection rules read (exp_on(VPX_EXP_...) in csrc/) is every name of the table but the kernel's diagnostics,
+    and tests/test_workspace_contract.py switches each on in the sweep of its family of entry points (the glue's c16 / weight-gradient
+    bits also in tests/test_glue_host.py's dry run)."""
+    import test_workspace_contract as wc
+    E = vpx._lib.Exp
+    read = set()
+    for path in _sources(("vp-suite_amd/csrc", (".hip", ".h"))):
+        read |= set(re.findall(r"exp_on\(VPX_EXP_(\w+)\)", open(path).read()))
+    assert read == set(E.__members__) - DIAGNOSTICS
+    family = {"convlstm": "CELL2_FULL_TILE HOIST_GEN1 NO_C3 C3_NARROW CELL2X CELL2X_COLSPLIT",
+              "stlstm": "ST_WGRAD_GEN1 ST_DGRAD_GEN1 ST_FWD_GEN1 C1_GEN1 C5_UNSPLIT C5_NO_KSPLIT ST_LAST_FP32",
+              "decouple": "C1_GEN1",
+              "glue": "CONVQ_FULL_TILE GLUE_DGRAD_GEN1 NO_C16 GLUE_WGRAD_TAPGROUP"}
+    assert set(" ".join(family.values()).split()) == read
+    assert set(wc.SWEPT_EXPERIMENTS) == set(family)
+    for fam, names in family.items():
+        swept = 0
+        for bits in wc.SWEPT_EXPERIMENTS[fam]:
+            swept |= bits
+            assert not bits & E.CELL2_PLACEMENT   # (its distance field would alias the selection bits)
+        assert all(swept & E[n] for n in names.split()), (fam, [n for n in names.split() if not swept & E[n]])
+        assert 0 in wc.SWEPT_EXPERIMENTS[fam] or fam == "convlstm"   # (its sweep runs without any option first)
+
+
 def test_workspace_queries_run_without_gpu(vpx):
     L = vpx._lib.lib()
     d = vpx._lib.ConvLSTMDesc(4, 10, 64, 64, 64, 64, 3, 3, 0, 0, 0, 1)

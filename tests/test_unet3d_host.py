@@ -204,9 +204,8 @@ def _fake(i):
 def L():
     from vp_suite_amd import _lib
     lib = _lib.lib()
-    prev = lib.vpx_set_option(_lib.OPT_DRY_RUN, 1)
-    yield lib
-    lib.vpx_set_option(_lib.OPT_DRY_RUN, prev)
+    with _lib.option(_lib.OPT_DRY_RUN, 1):
+        yield lib
     lib.vpx_set_deterministic(0)
 
 

@@ -11,6 +11,7 @@ Regression: round 4's intermittent abort of the GPU suite (GPUTEST_r04: SIGABRT 
 32 input channels) while `vpx_conv2d_nhwc_fwd_ex` packs with the stage size of the tiling it actually picks (1 group for Co <= 32:
 16-channel stages, 13 chunks each = 26 per 32 channels): the flow generator's 5x5 layers (h2f_conv1 64|96 -> 32, flows_conv
 32 -> 26) wrote 4-12 KB past a torch allocation. `test_trajgru_flow_generator_layers` pins exactly those layers."""
+import contextlib
 import ctypes
 import itertools
 
@@ -31,9 +32,8 @@ def _fake(i):                        # distinct fake tensor addresses far away f
 @pytest.fixture(scope="module")
 def L():
     lib = _lib.lib()
-    prev = lib.vpx_set_option(_lib.OPT_DRY_RUN, 1)
-    yield lib
-    lib.vpx_set_option(_lib.OPT_DRY_RUN, prev)
+    with _lib.option(_lib.OPT_DRY_RUN, 1):
+        yield lib
     lib.vpx_set_deterministic(0)
 
 
@@ -98,6 +98,17 @@ CLSTM_BLOCKS = [(16, 64, 64, 64), (64, 96, 32, 32), (96, 96, 16, 16), (96, 96, 3
                 (16, 64, 128, 128), (64, 96, 64, 64), (3, 8, 12, 10), (3, 64, 67, 83), (4, 8, 16, 16), (8, 8, 8, 8), (12, 12, 4, 4)]
 
 
+# Options of the ConvLSTM sweep, one at a time (inference calls of B <= 32, T > 1). The experiment bits change the route at these shapes:
+# NO_C3 / C3_NARROW where the half-tile grid has at most 256 workgroups (B <= 8 on the 64x64 blocks), HOIST_GEN1 on the small grids,
+# CELL2_FULL_TILE / CELL2X (both wave splits) where cell2_kernel_q takes the step: B = 32 on the 32x32 and 64x64 blocks whose Ch is in 32s.
+E = _lib.Exp
+CLSTM_EXPERIMENTS = (E.NO_C3, E.C3_NARROW, E.HOIST_GEN1, E.CELL2_FULL_TILE, E.CELL2X, E.CELL2X | E.CELL2X_COLSPLIT)
+CLSTM_OPTIONS = ((None, (_lib.OPT_CELL2, 0), (_lib.OPT_CELL2, 2), (_lib.OPT_CELL3, 0), (_lib.OPT_MFMA_SHAPE, 0)) +
+                 tuple((_lib.OPT_EXPERIMENT, e) for e in CLSTM_EXPERIMENTS))
+# ... and with the saved-for-backward reserve as well (the tile form also decides the data gradient's launch; the x form fills the reserve)
+CLSTM_OPTIONS_TRAINING = tuple((_lib.OPT_EXPERIMENT, e) for e in CLSTM_EXPERIMENTS[3:])
+
+
 @pytest.mark.parametrize("det", [0, 1])
 @pytest.mark.parametrize("prec", [0, 1, 2])
 def test_convlstm_seq(L, det, prec):
@@ -106,12 +117,10 @@ def test_convlstm_seq(L, det, prec):
         if B * H * W > 128 * 64 * 64 or (layout == 1 and B > 4) or (k == 5 and B > 4):
             continue
         for save in (0, 1):
-            for opt in (None, (_lib.OPT_CELL2, 0), (_lib.OPT_CELL2, 2), (_lib.OPT_CELL3, 0), (_lib.OPT_EXPERIMENT, 4096), (_lib.OPT_EXPERIMENT, 8192),
-                        (_lib.OPT_EXPERIMENT, 32), (_lib.OPT_MFMA_SHAPE, 0)):
-                if opt is not None and (save or B > 32 or T == 1):
+            for opt in CLSTM_OPTIONS:
+                if opt is not None and (B > 32 or T == 1 or (save and opt not in CLSTM_OPTIONS_TRAINING)):
                     continue
-                prev = L.vpx_set_option(*opt) if opt else None
-                try:
+                with _lib.option(*opt) if opt else contextlib.nullcontext():
                     d = ConvLSTMDesc(B, T, Cin, Ch, H, W, k, k, gate, layout, prec, _lib.FLAG_SAVE_FOR_BWD if save else 0)
                     nb = L.vpx_convlstm_workspace_bytes(ctypes.byref(d))
                     if nb == 0:
@@ -135,14 +144,14 @@ def test_convlstm_seq(L, det, prec):
                         rc = L.vpx_convlstm_seq_fwd(ctypes.byref(d), _fake(1), _fake(2), _fake(3), _fake(4), _fake(5), _fake(6), _fake(7), _fake(8),
                                                     _fake(9), _fake(10), _fake(11), None, 0, ctypes.c_void_p(WS_BASE), nb, None)
                         _ok(L, rc, tag + " fwd (split in/out)")
-                finally:
-                    if opt:
-                        L.vpx_set_option(opt[0], prev)
 
 
 ST_CELLS = [(16, 128, 16, 16, 5), (128, 128, 16, 16, 5), (48, 128, 32, 32, 5), (128, 128, 32, 32, 5), (16, 16, 8, 8, 5), (3, 8, 12, 10, 3),
             (16, 64, 16, 16, 3), (64, 64, 16, 16, 5), (16, 128, 16, 16, 3)]
-ST_EXPERIMENTS = (0, 64, 128, 256, 512, 1024, 2048, 64 | 128 | 256 | 512)
+# (ST_LAST_FP32 changes the route wherever c5 takes the forward: k = 5, Ch in 32s, no LayerNorm)
+ST_EXPERIMENTS = (0, E.ST_WGRAD_GEN1, E.ST_DGRAD_GEN1, E.ST_FWD_GEN1, E.C1_GEN1, E.C5_UNSPLIT, E.C5_NO_KSPLIT,
+                  E.ST_WGRAD_GEN1 | E.ST_DGRAD_GEN1 | E.ST_FWD_GEN1 | E.C1_GEN1, E.ST_LAST_FP32, E.C5_UNSPLIT | E.ST_LAST_FP32)
+DECOUPLE_EXPERIMENTS = (0, E.C1_GEN1)
 
 
 @pytest.mark.parametrize("det", [0, 1])
@@ -152,8 +161,7 @@ def test_stlstm_step(L, det, prec):
     for (Cin, Ch, H, W, k), B, ln, layout, exp in itertools.product(ST_CELLS, (1, 2, 4, 8, 16, 128, 256), (0, 1), (0, 1), ST_EXPERIMENTS):
         if (layout == 1 or ln == 1 or exp) and B > 8:
             continue
-        prev = L.vpx_set_option(_lib.OPT_EXPERIMENT, exp)
-        try:
+        with _lib.experiment(exp):
             for save in (0, 1):
                 for packed in (0, 1):
                     d = STLSTMDesc(B, Cin, Ch, H, W, k, ln, layout, prec, (_lib.FLAG_SAVE_FOR_BWD if save else 0) | (_lib.FLAG_WEIGHTS_PACKED if packed else 0))
@@ -189,16 +197,13 @@ def test_stlstm_step(L, det, prec):
                                 rc = L.vpx_stlstm_wgrad_batch(ctypes.byref(dT), _fake(1), (ctypes.c_void_p * 5)(*[0x400000000000 + i * (1 << 34) for i in range(5)]),
                                                               *[_fake(i) for i in range(25, 30)], ctypes.c_void_p(WS_BASE_ODD), nbb, None)
                                 _ok(L, rc, tag + f" wgrad_batch T={T}", allow_unsupported=False)
-        finally:
-            L.vpx_set_option(_lib.OPT_EXPERIMENT, prev)
 
 
 def test_decouple_tail(L):
     for det in (0, 1):
         L.vpx_set_deterministic(det)
-        for (B, Ch, H, W), prec, exp in itertools.product(((1, 16, 8, 8), (2, 128, 16, 16), (8, 128, 32, 32), (128, 128, 16, 16), (2, 8, 12, 10)), (0, 1, 2), (0, 512)):
-            prev = L.vpx_set_option(_lib.OPT_EXPERIMENT, exp)
-            try:
+        for (B, Ch, H, W), prec, exp in itertools.product(((1, 16, 8, 8), (2, 128, 16, 16), (8, 128, 32, 32), (128, 128, 16, 16), (2, 8, 12, 10)), (0, 1, 2), DECOUPLE_EXPERIMENTS):
+            with _lib.experiment(exp):
                 nb = L.vpx_decouple_workspace_bytes(B, Ch, H, W)
                 rc = L.vpx_decouple_fwd(_fake(1), _fake(2), _fake(3), _fake(4), B, Ch, H, W, prec, ctypes.c_void_p(WS_BASE), nb, None)
                 _ok(L, rc, f"decouple fwd {(B, Ch, H, W)} prec={prec}")
@@ -209,8 +214,6 @@ def test_decouple_tail(L):
                     gm = ctypes.c_void_p(gc.value + B * H * W * Ch * 4) if adjacent else _fake(6)
                     rc = L.vpx_decouple_bwd(dc, dm, _fake(3), _fake(4), gc, gm, _fake(7), B, Ch, H, W, prec, ctypes.c_void_p(WS_BASE_ODD), nb, None)
                     _ok(L, rc, f"decouple bwd {(B, Ch, H, W)} prec={prec} adjacent={adjacent}")
-            finally:
-                L.vpx_set_option(_lib.OPT_EXPERIMENT, prev)
 
 
 # the stage glue of EF-ConvLSTM / EF-TrajGRU (ef_conv_lstm.py:36-65, ef_traj_gru.py:37-44) and PredRNN's action / frame convolutions
@@ -221,14 +224,20 @@ GLUE = [  # (Ci, Co, k, stride, pad, transposed)
 ]
 
 
+# CONVQ_FULL_TILE: the 3x3-halo layers convq takes; GLUE_WGRAD_TAPGROUP: bf16x3 layers with channels in 8s; GLUE_DGRAD_GEN1: layers whose
+# adjoint convq takes (64 -> 64 / 96 -> 96 stride 2 and their transposes on the large batches); NO_C16: the 3x3 stride-1 layers onto 16 channels
+GLUE_EXPERIMENTS = (0, E.CONVQ_FULL_TILE, E.GLUE_WGRAD_TAPGROUP, E.GLUE_DGRAD_GEN1, E.NO_C16)
+# what the sweeps of this file switch on, per family of entry points (tests/test_host_logic.py holds it against the name table)
+SWEPT_EXPERIMENTS = {"convlstm": CLSTM_EXPERIMENTS, "stlstm": ST_EXPERIMENTS, "decouple": DECOUPLE_EXPERIMENTS, "glue": GLUE_EXPERIMENTS}
+
+
 @pytest.mark.parametrize("det", [0, 1])
 def test_stage_glue(L, det):
     L.vpx_set_deterministic(det)
-    for (Ci, Co, k, s, p, tr), (N, H, W), prec, slope, exp in itertools.product(GLUE, GEOS + [(1280, 16, 16), (40, 64, 64)], (0, 1, 2), (0.0, 0.2), (0, 16, 1 << 29)):
+    for (Ci, Co, k, s, p, tr), (N, H, W), prec, slope, exp in itertools.product(GLUE, GEOS + [(1280, 16, 16), (40, 64, 64)], (0, 1, 2), (0.0, 0.2), GLUE_EXPERIMENTS):
         if N * H * W * max(Ci, Co) > 1 << 31 or (exp and prec != 1):
             continue
-        prev = L.vpx_set_option(_lib.OPT_EXPERIMENT, exp)
-        try:
+        with _lib.experiment(exp):
             d = ConvDesc(N, H, W, Ci, Co, k, k, s, p, tr, slope, prec, 0, 0)
             ho, wo = ctypes.c_int(0), ctypes.c_int(0)
             if L.vpx_conv2d_ex_out_shape(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)) != OK:
@@ -257,8 +266,6 @@ def test_stage_glue(L, det):
                     rc = L.vpx_conv2d_ex_bwd_ex(ctypes.byref(d), _fake(1), _fake(10), _fake(2), _fake(4), _fake(6), None, _fake(8), None,
                                                 ctypes.c_void_p(WS_BASE_ODD), nbb, None)
                     _ok(L, rc, tag + " bwd_ex (dw only)")
-        finally:
-            L.vpx_set_option(_lib.OPT_EXPERIMENT, prev)
 
 
 def test_trajgru_sequence(L):

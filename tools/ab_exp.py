@@ -1,16 +1,16 @@
-"""A/B timing of kernel experiment bits (vpx_set_option(VPX_OPT_EXPERIMENT), MODES env, default "0,1,2,3") — derived from ab_shape.py: the two MFMA shapes of the second-generation main loop inside ONE process (vpx_set_option(VPX_OPT_MFMA_SHAPE)),
+"""A/B timing of kernel experiment bits (vpx_set_option(VPX_OPT_EXPERIMENT); MODES env: numbers or vp_suite_amd._lib.Exp names
+joined by |, default "0,CELL2_FULL_TILE,CELL2_FULL_TILE|CELL2_NO_STAGGER") — derived from ab_shape.py: the two MFMA shapes of the second-generation main loop inside ONE process (vpx_set_option(VPX_OPT_MFMA_SHAPE)),
 interleaved rounds, random data, per block shape: forward steps, and MODE=train a forward + backward of the block.
 BB = per-GPU batch (default 128)."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import vp_suite_amd as v
-L = v._lib.lib()
 dev = torch.device("cuda:0")
 shapes = [(64, 64, 64, 64), (16, 64, 64, 64), (64, 96, 32, 32), (96, 96, 32, 32), (96, 64, 64, 64)]
 B, T = int(os.environ.get("BB", 128)), 6
 train = os.environ.get("MODE", "infer") == "train"
-MODES = [int(x) for x in os.environ.get("MODES", "0,1,2,3").split(",")]
+MODES = [v._lib.exp_bits(x) for x in os.environ.get("MODES", "0,CELL2_FULL_TILE,CELL2_FULL_TILE|CELL2_NO_STAGGER").split(",")]
 PREC = os.environ.get("PREC", "bf16x3")   # bf16: inference only (the plain form of the fused cell)
 ZERO = os.environ.get("ZERO", "0") == "1"  # all-zero operands: the clock the chip holds without data toggling (MI355X_MICROARCH.md, DVFS give-back 1)
 res, data = {}, {}
@@ -35,14 +35,14 @@ def once(s):
 for rnd in range(5):
     for s in shapes:
         for mode in MODES:
-            L.vpx_set_option(v._lib.OPT_EXPERIMENT, mode)
-            once(s)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(3):
+            with v._lib.experiment(mode):
                 once(s)
-            torch.cuda.synchronize()
-            res.setdefault((s, mode), []).append((time.perf_counter() - t0) / 3)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(3):
+                    once(s)
+                torch.cuda.synchronize()
+                res.setdefault((s, mode), []).append((time.perf_counter() - t0) / 3)
 for s in shapes:
     Cin, Ch, H, W = s
     fl = 2.0 * 4 * Ch * (Cin + Ch * (T - 1) / T) * 9 * H * W * B * T * (3 if train else 1)

@@ -1,5 +1,5 @@
 """Developer script (GPU box): where does the convq data gradient of a glue layer differ from torch? Error by border / position,
-with the first-generation launch (VPX_OPT_EXPERIMENT bit 14) next to it."""
+with the first-generation launch (VPX_EXP_GLUE_DGRAD_GEN1) next to it."""
 import sys
 import numpy as np
 import torch
@@ -10,7 +10,7 @@ import vp_suite_amd as vpx
 torch.manual_seed(0)
 L = vpx._lib.lib()
 CASES = [(False, 64, 64, 3, 2, 1, 64, 64, 24), (False, 64, 64, 3, 2, 1, 32, 32, 24), (True, 96, 96, 4, 2, 1, 16, 16, 24), (False, 64, 96, 3, 2, 1, 33, 47, 24)]
-for bit in (0, 16384, 0):
+for bit in (0, vpx._lib.Exp.GLUE_DGRAD_GEN1, 0):
     L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, bit)
     print("==== experiment bits", bit)
     for (tr, Ci, Co, k, s, p, H, W, n) in CASES:

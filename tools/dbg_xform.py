@@ -7,12 +7,11 @@ import vp_suite_amd as vpx
 import test_gpu_cell2 as t
 tag = os.environ.get("TAG", "plain_s7_many_tiles")
 prec = os.environ.get("PREC", "bf16x3")
-bits = int(os.environ.get("EXP", "32768"))
+bits = vpx._lib.exp_bits(os.environ.get("EXP", "CELL2X"))
 L = vpx._lib.lib()
 L.vpx_set_option(vpx._lib.OPT_CELL2, 2)
 L.vpx_set_option(vpx._lib.OPT_MFMA_SHAPE, 1)
 with torch.no_grad():
-    L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, 0)
     o1, h1, c1, _ = t._run(vpx, tag, grads=False, precision=prec)
     o1b, _, c1b, _ = t._run(vpx, tag, grads=False, precision=prec)
     print("q vs q equal:", torch.equal(o1, o1b), torch.equal(c1, c1b))

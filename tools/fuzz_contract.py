@@ -21,7 +21,9 @@ OKS = (0, -1, -4)
 findings = []
 chs = [1, 2, 3, 4, 5, 7, 8, 12, 16, 20, 24, 26, 31, 32, 33, 40, 48, 64, 72, 96, 100, 128, 160, 192, 256, 288]
 dims = [1, 2, 3, 4, 5, 7, 8, 9, 12, 15, 16, 17, 20, 24, 31, 32, 33, 47, 48, 64, 67, 83, 96, 128]
-EXP = [0, 1, 4, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384, 64 | 128 | 256 | 512, 1024 | 2048]
+E = _lib.Exp
+EXP = [0, E.CELL2_NO_STAGGER, E.CELL2_FULL_TILE, E.CONVQ_FULL_TILE, E.HOIST_GEN1, E.ST_WGRAD_GEN1, E.ST_DGRAD_GEN1, E.ST_FWD_GEN1, E.C1_GEN1, E.C5_UNSPLIT,
+       E.C5_NO_KSPLIT, E.NO_C3, E.C3_NARROW, E.GLUE_DGRAD_GEN1, E.ST_WGRAD_GEN1 | E.ST_DGRAD_GEN1 | E.ST_FWD_GEN1 | E.C1_GEN1, E.C5_UNSPLIT | E.C5_NO_KSPLIT]
 
 
 def note(what, rc):

@@ -1,5 +1,5 @@
 """Developer tool (GPU): random PredRNN-V2 training passes — deferred weight gradients (stw_kernel over a whole pass: 1..32 K slices, both block
-decodes) against the first-generation per-step weight gradients (VPX_OPT_EXPERIMENT bit 6), every parameter gradient. usage: fuzz_stw.py [cases] [seed]"""
+decodes) against the first-generation per-step weight gradients (VPX_EXP_ST_WGRAD_GEN1), every parameter gradient. usage: fuzz_stw.py [cases] [seed]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -12,7 +12,6 @@ from golden_util import fill_state_dict_, name_seed, seeded_rand
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 5)
-L = vpx._lib.lib()
 lp = PredictionLossProvider({"device": "cuda", "losses_and_scales": {"mse": 1.0}})
 worst_all = 0.0
 for case in range(n_cases):
@@ -28,8 +27,7 @@ for case in range(n_cases):
     frames = seeded_rand((B, Ttot, c, hw, hw), name_seed(f"fuzz_stw.{case}")).cuda()
     res = {}
     for first_generation in (False, True):
-        prev = L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, 64 if first_generation else 0)
-        try:
+        with vpx._lib.experiment(vpx._lib.Exp.ST_WGRAD_GEN1 if first_generation else 0):
             m = MODEL_CLASSES["predrnn-pp"]("cuda", **kw)
             fill_state_dict_(m, name_seed(f"fuzz_stw.model.{case}"))
             m = m.to("cuda")
@@ -38,8 +36,6 @@ for case in range(n_cases):
             loss = m.training_loss(frames, frames[:, Ttot - P:], P, lp)
             loss.backward()
             torch.cuda.synchronize()
-        finally:
-            L.vpx_set_option(vpx._lib.OPT_EXPERIMENT, prev)
         named = dict(m.named_parameters())
         res[first_generation] = (float(loss.detach()), {k: named[k].grad.detach().cpu().numpy() for k in sorted(named)})
         del m, loss

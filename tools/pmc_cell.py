@@ -5,7 +5,7 @@ import torch
 import vp_suite_amd as v
 dev = torch.device("cuda:0")
 if os.environ.get("EXP"):
-    v._lib.lib().vpx_set_option(v._lib.OPT_EXPERIMENT, int(os.environ["EXP"]))
+    v._lib.lib().vpx_set_option(v._lib.OPT_EXPERIMENT, v._lib.exp_bits(os.environ["EXP"]))
 B, T = int(os.environ.get("BB", 32)), 4
 Cin, Ch, H, W = [int(t) for t in os.environ.get('SHAPE', '64,64,64,64').split(',')]
 x = v.ops.to_channels_last(torch.rand(B, T, Cin, H, W, device=dev))

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs ON THE GPU BOX: separate --pmc passes (kernel-trace only) over tools/pmc_cell.py for the cell kernel selected by
-# EXP (bits of VPX_OPT_EXPERIMENT); BB = batch. Output: $OUT/summary.txt (OUT below)
+# EXP (VPX_OPT_EXPERIMENT: numbers or names of vp_suite_amd._lib.Exp joined by |); BB = batch. Output: $OUT/summary.txt (OUT below)
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 TAG=${1:-gen2}

@@ -2,7 +2,9 @@
 pointers (tensor.data_ptr()), sizes and the current HIP stream handle.
 
 There is NO CPU fallback: if the shared library is missing or fails to load, every op raises."""
+import contextlib
 import ctypes
+import enum
 import os
 import subprocess
 
@@ -29,6 +31,33 @@ OPT_CELL3 = 2
 OPT_EXPERIMENT = 4
 OPT_DRY_RUN = 5      # host-side work only, no HIP call (tests/test_workspace_contract.py)
 OPT_MFMA_SHAPE = 3   # 0: v_mfma_f32_32x32x16_bf16, 1: v_mfma_f32_16x16x32_bf16 in the second-generation kernels' main loop
+
+
+class Exp(enum.IntFlag):
+    """Values of OPT_EXPERIMENT: the VPX_EXP_* table of include/vpx.h, name for name (tests/test_host_logic.py holds the two together).
+    Each bit switches one kernel form on in place of the product's; 0 is the product."""
+    CELL2_FULL_TILE = 4
+    CONVQ_FULL_TILE = 16
+    HOIST_GEN1 = 32
+    ST_WGRAD_GEN1 = 64
+    ST_DGRAD_GEN1 = 128
+    ST_FWD_GEN1 = 256
+    C1_GEN1 = 512
+    C5_UNSPLIT = 1024
+    C5_NO_KSPLIT = 2048
+    NO_C3 = 4096
+    C3_NARROW = 8192
+    GLUE_DGRAD_GEN1 = 16384
+    CELL2X = 32768
+    CELL2X_COLSPLIT = 65536
+    ST_LAST_FP32 = 1 << 27
+    NO_C16 = 1 << 28
+    GLUE_WGRAD_TAPGROUP = 1 << 29
+    # diagnostics inside cell2_kernel_q; PLACEMENT takes a distance in bits 8-19 (value | D << 8): never with a selection bit of that range
+    CELL2_NO_STAGGER = 1
+    CELL2_PLACEMENT = 8
+    CELL2_DIAG_MASK = 1 | 8 | 0xfff << 8
+
 
 class ConvLSTMDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("B", "T", "Cin", "Ch", "H", "W", "kh", "kw", "gate_order", "layout",
@@ -224,6 +253,30 @@ def lib():
             fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
+
+
+@contextlib.contextmanager
+def option(opt: int, value: int):
+    """vpx_set_option(opt, value) for a block; the previous value comes back on the way out, exception or not."""
+    prev = lib().vpx_set_option(opt, int(value))
+    try:
+        yield prev
+    finally:
+        lib().vpx_set_option(opt, prev)
+
+
+def experiment(bits: int):
+    """option(OPT_EXPERIMENT, bits): an OR of Exp members (0 = the product's kernels)."""
+    return option(OPT_EXPERIMENT, bits)
+
+
+def exp_bits(text: str) -> int:
+    """An OPT_EXPERIMENT value as the tools take it from the command line: Exp names and / or numbers joined by '|'
+    ("0", "CELL2X|CELL2X_COLSPLIT", "4096")."""
+    bits = 0
+    for t in text.split("|"):
+        bits |= Exp[t.strip()] if t.strip() in Exp.__members__ else int(t, 0)
+    return int(bits)
 
 
 def check(rc: int, what: str):

@@ -910,11 +910,11 @@ __global__ __launch_bounds__(64 * NW, 2) void cell2_kernel_q(const Cell2Plan P, 
 // Half tile (cell2_kernel_q<.., 4>: 16x16-pixel tiles, two workgroups per CU) or the 32x16 tile? Measured (tools/ab_exp.py,
 // B=128, five block shapes): the half tile is +1.5..7 % per forward step and +1.3..3 % per block forward + backward (one shape
 // -0.5 %) — 14 % fewer cycles, of which the chip takes 10 % back as clock (1.96 -> 1.77 GHz: MFMA busy 60 -> 69 %, power-bound).
-// VPX_OPT_EXPERIMENT bit 2 forces the full tile (A/B runs, tests).
+// VPX_EXP_CELL2_FULL_TILE forces the full tile (A/B runs, tests).
 static bool cell2_half_tile(const Cell2Plan& p, bool ragged_ok) {
     if (!ragged_ok && (p.H & 15) != 0) return false;   // the fused step's vector epilogue wants tiles inside the image
     if (!ragged_ok && (p.H & 31) != 0) return true;    // ... and 32-row tiles would not be
-    return !(g_experiment & 4);
+    return !exp_on(VPX_EXP_CELL2_FULL_TILE);
 }
 
 template <class Epi, bool ALLG>
@@ -932,7 +932,7 @@ static hipError_t launch_cell2_t(const Cell2Plan& plan, const Epi& epi, hipStrea
     Cell2Plan p = plan;
     p.grid_m = plan.B * plan.tiles_x * plan.tiles_y;
     if (plan.qform) {
-        p._q = g_experiment;
+        p._q = g_experiment & VPX_EXP_CELL2_DIAG_MASK;   // the kernel's two diagnostics and nothing else of the option word
         if (plan.plain || cell2_half_tile(p, std::is_same<Epi, Conv2Epi>::value)) {
             p.tiles_y = (p.H + 15) / 16;
             p.grid_m = p.B * p.tiles_x * p.tiles_y;

@@ -376,8 +376,8 @@ __global__ __launch_bounds__(512, 4) void cell2_kernel_x(const Cell2Plan P, cons
 // whole 16x16 tiles, whole 32-channel N tiles) and set tiles_y / grid_m for 16-row tiles
 hipError_t launch_cell2x(const Cell2Plan& p_in, const ConvLSTMStepArgs& ea, void* h_sp, long long h_sp_bstride, hipStream_t s) {
     // split: 0 = columns, 1 = rows. Default: rows for both precisions (bf16x3: the column split spills fragment registers inside the loop at
-    // 128 registers; plain bf16: the row split's full-line epilogue measured faster, profiles/r06_cell2x_ab.txt). VPX_OPT_EXPERIMENT bit 16 = columns.
-    const int split = (g_experiment & 65536) ? 0 : 1;
+    // 128 registers; plain bf16: the row split's full-line epilogue measured faster, profiles/r06_cell2x_ab.txt). VPX_EXP_CELL2X_COLSPLIT = columns.
+    const int split = exp_on(VPX_EXP_CELL2X_COLSPLIT) ? 0 : 1;
     constexpr int LDS8 = CQGeom<4>::LDS;   // 80 KiB: two workgroups per CU
     static bool attr_set = false;
     if (!attr_set) {

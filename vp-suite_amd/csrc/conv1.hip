@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void c1_kernel(const C1Args a) {
 }
 
 bool c1_applicable(const C1Args& a, int prec) {
-    if (prec != VPX_PREC_BF16X3 || (g_experiment & 512)) return false;   // VPX_OPT_EXPERIMENT bit 9: the implicit-GEMM kernel (A/B runs, tests)
+    if (prec != VPX_PREC_BF16X3 || exp_on(VPX_EXP_C1_GEN1)) return false;   // VPX_EXP_C1_GEN1: the implicit-GEMM kernel (A/B runs, tests)
     const int K = a.xc[0] + a.xc[1];
     if ((a.xc[0] & 31) || (a.xc[1] & 31) || a.xc[0] < 32) return false;
     if (!((a.Co == 128 && K == 256) || (a.Co == 256 && K == 128) || (a.Co == 128 && K == 128))) return false;

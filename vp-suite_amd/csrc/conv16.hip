@@ -187,7 +187,7 @@ __global__ __launch_bounds__(512, 2) void c16_kernel(const C16Args a) {
 
 // the layers this kernel takes: bf16x3, 3x3, stride 1, pad 1 (plain or transposed), 16 output channels, 16 / 32 / 48 / 64 input channels
 bool c16_applicable(const vpx_conv_desc* d) {
-    if (g_experiment & (1 << 28)) return false;   // VPX_OPT_EXPERIMENT bit 28: the first-generation kernel (A/B runs, tests)
+    if (exp_on(VPX_EXP_NO_C16)) return false;   // VPX_EXP_NO_C16: the first-generation kernel (A/B runs, tests)
     return d->precision == VPX_PREC_BF16X3 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->Co == 16 &&
            (d->Ci & 15) == 0 && d->Ci >= 16 && d->Ci <= 64;
 }

@@ -618,7 +618,7 @@ int ex_adjoint(const vpx_conv_desc* d, const ExGeo& g, vpx_conv_desc& a) {
 
 // weight gradient on split copies of x and dy (wgrad2_kernel's glue form): bf16x3 on the 16x16x32 shape, channel counts in whole groups of 8
 static bool ex_wgrad_split(const vpx_conv_desc* d) {
-    return !(g_experiment & (1 << 29)) && d->precision == VPX_PREC_BF16X3 && g_mfma_shape == 1 && (d->Ci & 7) == 0 && (d->Co & 7) == 0 &&
+    return !exp_on(VPX_EXP_GLUE_WGRAD_TAPGROUP) && d->precision == VPX_PREC_BF16X3 && g_mfma_shape == 1 && (d->Ci & 7) == 0 && (d->Co & 7) == 0 &&
            d->kh <= 2 * d->stride + 1 && d->kw <= 2 * d->stride + 1 && d->kh * d->kw > 1 &&
            !(!d->transposed && wgrad_small_applicable(d->Co, d->Ci, d->kh, d->kw, d->stride, d->pad));
 }
@@ -646,9 +646,9 @@ extern "C" {
 // Round 5: the data gradient of a glue layer = its adjoint layer on dy. Where that adjoint is a layer the schedule-driven K = 32 kernel
 // (convq) takes — the same rule as in the forward: bf16x3, >= 64 output channels, a grid that fills the chip — it runs THERE: the pass
 // that scales dy by LeakyReLU' (and sums the bias gradient) writes the scaled gradient once more in the split operand format.
-// VPX_OPT_EXPERIMENT bit 14 keeps the first-generation launch (A/B runs, tests).
+// VPX_EXP_GLUE_DGRAD_GEN1 keeps the first-generation launch (A/B runs, tests).
 static bool ex_bwd_q(const vpx_conv_desc* d, const vpx_conv_desc* a, ConvQProblem& pr) {
-    if ((g_experiment & 16384) || (d->Co & 7)) return false;
+    if (exp_on(VPX_EXP_GLUE_DGRAD_GEN1) || (d->Co & 7)) return false;
     const ExGeo ga{d->H, d->W};
     return exq_preferred(a, ga, pr) && convq_wpk_bytes(pr) != 0;
 }

@@ -456,9 +456,9 @@ struct QBuild {
     int halo, NTS, nw;
 };
 
-// waves per workgroup: 4 = the half tile (two workgroups per CU), 3x3-halo layers only; experiment bit 4 keeps the 32x16 tile
+// waves per workgroup: 4 = the half tile (two workgroups per CU), 3x3-halo layers only; VPX_EXP_CONVQ_FULL_TILE keeps the 32x16 tile
 int convq_pick_nw(const ConvQProblem& pr) {
-    if (g_experiment & 16) return 8;   // VPX_OPT_EXPERIMENT bit 4: the 32x16 tile (A/B runs, tests)
+    if (exp_on(VPX_EXP_CONVQ_FULL_TILE)) return 8;   // VPX_EXP_CONVQ_FULL_TILE: the 32x16 tile (A/B runs, tests)
     return pr.halo == 2 ? 4 : 8;
 }
 

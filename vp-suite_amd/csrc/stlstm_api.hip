@@ -37,7 +37,7 @@ static inline int c5f_nt_o(const vpx_stlstm_desc* d) {
     return mt * ((d->Ch + 63) / 64) < 384 ? 2 : 4;
 }
 
-// VPX_OPT_EXPERIMENT bit 8 keeps the first-generation forward launches (A/B runs, tests)
+// VPX_EXP_ST_FWD_GEN1 keeps the first-generation forward launches (A/B runs, tests)
 // Grid rule (measured, tools/ab_predrnn.py, predrnn-pp inference, ms per forward c5 vs first generation): 16x16 maps B = 8 / 16 / 32 / 64 /
 // 128: 23.5 / 23.7 / 24.4 / 30.5 / 53.8 vs 13.7 / 14.1 / 17.1 / 26.9 / 58.5; 32x32 maps (128x128x3, 4 layers, 10 -> 30) B = 4 / 8 / 16:
 // 72.5 / 78.1 / 90.9 vs 45.0 / 53.0 / 83.5 — a c5 workgroup runs its whole K (200 steps of 96 MFMAs) on one CU, the first generation
@@ -46,15 +46,15 @@ static inline int c5f_nt_o(const vpx_stlstm_desc* d) {
 // ms per forward unsplit vs K-split: B = 40 30.2 vs 28.9, 48 30.7 vs 33.2, 56 32.1 vs 34.7, 64 33.5 vs 36.2, 80 47.1 vs 50.4); the backward
 // launches keep 96 (training step B = 48 221 vs 211 ms, 64 246 vs 242, 80 309.5 vs 309.1).
 static bool c5_shape_ok(const vpx_stlstm_desc* d) {
-    return d->k == 5 && d->precision == VPX_PREC_BF16X3 && !(d->Ch & 31) && !(d->Cin & 7) && !d->layer_norm && !(g_experiment & 256);
+    return d->k == 5 && d->precision == VPX_PREC_BF16X3 && !(d->Ch & 31) && !(d->Cin & 7) && !d->layer_norm && !exp_on(VPX_EXP_ST_FWD_GEN1);
 }
 constexpr int C5_MIN_TILES = 48;
 bool c5_fwd_applicable(const vpx_stlstm_desc* d) {
     const long long mt = (long long)d->B * ((d->H + 15) / 16) * ((d->W + 15) / 16);
-    return c5_shape_ok(d) && (mt >= C5_MIN_TILES || (g_experiment & 1024));   // (bit 10 forces the unsplit form on small grids: tests)
+    return c5_shape_ok(d) && (mt >= C5_MIN_TILES || exp_on(VPX_EXP_C5_UNSPLIT));   // (VPX_EXP_C5_UNSPLIT forces the unsplit form on small grids: tests)
 }
-// below the bar: K-split jobs (VPX_OPT_EXPERIMENT bit 11 keeps the first-generation launches there)
-bool c5k_fwd_applicable(const vpx_stlstm_desc* d) { return c5_shape_ok(d) && !c5_fwd_applicable(d) && !(g_experiment & 2048); }
+// below the bar: K-split jobs (VPX_EXP_C5_NO_KSPLIT keeps the first-generation launches there)
+bool c5k_fwd_applicable(const vpx_stlstm_desc* d) { return c5_shape_ok(d) && !c5_fwd_applicable(d) && !exp_on(VPX_EXP_C5_NO_KSPLIT); }
 // K chunks so that the launch has about 448 workgroups, every chunk at least four 8-channel stages (25 steps), at most six chunks
 static int c5k_chunks(long long wgs1, int S8) {
     constexpr long long C5K_TARGET = 448;   // workgroups the chunked launch aims at
@@ -446,9 +446,9 @@ int vpx_stlstm_step_fwd_ex(const vpx_stlstm_desc* d, const float* x, const float
     c1.npix = (long long)B * (long long)HW;
     c1.w = Wlast; c1.w_sn = 2 * Ch; c1.w_sc = 1;
     c1.y[0] = lc; c1.yld[0] = Ch; c1.ysplit = Ch; c1.Co = Ch;
-    if ((L.c5 || L.c5k) && cn_sp && mn_sp && !(g_experiment & (1 << 27))) {
+    if ((L.c5 || L.c5k) && cn_sp && mn_sp && !exp_on(VPX_EXP_ST_LAST_FP32)) {
         // the gate stage left c_new / m_new in the operand format as well: read THOSE (no fp32 -> (hi, lo) conversion in the kernel; round 6).
-        // VPX_OPT_EXPERIMENT bit 27 keeps the fp32 sources (tests, A/B)
+        // VPX_EXP_ST_LAST_FP32 keeps the fp32 sources (tests, A/B)
         c1.x[0] = reinterpret_cast<const float*>(cn_sp); c1.x[1] = reinterpret_cast<const float*>(mn_sp); c1.x_split = 1;
     }
     if (c1_applicable(c1, d->precision)) {

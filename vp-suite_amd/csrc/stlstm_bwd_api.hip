@@ -29,9 +29,9 @@ struct STBwdLayout {
 };
 constexpr int C5_NT = 4;   // 64-column N tiles: 6 jobs x 128 pixel tiles of unequal K balance over the chip (see convq.hip)
 
-// VPX_OPT_EXPERIMENT bit 6 keeps the first-generation weight-gradient launches (A/B runs, tests)
+// VPX_EXP_ST_WGRAD_GEN1 keeps the first-generation weight-gradient launches (A/B runs, tests)
 bool stw_applicable(const vpx_stlstm_desc* d) {
-    return d->k == 5 && d->precision == VPX_PREC_BF16X3 && !(d->Ch & 7) && !(d->Cin & 7) && !d->layer_norm && !(g_experiment & 64);
+    return d->k == 5 && d->precision == VPX_PREC_BF16X3 && !(d->Ch & 7) && !(d->Cin & 7) && !d->layer_norm && !exp_on(VPX_EXP_ST_WGRAD_GEN1);
 }
 
 int mk_dg(STBwdLayout::DG& g, const int* segC, int nseg, int k, int n_out, int prec, long long m_tiles) {
@@ -81,14 +81,14 @@ int st_bwd_layout(const vpx_stlstm_desc* d, STBwdLayout& L) {
             if (need > L.slab_floats) L.slab_floats = need;
         }
     }
-    // VPX_OPT_EXPERIMENT bit 7 keeps the first-generation data-gradient launches (A/B runs, tests)
+    // VPX_EXP_ST_DGRAD_GEN1 keeps the first-generation data-gradient launches (A/B runs, tests)
     // From 96 pixel tiles of 16x16 on, a job runs its whole K (the grid rule of the forward launches, stlstm_api.hip; measured training
     // step at 16x16 maps, unsplit c5 vs first-generation K-split data gradients: B = 8 130 vs 78 ms, B = 32 165 vs 136 ms, B = 128 361
-    // vs ~405 ms); below, the K of every slot is cut into chunks (bit 11 of VPX_OPT_EXPERIMENT keeps the first generation there).
+    // vs ~405 ms); below, the K of every slot is cut into chunks (VPX_EXP_C5_NO_KSPLIT keeps the first generation there).
     const long long mt16 = (long long)d->B * ((d->H + 15) / 16) * ((d->W + 15) / 16);
     constexpr int C5B_MIN_TILES = 96;
-    const bool big = mt16 >= C5B_MIN_TILES || (g_experiment & 1024);
-    L.c5 = L.stw && !(g_experiment & 128) && (big || !(g_experiment & 2048));
+    const bool big = mt16 >= C5B_MIN_TILES || exp_on(VPX_EXP_C5_UNSPLIT);
+    L.c5 = L.stw && !exp_on(VPX_EXP_ST_DGRAD_GEN1) && (big || !exp_on(VPX_EXP_C5_NO_KSPLIT));
     if (L.c5) {
         const int K[5] = {Ch, Ch, 7 * Ch, 4 * Ch, 3 * Ch}, Co[5] = {Ch, Ch, Cin, Ch, Ch};
         const int ks_small[5] = {4, 4, 6, 3, 3}, ks_mid[5] = {2, 2, 4, 2, 2};

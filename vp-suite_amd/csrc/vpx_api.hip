@@ -127,9 +127,9 @@ size_t vpx_convlstm_reserve_bytes(const vpx_convlstm_desc* d) {
 // launches in which the half tile of cell2_kernel_q leaves most of the chip empty (B = 4 on 64x64 maps: 128 workgroups of four waves,
 // one wave per SIMD on half the CUs, each running 36 steps of 96 MFMAs plus a 25 k-cycle epilogue alone). Halving / quartering the N
 // tile doubles / quadruples the waves and shortens each wave's critical path. Inference only (it does not write the saved gates).
-// VPX_OPT_EXPERIMENT bit 12 keeps the half tile there (A/B runs, tests).
+// VPX_EXP_NO_C3 keeps the half tile there (A/B runs, tests).
 static int c3_nt(const vpx_convlstm_desc* d, const ConvLSTMLayout& L) {   // 0: not applicable; else column tiles per N tile (4 | 2)
-    if (!L.v2 || !cell2_q_applicable(d) || d->precision != VPX_PREC_BF16X3 || (d->flags & VPX_FLAG_SAVE_FOR_BWD) || (g_experiment & 4096)) return 0;
+    if (!L.v2 || !cell2_q_applicable(d) || d->precision != VPX_PREC_BF16X3 || (d->flags & VPX_FLAG_SAVE_FOR_BWD) || exp_on(VPX_EXP_NO_C3)) return 0;
     if ((d->Cin & 7) || (d->Ch & 15)) return 0;
     const long long mt = (long long)d->B * ((d->H + 15) / 16) * ((d->W + 15) / 16);
     // Measured (round 4, B = 4, 64x64 maps, Ch = 64: 128 half-tile workgroups of 39 us). First pass: 32-column tiles (512 workgroups) 34 us,
@@ -141,7 +141,7 @@ static int c3_nt(const vpx_convlstm_desc* d, const ConvLSTMLayout& L) {   // 0: 
     // c3 up to 256 half-tile workgroups (128 in the first pass of the round, for the 32-column tiles).
     constexpr int C3_MAX = 256;
     if (mt * L.n_tiles > C3_MAX) return 0;
-    return (g_experiment & 8192) ? 2 : 4;   // VPX_OPT_EXPERIMENT bit 13: the 32-column tiles (tests, A/B runs)
+    return exp_on(VPX_EXP_C3_NARROW) ? 2 : 4;   // VPX_EXP_C3_NARROW: the 32-column tiles (tests, A/B runs)
 }
 
 static size_t cell2_wpk_bytes(const vpx_convlstm_desc* d, const ConvLSTMLayout& L) {
@@ -196,7 +196,7 @@ int vpx_convlstm_writes_split_output(const vpx_convlstm_desc* d) {   // the seco
 // 40 frames 64 -> 4x96 channels at 32x32: 84 -> ~25 us against the first-generation launch.
 static bool hoist_q_problem(const vpx_convlstm_desc* d, ConvQProblem& pr) {
     memset(&pr, 0, sizeof(pr));
-    if (g_experiment & 32) return false;   // VPX_OPT_EXPERIMENT bit 5: the first-generation launch (tests, A/B)
+    if (exp_on(VPX_EXP_HOIST_GEN1)) return false;   // VPX_EXP_HOIST_GEN1: the first-generation launch (tests, A/B)
     if (d->precision != VPX_PREC_BF16X3 || d->kh != 3 || d->kw != 3 || (d->Cin & 15) || d->Cin < 16 || d->layout != VPX_LAYOUT_NHWC) return false;
     pr.N = d->B * d->T; pr.H = d->H; pr.W = d->W; pr.halo = 2;
     pr.nseg = 1;

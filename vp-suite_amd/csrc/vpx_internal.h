@@ -189,7 +189,8 @@ struct Cell2Seg { const char* sp; long long bstride; int C; int _pad; };   // sp
 // arithmetic on these fields (a table walk cost an s_load + s_waitcnt lgkmcnt(0) per copy inside the MFMA loop).
 struct Cell2Plan {
     int B, H, W, tiles_x, tiles_y, n_tiles, nx, nh, hs_off, chunks_total, grid_m, _p;
-    int qform, _q;            // 1: the 16x16x32 main loop (cell2_kernel_q); wpk / chunks_total then describe K = 32 chunks (below)
+    int qform, _q;            // 1: the 16x16x32 main loop (cell2_kernel_q); wpk / chunks_total then describe K = 32 chunks (below).
+                              // _q: the option word under VPX_EXP_CELL2_DIAG_MASK (the kernel's diagnostics; launch_cell2_t sets it)
     int plain;                // q form, half tile: VPX_PREC_BF16 (hi parts only, one MFMA per product)
     int n_groups, gpt;        // conv2 only: 32-column output groups in total / per N tile (the last tile may hold fewer)
     Cell2Seg seg[2];
@@ -214,14 +215,15 @@ size_t cell2_packed_bytes(int n_tiles, int chunks_total);   // 32x32x16 form: ch
 size_t cell2_packed_bytes_q(int n_tiles, int S);             // q form: cell2_qchunks(S) chunks of 16 KiB
 // The library never reads the process environment: kernel selection depends on the descriptor and on vpx_set_option /
 // vpx_set_deterministic only. The tuning values of the selection rules are constants next to the rules they feed.
-extern int g_experiment;   // vpx_api.hip: bits of kernel experiments in flight (vpx_set_option(VPX_OPT_EXPERIMENT)); 0 in the product
+extern int g_experiment;   // vpx_api.hip: VPX_EXP_* bits of kernel experiments in flight (vpx_set_option(VPX_OPT_EXPERIMENT)); 0 in the product
+static inline bool exp_on(int bit) { return (g_experiment & bit) != 0; }   // the one reader of the selection bits
 extern int g_mfma_shape;   // vpx_api.hip: 0 / 1 (vpx_set_option(VPX_OPT_MFMA_SHAPE)), default 1
 hipError_t launch_cell2(const Cell2Plan& plan, const ConvLSTMStepArgs& ea, void* h_sp, long long h_sp_bstride, hipStream_t s);
 // the same step on the eight-wave half tile (cell2x.hip, round 6: 64-register wave tiles, four waves per SIMD); plan.qform launches only
-// (maps in whole 16x16 tiles, whole 32-channel N tiles), tiles_y / grid_m set for 16-row tiles. VPX_OPT_EXPERIMENT bit 15 selects it
+// (maps in whole 16x16 tiles, whole 32-channel N tiles), tiles_y / grid_m set for 16-row tiles. VPX_EXP_CELL2X selects it
 // (development state: the four-wave half tile stays the default until the A/B says otherwise)
 hipError_t launch_cell2x(const Cell2Plan& plan, const ConvLSTMStepArgs& ea, void* h_sp, long long h_sp_bstride, hipStream_t s);
-static inline bool cell2x_selected() { return (g_experiment & 32768) != 0; }
+static inline bool cell2x_selected() { return exp_on(VPX_EXP_CELL2X); }
 // c16 (conv16.hip): 3x3 stride-1 'same' (transposed or not) layers with 16 output channels on split input, weights resident in registers
 bool c16_applicable(const ::vpx_conv_desc* d);
 size_t c16_wpk_bytes(const ::vpx_conv_desc* d);

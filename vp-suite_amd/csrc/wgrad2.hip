@@ -476,7 +476,7 @@ hipError_t launch_wgrad2(const WgradArgs& a_in, int max_slices, int* used_slices
 
 // ---- glue form (wgrad2_kernel<true, true>): one stride residue of a stage-glue layer's weight gradient, both operands pre-split ----
 bool wgrad2g_applicable(const WgradArgs& a) {
-    if (g_experiment & (1 << 29)) return false;   // VPX_OPT_EXPERIMENT bit 29: the tap-group kernel on fp32 operands (A/B runs, tests)
+    if (exp_on(VPX_EXP_GLUE_WGRAD_TAPGROUP)) return false;   // VPX_EXP_GLUE_WGRAD_TAPGROUP: the tap-group kernel on fp32 operands (A/B runs, tests)
     if (g_mfma_shape != 1 || a.prec != VPX_PREC_BF16X3 || !a.g_sp || !a.x_sp || a.T != 1) return false;
     const int taps = a.kh * a.kw;
     if (taps < 2 || a.kh > 3 || a.kw > 3) return false;
