@@ -381,3 +381,51 @@ def test_x_form_training_path_vs_oracle(vpx, cell2_switch, shape_switch, experim
         assert _relmax(out, ro) < 2e-5
         for k in rg:
             assert _relmax(g[k], rg[k]) < 5e-5, (bits, k)
+
+
+# ---- a workspace kept between inference calls (ops._clstm_ws, VPX_FLAG_WEIGHTS_PACKED) still finds its packs, on every route ----
+CASES["gen1_tiny"] = (3, 8, 12, 10, 2, 3, True, False, True, 0)
+KEPT = [  # (tag, precision, {option: value}, bit-identical between calls)
+    ("q_enc1_oddx", "bf16x3", {"OPT_CELL2": 2, "OPT_EXPERIMENT": "NO_C3"}, True),      # q form, two packs: x-only at t = 0
+    ("q_fore3_noinput", "bf16x3", {"OPT_CELL2": 2, "OPT_EXPERIMENT": "NO_C3"}, True),  # q form, the h-only pack
+    ("q_enc2", "bf16x3", {"OPT_CELL2": 2}, True),                                      # small grid: the c3 form in cell2's pack slots
+    ("enc3_states", "bf16x3", {}, True),                                               # cell3, its hoisted projection on convq
+    ("enc1_ragged", "bf16x3", {"OPT_CELL2": 2}, True),                                 # ragged map: cell2's 32x32x16 form
+    ("gen1_tiny", "f32", {"deterministic": True}, True),                               # first generation, fused (one pack, T launches in the dry-run log)
+    ("gen1_tiny", "f32", {}, True),                                                    # ... without the deterministic mode: hoisted projection, K unsplit (3 packs)
+    ("enc2_b4", "bf16x3", {"OPT_CELL3": 0}, False),                                    # hoisted projection + K split: atomics
+]
+
+
+@pytest.mark.parametrize("tag,precision,options,exact", KEPT, ids=[k[0] + ("_det" if k[2].get("deterministic") else "") for k in KEPT])
+def test_kept_workspace_still_holds_the_packs(vpx, tag, precision, options, exact):
+    """Three inference calls on the same tensors: fresh (packs written), on the kept workspace (VPX_FLAG_WEIGHTS_PACKED: no pack launch,
+    every pack read where the first call's carve put it), and fresh again after ops.clear_layout_cache(). A carve that moved a pack
+    between the calls would fault nothing and compute garbage; out, hT and cT must agree bit for bit — on the route that splits K with
+    atomics within 1e-5, the forward bound of test_gpu_more.py::test_small_grids_fused_and_split_paths_agree for that path."""
+    import contextlib
+    Cin, Ch, H, W, B, T, with_x, with_state, peep, order = CASES[tag]
+    inp = {k: (None if v is None else v.cuda()) for k, v in _inputs(tag).items()}
+    with contextlib.ExitStack() as stack, torch.no_grad():
+        for opt, v in options.items():
+            if opt == "deterministic":
+                torch.use_deterministic_algorithms(True)
+                stack.callback(torch.use_deterministic_algorithms, False)
+            else:
+                stack.enter_context(vpx._lib.option(getattr(vpx._lib, opt), int(vpx._lib.Exp[v]) if isinstance(v, str) else v))
+        runs, kept = [], []
+        vpx.ops.clear_layout_cache()
+        for call in range(3):
+            if call == 2:
+                vpx.ops.clear_layout_cache()
+            runs.append(vpx.ops.convlstm_seq(inp["x"], inp["h0"], inp["c0"], inp["W"], inp["b"], inp["Wci"], inp["Wcf"], inp["Wco"],
+                                             seq_len=T, in_channels=Cin, gate_order=order, precision=precision))
+            if call < 2:   # one entry, and the second call ran on the very workspace the first one filled (a miss would have put a new one)
+                assert len(vpx.ops._clstm_ws.ents) == 1
+                kept.append(next(iter(vpx.ops._clstm_ws.ents.values()))[3])
+        assert kept[0] is kept[1]
+        for other in runs[1:]:
+            for a, b in zip(runs[0], other):
+                assert torch.equal(a, b) if exact else _relmax(b, a) < 1e-5
+    vpx.ops.clear_layout_cache()
+

@@ -108,6 +108,28 @@ def test_no_magic_experiment_masks_left():
     assert [ln for f, ln in named if f == "cell2.hip"][0].startswith("p._q = g_experiment & VPX_EXP_CELL2_DIAG_MASK;")
 
 
+def test_convlstm_reserve_offsets_are_spelled_in_one_place():
+    """The layout of the ConvLSTM reserve (gates, cell states, split operands) is written once, in convlstm_reserve (csrc/vpx_host.h):
+    the sums `align256((size_t)T * L.n_state ...` that forward, backward and size query each spelled out occur in at most one function
+    under csrc/, both directions call convlstm_reserve, and neither does arithmetic on the `reserve` pointer itself."""
+    needles = ("align256((size_t)T * L.n_state", "align256((size_t)d->T * L.n_state")
+    owners, n = set(), 0
+    for path in _sources(("vp-suite_amd/csrc", (".hip", ".h"))):
+        n += 1
+        func = None
+        for ln in open(path):
+            if ln[:1] not in (" ", "\t", "\n", "/", "#", "}", "{") and "(" in ln:   # a definition starts in column 0
+                func = ln.split("(")[0].split()[-1]
+            if any(nd in ln for nd in needles):
+                owners.add((os.path.basename(path), func))
+    assert n > 30 and len(owners) <= 1, owners
+    pointer_sum = re.compile(r"reserve\)?\s*\+")
+    assert pointer_sum.search("(char*)reserve" + " + off") and pointer_sum.search("(const char*)(reserve)" + " + off")
+    for name in ("convlstm_fwd_api.hip", "convlstm_bwd_api.hip"):
+        text = open(os.path.join(ROOT, "vp-suite_amd", "csrc", name)).read()
+        assert "convlstm_reserve(d, L, " in text and not pointer_sum.search(text), name
+
+
 def test_option_restores_the_previous_value_on_exception(vpx):
     """_lib.option / _lib.experiment: the value holds inside the block and the one from before comes back when the block raises — for all
     five options, nested. In a dry run: nothing here needs a GPU. vpx_set_option stores any value, named or not."""

@@ -146,6 +146,50 @@ def test_convlstm_seq(L, det, prec):
                         _ok(L, rc, tag + " fwd (split in/out)")
 
 
+# One descriptor per route of the ConvLSTM forward (csrc/convlstm_fwd_api.hip: Route), as its dry-run launches show; inference calls with x.
+# The saving variant of the same descriptor may take another route (c3 is inference only: the q form of cell2 takes the saving call).
+CLSTM_ROUTES = [  # ((Cin, Ch, H, W), B, T, prec, options)
+    ((16, 64, 64, 64), 4, 10, 0, ()),                                              # fused first generation (256 workgroups: not below the bar)
+    ((96, 96, 16, 16), 4, 1, 0, ()),                                               # K split, T = 1: nothing to hoist
+    ((96, 96, 16, 16), 4, 10, 0, ()),                                              # hoist (fp32: cell3 does not apply)
+    ((96, 96, 16, 16), 4, 10, 1, ()),                                              # cell3, its projection on convq
+    ((64, 96, 32, 32), 4, 10, 1, ((_lib.OPT_CELL2, 2), (_lib.OPT_MFMA_SHAPE, 0))),  # cell2 without the q form (32x32x16 MFMAs), forced onto a small grid
+    ((64, 64, 64, 64), 32, 10, 1, ()),                                             # cell2, q form (1024 half-tile workgroups)
+    ((64, 64, 64, 64), 4, 10, 1, ()),                                              # c3 (128 half-tile workgroups)
+]
+
+
+@pytest.mark.parametrize("case", CLSTM_ROUTES, ids=["fused", "ksplit", "hoist", "cell3", "cell2", "cell2q", "c3"])
+def test_convlstm_routes_refuse_short_buffers_and_accept_exact_ones(L, case):
+    """Every route, both directions: the sizes the queries return are accepted at an aligned and at an odd base; a workspace 256 bytes
+    short, and (saving call) a reserve one byte short, are refused with VPX_ERR_WORKSPACE before anything is carved or launched."""
+    (Cin, Ch, H, W), B, T, prec, options = case
+    L.vpx_set_deterministic(0)
+
+    def fwd(d, rs, base, nb):
+        return L.vpx_convlstm_seq_fwd(ctypes.byref(d), _fake(1), _fake(2), _fake(3), _fake(4), _fake(5), _fake(6), _fake(7), _fake(8),
+                                      _fake(9), _fake(10), _fake(11), _fake(12), rs, ctypes.c_void_p(base), nb, None)
+
+    def bwd(d, rs, base, nb):
+        return L.vpx_convlstm_seq_bwd(ctypes.byref(d), _fake(1), _fake(2), _fake(3), _fake(4), _fake(6), _fake(7), _fake(8), _fake(9), _fake(12), rs,
+                                      _fake(13), _fake(14), _fake(15), _fake(16), _fake(17), _fake(18), _fake(19), _fake(20), _fake(21), _fake(22),
+                                      _fake(23), ctypes.c_void_p(base), nb, None)
+    with contextlib.ExitStack() as stack:
+        for opt in options:
+            stack.enter_context(_lib.option(*opt))
+        for save in (0, 1):
+            d = ConvLSTMDesc(B, T, Cin, Ch, H, W, 3, 3, 0, 0, prec, _lib.FLAG_SAVE_FOR_BWD if save else 0)
+            nb, rs = L.vpx_convlstm_workspace_bytes(ctypes.byref(d)), L.vpx_convlstm_reserve_bytes(ctypes.byref(d))
+            assert nb > 256 and (rs > 0) == bool(save)
+            calls = (fwd, bwd) if save else (fwd,)
+            for call in calls:
+                assert call(d, rs, WS_BASE, nb - 256) == E_WS, (call.__name__, save)
+                if save:
+                    assert call(d, rs - 1, WS_BASE, nb) == E_WS, (call.__name__, "reserve")
+                for base in (WS_BASE, WS_BASE_ODD):
+                    _ok(L, call(d, rs, base, nb), f"{call.__name__} save={save} base={base:#x}", allow_unsupported=False)
+
+
 ST_CELLS = [(16, 128, 16, 16, 5), (128, 128, 16, 16, 5), (48, 128, 32, 32, 5), (128, 128, 32, 32, 5), (16, 16, 8, 8, 5), (3, 8, 12, 10, 3),
             (16, 64, 16, 16, 3), (64, 64, 16, 16, 5), (16, 128, 16, 16, 3)]
 # (ST_LAST_FP32 changes the route wherever c5 takes the forward: k = 5, Ch in 32s, no LayerNorm)

@@ -247,24 +247,23 @@ static inline int convlstm_layout(const vpx_convlstm_desc* d, ConvLSTMLayout& L)
     return VPX_OK;
 }
 
+// A carve function takes its slots by ws.take() from a call's Carver, or from this: the same list of slots, added up for the size query.
+// It registers nowhere, records no slot, touches no pending pack or violation text and hands out no address.
+struct CarveMeasure { size_t off = 0; float* take(size_t nfloat) { off += align256(nfloat * sizeof(float)); return nullptr; } };
+size_t convlstm_bwd_workspace_bytes(const vpx_convlstm_desc* d, const ConvLSTMLayout& L);   // vpx_convlstm_seq_bwd's own carve, measured
 
-static inline size_t convlstm_bwd_workspace_bytes(const vpx_convlstm_desc* d, const ConvLSTMLayout& L) {
-    size_t b = align256(packed_weight_bytes(L.d_tiles_full, L.d_chunks, 4, d->precision, L.d_qpc));  // upper bound over both tilings
-    b += align256((size_t)d->T * L.n_state * 4 * sizeof(float));  // dG, all steps
-    b += 2 * align256(L.n_state * sizeof(float));                 // dh, dc carries
-    b += align256(L.slab_floats * sizeof(float));
-    b += align256((size_t)d->T * GATE_BWD_MAX_SLICES * gate_bwd_blocks(d->H * d->W, d->Ch) * 4 * d->Ch * sizeof(float));  // bias-gradient partials
-    b += align256((size_t)COLSUM_BLOCKS * 4 * d->Ch * sizeof(float));                                // ... and their second level
-    b += 3 * align256((size_t)GATE_BWD_MAX_SLICES * L.n_peep * sizeof(float));                       // per-batch-slice peephole-gradient partials
-    if (L.v2)  // dG of all steps in split operand format + the conv2 weight pack of the data gradient
-        b += align256((size_t)d->T * L.n_state * 16) + align256(cell2_packed_bytes(conv2_tiles(d->Cin + d->Ch), 3 * (4 * d->Ch / 16)) + 16384 * conv2_tiles(d->Cin + d->Ch));
-    if (wgrad2_wsp(d, L))  // split dG of all steps + split copies of x, the output sequence and h0
-        b += align256((size_t)d->T * L.n_state * 16) + align256(L.n_x * 4) + align256(L.n_out * 4) + align256(L.n_state * 4);
-    if (d->layout == VPX_LAYOUT_NCHW) {
-        // staged copies of x, out, dout, dx + states (h0,c0,dhT,dcT,dh0,dc0) + 6 peephole-sized buffers
-        b += 2 * align256(L.n_x * 4) + 2 * align256(L.n_out * 4) + 6 * align256(L.n_state * 4) + 6 * align256(L.n_peep * 4);
-    }
-    return b;
+// The reserve a saving forward fills and the backward reads: gates [T][B,H,W,4Ch], cell states [T][B,H,W,Ch] and, where the forward runs
+// on the second-generation cell, the operands in split format for the weight gradient (x all frames, h_0, h_1 .. h_T).
+// base == nullptr: the size alone. A descriptor that does not save has none (all null, 0 bytes).
+struct ConvLSTMReserve { float *gates, *cs; char *x_sp, *h0_sp, *h_sp; size_t bytes; };
+static inline ConvLSTMReserve convlstm_reserve(const vpx_convlstm_desc* d, const ConvLSTMLayout& L, void* base) {
+    ConvLSTMReserve r{};
+    if (!(d->flags & VPX_FLAG_SAVE_FOR_BWD)) return r;
+    auto slot = [&](size_t bytes) { char* p = base ? (char*)base + r.bytes : nullptr; r.bytes += align256(bytes); return p; };
+    r.gates = (float*)slot((size_t)d->T * L.n_state * 4 * sizeof(float));
+    r.cs = (float*)slot((size_t)d->T * L.n_state * sizeof(float));
+    if (L.v2) { r.x_sp = slot(L.n_x * 4); r.h0_sp = slot(L.n_state * 4); r.h_sp = slot((size_t)d->T * L.n_state * 4); }
+    return r;
 }
 
 // ---- plain stride-1 'same' convolution / weight gradient on NHWC tensors (shared by conv_api, stlstm LN path) ----
