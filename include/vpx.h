@@ -34,6 +34,7 @@
  * vpx_mmnist_frames                MovingMNISTOnTheFly.__getitem__ (a batch) vp_suite/datasets/mmnist_on_the_fly.py:78-104,133-147
  * vpx_frames_preprocess            VPDataset.preprocess (a batch of stored sequences)  vp_suite/base/base_dataset.py:233-273, datasets/mmnist.py:56-57
  * vpx_frames_postprocess           VPDataset.postprocess                    vp_suite/base/base_dataset.py:286-297
+ * vpx_actions_gather               the action rows of a batch of stored sequences  vp_suite/datasets/bair.py:60-61
  * vpx_frames_augment               the colour and erasing entries of VPDataset's augmentation list  vp_suite/base/base_dataset.py:19-23,135-141
  * vpx_frames_adapt                 ScaleToModel / ScaleToTest + TF.Resize   vp_suite/utils/compatibility.py:31-50, utils/models.py:7-64
  * vpx_nchw_to_nhwc / nhwc_to_nchw  (layout adaptors at the boundary; the reference is NCHW throughout)
@@ -607,6 +608,16 @@ enum { VPX_FRAMES_U8 = 0, VPX_FRAMES_U16 = 1, VPX_FRAMES_F32 = 2 };
 int vpx_frames_preprocess(const void* src, int dtype, long long N, int Tp, int H, int W, int Cs, const int* table, int B, int n_frames,
                           int seq_step, int ch, int cw, int oh, int ow, int C_out, double lo, double hi, float* out, void* stream);
 int vpx_frames_postprocess(const float* x, long long N, int C, int h, int w, double lo, double hi, unsigned char* out, void* stream);
+/* The action rows that go with such a batch (vp_suite/datasets/bair.py:60-61): src [N, T', A] of element type VPX_ACTIONS_F32 / _F64,
+ * the SAME device table [B, 4] as vpx_frames_preprocess of which only column 0 (the sequence index) is read; out [B, n_frames, A] dense
+ * fp32, out[b, t, :] = float(src[table[b].seq, t * seq_step, :]). float64 is rounded to nearest even, as numpy's astype(float32) does;
+ * float32 is copied; no other arithmetic. One launch on the caller's stream, no workspace, no atomics, no host sync, 64-bit source
+ * offsets. VPX_ERR_ARG: a NULL pointer, an unknown element type, a size < 1, (n_frames - 1) * seq_step + 1 > T'. VPX_ERR_UNSUPPORTED: more
+ * workgroups than one launch holds. The CALLER checks the table: a sequence index outside [0, N) yields zeros and reads nothing out of
+ * bounds. */
+enum { VPX_ACTIONS_F32 = 0, VPX_ACTIONS_F64 = 1 };
+int vpx_actions_gather(const void* src, int dtype, long long N, int Tp, int A, const int* table, int B, int n_frames, int seq_step,
+                       float* out, void* stream);
 
 /* ---- photometric augmentations and erasing of a preprocessed batch, in place (torchvision's tensor transforms, restated) ----
  * x [B, n_frames, C, h, w] dense fp32, changed in place by ONE launch; programs [B, max_ops, VPX_FRAMES_AUG_ROW] (fp32, on the device):

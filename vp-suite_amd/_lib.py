@@ -24,6 +24,7 @@ FLAG_WEIGHTS_PACKED = 2
 FLAG_X_SPLIT = 4
 FLAG_OUT_SPLIT = 8
 FRAMES_U8, FRAMES_U16, FRAMES_F32 = 0, 1, 2
+ACTIONS_F32, ACTIONS_F64 = 0, 1
 FRAMES_AUG_ROW, FRAMES_AUG_MIN_OPS, FRAMES_AUG_MAX_OPS = 9, 16, 64   # a program row: opcode + 8 parameters; rows per program
 
 OPT_CELL2 = 1
@@ -218,6 +219,7 @@ SIGNATURES = {
     # stored frames to a model-ready batch and back
     "vpx_frames_preprocess": (ci, [vp, ci, ll] + [ci] * 4 + [vp] + [ci] * 8 + [dbl, dbl, vp, vp]),   # src dtype N T' H W Cs | table B F step ch cw oh ow C_out | lo hi | out
     "vpx_frames_postprocess": (ci, [vp, ll] + [ci] * 3 + [dbl, dbl, vp, vp]),                       # x N C h w | lo hi | out
+    "vpx_actions_gather": (ci, [vp, ci, ll, ci, ci, vp] + [ci] * 3 + [vp, vp]),                     # src dtype N T' A | table B F step | out
     "vpx_frames_augment": (ci, [vp, vp] + [ci] * 6 + [vp]),                                           # x programs | B F C h w max_ops
     # frame adapter between a model and a test set
     "vpx_frames_adapt": (ci, [vp, ll] + [ci] * 5 + [dbl] * 4 + [vp, vp]),                            # x N C H W oh ow | src lo hi, dst lo hi | out

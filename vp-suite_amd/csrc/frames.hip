@@ -3,6 +3,8 @@
 //   vpx_frames_preprocess    src [N][T'][H][W][Cs] (uint8 / uint16 / float32, channels last as the files hold them) and a device table
 //                            int32 [B][4] = (sequence, crop y0, crop x0, flip bits) -> out float32 [B][F][C_out][oh][ow]
 //   vpx_frames_postprocess   x float32 [N][C][h][w] -> out uint8 [N][h][w][C]; x is only read
+//   vpx_actions_gather       src [N][T'][A] (float32 / float64) and the same device table -> out float32 [B][F][A]: the action rows that go
+//                            with the frames of a batch, out[b][t][:] = float(src[table[b].seq][t * step][:]); a conversion, no arithmetic
 // Streaming kernels: a thread owns four neighbouring output pixels of one row in every channel, so a channel plane receives one 16-byte
 // store per thread where the rows allow it, and on the path without resize every source element is read exactly once (for Cs = 3 the
 // thread's four pixels are 12 contiguous bytes). The resize path gathers four taps per pixel and channel from the same family.
@@ -199,6 +201,31 @@ __global__ __launch_bounds__(FR_THREADS) void frames_postprocess_kernel(PostArgs
     }
 }
 
+struct ActionsArgs {
+    const void* src;                   // [N][Tp][A]
+    const int* table;                  // [B][4]: column 0, the sequence index, is all that is read
+    float* out;                        // [B][F][A]
+    long long N;
+    long long items;                   // B * F * A: one thread each
+    int Tp, A, F, step;
+};
+
+// thread = one output element (sample b, frame t, component a). float64 storage: the conversion rounds to nearest even (the default
+// mode), as numpy's astype(float32) does; float32 storage is copied.
+template <typename T>
+__global__ __launch_bounds__(FR_THREADS) void actions_gather_kernel(ActionsArgs a) {
+    const long long item = (long long)blockIdx.x * FR_THREADS + threadIdx.x;
+    if (item >= a.items) return;
+    const int c = (int)(item % a.A);
+    const long long r = item / a.A;
+    const int t = (int)(r % a.F);
+    const long long b = r / a.F;
+    const long long seq = a.table[(size_t)b * 4];
+    float v = 0.0f;                                                    // a row the caller did not check reads nothing out of bounds: zeros
+    if (seq >= 0 && seq < a.N) v = (float)((const T*)a.src)[((size_t)seq * a.Tp + (size_t)t * a.step) * a.A + c];
+    a.out[item] = v;
+}
+
 template <typename T>
 static void launch_preprocess(const FramesArgs& a, int resize, unsigned blocks, hipStream_t stream) {
     if (resize) VPX_LAUNCH((frames_preprocess_kernel<T, 1>), dim3(blocks), dim3(FR_THREADS), 0, stream, a);
@@ -265,6 +292,27 @@ int vpx_frames_postprocess(const float* x, long long N, int C, int h, int w, dou
     a.lo = (float)lo;
     const unsigned blocks = (unsigned)((a.items + FR_THREADS - 1) / FR_THREADS);
     VPX_LAUNCH(frames_postprocess_kernel, dim3(blocks), dim3(FR_THREADS), 0, (hipStream_t)stream, a);
+    VPX_CHECK_HIP(vpx_hip_last_error());
+    return VPX_OK;
+}
+
+int vpx_actions_gather(const void* src, int dtype, long long N, int Tp, int A, const int* table, int B, int n_frames, int seq_step,
+                       float* out, void* stream) {
+    const char* who = "vpx_actions_gather";
+    if (!src || !table || !out) { set_error("%s: NULL tensor argument", who); return VPX_ERR_ARG; }
+    if (dtype != VPX_ACTIONS_F32 && dtype != VPX_ACTIONS_F64) { set_error("%s: unknown element type %d (float32 and float64 are stored)", who, dtype); return VPX_ERR_ARG; }
+    if (N < 1 || Tp < 1 || A < 1) { set_error("%s: every source size must be >= 1 (got N=%lld T'=%d A=%d)", who, N, Tp, A); return VPX_ERR_ARG; }
+    if (B < 1 || n_frames < 1 || seq_step < 1) { set_error("%s: B, n_frames and seq_step must be >= 1 (got %d, %d, %d)", who, B, n_frames, seq_step); return VPX_ERR_ARG; }
+    if ((long long)(n_frames - 1) * seq_step + 1 > Tp) { set_error("%s: frame %d at step %d lies past the %d stored frames", who, n_frames - 1, seq_step, Tp); return VPX_ERR_ARG; }
+    const double items_d = (double)B * n_frames * A;
+    if (items_d / FR_THREADS + 1.0 > 2147483647.0) { set_error("%s: %d samples of %d rows of %d exceed one launch", who, B, n_frames, A); return VPX_ERR_UNSUPPORTED; }
+    ActionsArgs a;
+    a.src = src; a.table = table; a.out = out;
+    a.N = N; a.Tp = Tp; a.A = A; a.F = n_frames; a.step = seq_step;
+    a.items = (long long)B * n_frames * A;
+    const unsigned blocks = (unsigned)((a.items + FR_THREADS - 1) / FR_THREADS);
+    if (dtype == VPX_ACTIONS_F32) VPX_LAUNCH(actions_gather_kernel<float>, dim3(blocks), dim3(FR_THREADS), 0, (hipStream_t)stream, a);
+    else VPX_LAUNCH(actions_gather_kernel<double>, dim3(blocks), dim3(FR_THREADS), 0, (hipStream_t)stream, a);
     VPX_CHECK_HIP(vpx_hip_last_error());
     return VPX_OK;
 }

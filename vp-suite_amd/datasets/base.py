@@ -7,7 +7,12 @@ produces its frames at their final size and value range in the generating kernel
 StoredVPDataset: sequences held as ONE raw tensor [N, T', H, W(, C)] — on the GPU, or in pinned host memory — and the reference's
 preprocess() / postprocess() chain (convert, permute, scale, crop, resize, flip) as one launch of csrc/frames.hip per batch and
 direction. No ATen op touches a pixel between the stored bytes and the batch a model reads. The colour and erasing augmentations of the
-reference's list run as per-sample programs in at most one further launch (csrc/frames_aug.hip), in place on the batch."""
+reference's list run as per-sample programs in at most one further launch (csrc/frames_aug.hip), in place on the batch.
+
+Stored actions (`actions=` [N, T', A]) are kept where the frames are and a batch's rows are gathered by one more launch of csrc/frames.hip
+(vpx_actions_gather) from the table of the frames launch. WHAT DIFFERS FROM THE REFERENCE: a stored dataset with actions puts
+`supports_actions = True` into its `config`. No dataset of the reference sets that key, although its compatibility check reads it, so
+there an action-conditional model is accepted by no dataset at all; here it is accepted by the datasets that really carry actions."""
 import math
 import random
 
@@ -346,6 +351,27 @@ class _IndexLoader:
             start += n
 
 
+class _PinnedStage:
+    """A pinned staging buffer: a batch's rows (their first `steps` entries along T') are gathered into it and copied to the GPU once.
+    It is reused while it fits; the event tells when the previous batch's copy has left it."""
+
+    def __init__(self):
+        self.buffer = self.event = None
+
+    def to_device(self, raw, indices, steps, device):
+        n = len(indices)
+        if self.buffer is None or self.buffer.shape[0] < n or self.buffer.shape[1] != steps:
+            self.buffer = torch.empty((n, steps) + tuple(raw.shape[2:]), dtype=raw.dtype).pin_memory()
+        elif self.event is not None:
+            self.event.synchronize()                              # the previous batch's copy has left the buffer
+        for k, i in enumerate(indices):
+            self.buffer[k].copy_(raw[i, :steps])
+        dev = self.buffer[:n].to(device, non_blocking=True)
+        self.event = torch.cuda.Event()
+        self.event.record()
+        return dev
+
+
 class StoredSubset:
     """Some samples of a stored dataset (the reference's VPSubset): forwards every other attribute to the dataset, keeps batch() / loader()."""
 
@@ -388,7 +414,12 @@ class StoredVPDataset(VPDataset):
     in the list and were drawn, so the result is the list applied in order. The flips land in `augmentations`, the rest in `photometric`.
     The clamps of colour jitter and autocontrast are to [0, 1] literally, also under a value range such as (-1, 1): the reference
     scales before it transforms and torchvision clamps float tensors to [0, 1], so it behaves the same way. A channel that is constant
-    over a frame is left unchanged by autocontrast."""
+    over a frame is left unchanged by autocontrast.
+    actions: None, or the stored actions [N, T', A] as numpy float32 / float64 with the leading two sizes of `raw`. They live where
+    `storage` keeps the frames (on the GPU, or pinned and staged per batch like the frames); ACTION_SIZE becomes A, `config` gains
+    supports_actions = True, and batch() / __getitem__ return actions[i, :seq_len:seq_step] as float32 (float64 rounded to nearest even,
+    what torch's .float() and numpy's astype do) from one further launch instead of zeros. Crops, flips and photometric entries never
+    touch them (the reference's do not either). Without `actions` nothing changes: the same zeros, launches and draws."""
     NAME = "Stored sequences"
     ACTION_SIZE = 0
     SUPPORTS_TRANSFORMS = True
@@ -404,7 +435,7 @@ class StoredVPDataset(VPDataset):
     augmentations = None   # the flips [(bit, p)]
     photometric = None     # every other entry, parse_photometric()'s form
 
-    def __init__(self, split, raw=None, **dataset_kwargs):
+    def __init__(self, split, raw=None, actions=None, **dataset_kwargs):
         super().__init__(split, **dataset_kwargs)
         self.NON_CONFIG_VARS = self.NON_CONFIG_VARS + ["transform_rng"]
         self.storage = dataset_kwargs.get("storage", self.storage)
@@ -422,10 +453,13 @@ class StoredVPDataset(VPDataset):
         self.photometric = parse_photometric([aug for aug in given if not is_flip(aug)])
         flips_before = np.cumsum([is_flip(aug) for aug in given]).tolist()
         self._flips_before = [n for n, aug in zip(flips_before, given) if not is_flip(aug)]   # per photometric entry: flips ahead of it in the list
-        self._raw = self._raw_host = self._staging = self._staging_event = None
+        self._raw = self._raw_host = self._actions = self._actions_host = None
+        self._staging, self._actions_staging = _PinnedStage(), _PinnedStage()
         self.reset_rng()
         if raw is not None:
             self._set_raw(raw)
+        if actions is not None:
+            self._set_actions(actions)
 
     # ---- storage ----
     def _set_raw(self, raw):
@@ -453,31 +487,50 @@ class StoredVPDataset(VPDataset):
         self.img_shape = (int(c_out),) + self._out_hw
         check_photometric(self.photometric, int(c_out))
 
+    def _set_actions(self, actions):
+        """Takes the stored actions [N, T', A] (numpy float32 / float64, or such a torch tensor on the host) of the sequences set before."""
+        if self._raw_host is None:
+            raise ValueError("actions need the sequences they belong to: give raw= as well")
+        actions = actions.detach().cpu().numpy() if torch.is_tensor(actions) else np.asarray(actions)
+        if actions.dtype not in (np.float32, np.float64):
+            raise ValueError(f"stored actions must be float32 or float64 (got {actions.dtype})")
+        if actions.ndim != 3 or actions.shape[2] < 1 or tuple(actions.shape[:2]) != tuple(self._raw_host.shape[:2]):
+            raise ValueError(f"stored actions must be [N, T', A] with the sequences' N = {self._raw_host.shape[0]} and T' = {self._raw_host.shape[1]} "
+                             f"(got {actions.shape})")
+        self._actions_host = np.ascontiguousarray(actions)
+        self.ACTION_SIZE = int(actions.shape[2])
+
+    def _place(self, host):
+        t = torch.from_numpy(host)
+        return t.to(self.device) if self.storage == "device" else t.pin_memory()
+
     def _stored(self):
         """The raw tensor where the storage mode keeps it (made at the first use: building a dataset needs no GPU)."""
         if self._raw is None:
             if self._raw_host is None:
                 raise VpxError(f"'{self.NAME}' holds no sequences")
-            t = torch.from_numpy(self._raw_host)
-            self._raw = t.to(self.device) if self.storage == "device" else t.pin_memory()
+            self._raw = self._place(self._raw_host)
         return self._raw
+
+    def _stored_actions(self):
+        if self._actions is None:
+            self._actions = self._place(self._actions_host)
+        return self._actions
 
     def _on_device(self, indices):
         """(raw tensor on the GPU, sequence index of every sample in it)."""
         raw = self._stored()
         if self.storage == "device":
             return raw, list(indices)
-        n, frames = len(indices), min(self.seq_len, raw.shape[1])
-        if self._staging is None or self._staging.shape[0] < n or self._staging.shape[1] != frames:
-            self._staging = torch.empty((n, frames) + tuple(raw.shape[2:]), dtype=raw.dtype).pin_memory()
-        elif self._staging_event is not None:
-            self._staging_event.synchronize()                     # the previous batch's copy has left the buffer
-        for k, i in enumerate(indices):
-            self._staging[k].copy_(raw[i, :frames])
-        dev = self._staging[:n].to(self.device, non_blocking=True)
-        self._staging_event = torch.cuda.Event()
-        self._staging_event.record()
-        return dev, list(range(n))
+        dev = self._staging.to_device(raw, indices, min(self.seq_len, raw.shape[1]), self.device)
+        return dev, list(range(len(indices)))
+
+    def _actions_on_device(self, indices):
+        """The stored actions on the GPU, laid out as _on_device() lays out the frames: the table of the frames launch indexes both."""
+        raw = self._stored_actions()
+        if self.storage == "device":
+            return raw
+        return self._actions_staging.to_device(raw, indices, min(self.seq_len, raw.shape[1]), self.device)
 
     # ---- transforms ----
     def reset_rng(self):
@@ -622,9 +675,17 @@ class StoredVPDataset(VPDataset):
     def origin(self, i):
         return f"stored sequence {i}"
 
+    @property
+    def config(self) -> dict:
+        cfg = super().config
+        if self._actions_host is not None:
+            cfg["supports_actions"] = True                        # (no dataset of the reference sets the key: see the module docstring)
+        return cfg
+
     def batch(self, indices):
         """The reference's dict for these samples from ONE launch (two when a photometric program was drawn): frames [n, total_frames, C, h, w] on the GPU, actions zeros
-        [n, total_frames, max(ACTION_SIZE, 1)], origin. Equal to the __getitem__ calls in the same order."""
+        [n, total_frames, max(ACTION_SIZE, 1)], origin. Equal to the __getitem__ calls in the same order. With stored actions: one more
+        launch, directly after the frames launch and from its table, gathers them as float32 [n, total_frames, ACTION_SIZE]."""
         if not self.ready_for_usage:
             raise RuntimeError("Dataset is not yet ready for usage (maybe you forgot to call set_seq_len()).")
         indices = [int(i) for i in indices]
@@ -636,8 +697,11 @@ class StoredVPDataset(VPDataset):
         table, programs = self.draws(seqs)
         frames = ops.frames_preprocess(raw, table, self.total_frames, self.seq_step, self._crop_hw, self._out_hw, self.img_shape[0],
                                        (self.value_range_min, self.value_range_max))
+        if self._actions_host is not None:                        # directly after the frames launch, from its table
+            actions = ops.actions_gather(self._actions_on_device(indices), table, self.total_frames, self.seq_step)
         self._augment(frames, programs)
-        actions = torch.zeros((len(indices), self.total_frames, max(self.ACTION_SIZE, 1)), device=frames.device)
+        if self._actions_host is None:
+            actions = torch.zeros((len(indices), self.total_frames, max(self.ACTION_SIZE, 1)), device=frames.device)
         return {"frames": frames, "actions": actions, "origin": [self.origin(i) for i in indices]}
 
     def __getitem__(self, i):

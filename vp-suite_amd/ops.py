@@ -1417,6 +1417,47 @@ def frames_preprocess(src, table, n_frames, seq_step=1, crop_size=None, out_size
     return out
 
 
+ACTION_DTYPES = {torch.float32: _lib.ACTIONS_F32, torch.float64: _lib.ACTIONS_F64}
+
+
+def actions_gather(raw_actions, table, n_frames, seq_step=1):
+    """float32 [B, n_frames, A] from stored actions `raw_actions` [N, T', A] (a float32 / float64 GPU tensor) in ONE launch:
+    out[b, t] = float32(raw_actions[table[b, 0], t * seq_step]) — see include/vpx.h. `table`: the host rows [B, 4] a preprocess launch
+    takes, or a GPU int32 tensor [B, 4] whose sequence indices the caller has checked (a dataset hands over the table of its frames
+    launch); only column 0 is read. float64 is rounded to nearest even, as numpy's astype(float32) does."""
+    if not (torch.is_tensor(raw_actions) and raw_actions.is_cuda):
+        raise _lib.VpxError("actions_gather: raw_actions must be a GPU tensor; the rows are gathered by a HIP kernel, there is no CPU fallback")
+    if raw_actions.dtype not in ACTION_DTYPES:
+        raise ValueError(f"actions_gather: stored element type {raw_actions.dtype} is unknown (float32 and float64 are)")
+    if raw_actions.ndim != 3 or min(raw_actions.shape) < 1:
+        raise ValueError(f"actions_gather: raw_actions must be [N, T', A], nothing empty (got {tuple(raw_actions.shape)})")
+    src = raw_actions.contiguous()
+    N, Tp, A = (int(s) for s in src.shape)
+    n_frames, seq_step = int(n_frames), int(seq_step)
+    if min(n_frames, seq_step) < 1:
+        raise ValueError(f"actions_gather: n_frames and seq_step must be >= 1 (got {n_frames}, {seq_step})")
+    if (n_frames - 1) * seq_step + 1 > Tp:
+        raise ValueError(f"actions_gather: frame {n_frames - 1} at step {seq_step} lies past the {Tp} stored frames")
+    if torch.is_tensor(table) and table.is_cuda:
+        if table.dtype != torch.int32 or table.ndim != 2 or table.shape[1] != 4 or table.shape[0] < 1 or not table.is_contiguous() or table.device != src.device:
+            raise ValueError(f"actions_gather: a device table must be a contiguous int32 [B, 4] on the actions' GPU (got {table.dtype} {tuple(table.shape)})")
+        dev_table = table
+    else:
+        import numpy as np
+        t = table.numpy() if torch.is_tensor(table) else np.asarray(table)
+        if t.ndim != 2 or t.shape[1] != 4 or t.shape[0] < 1 or not np.issubdtype(t.dtype, np.integer):
+            raise ValueError(f"table must be an integer table [B, 4] (got {t.dtype} {t.shape})")
+        if t[:, 0].min() < 0 or t[:, 0].max() >= N:
+            raise ValueError(f"sequence index outside [0, {N})")
+        dev_table = torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32)).to(src.device)
+    B = int(dev_table.shape[0])
+    out = torch.empty((B, n_frames, A), dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        check(_lib.lib().vpx_actions_gather(ptr(src), ACTION_DTYPES[src.dtype], N, Tp, A, ptr(dev_table), B, n_frames, seq_step, ptr(out), stream()),
+              "vpx_actions_gather")
+    return out
+
+
 def frames_postprocess(x, lo=0.0, hi=1.0):
     """uint8 [..., h, w, C] on the GPU from float32 [..., C, h, w] in one launch: ((x - lo) / (hi - lo)) * 255 in float32, clamped to
     [0, 255], truncated; NaN gives 0. `x` is left as it is (the reference subtracts in place)."""

@@ -25,7 +25,14 @@ DEFAULT_RUN_CONFIG is the reference's DefaultRunConfig (defaults.py:37-64) key f
   * test() RETURNS its results, {dataset NAME: {model NAME: [metric dict per prediction horizon]}}, besides printing what the reference
     prints. Tested models that share a NAME are told apart by " #k", k = the position in the test set's list of models.
   * download_dataset() raises NotImplementedError: nothing is ever fetched.
-  * Models bridge a differing value range / frame size through ONE fused HIP launch per direction (compatibility.FrameAdapter)."""
+  * Models bridge a differing value range / frame size through ONE fused HIP launch per direction (compatibility.FrameAdapter).
+  * Actions. A stored dataset that carries actions ("BAIR", or StoredVPDataset(actions=...)) sets supports_actions = True in its
+    `config`; no dataset of the reference sets the key its compatibility check reads, so there no dataset accepts an action-conditional
+    model. When a run leaves `use_actions` open (it is not among the run arguments), it is taken as True for an action-conditional model
+    whose dataset carries actions, so that load_dataset("BAIR") / create_model(..., action_conditional=True) / train() / test() runs as
+    it stands; a given `use_actions` always holds, and with datasets without actions nothing changes. test() hands the batch's actions
+    to every action-conditional model (the reference asks for a `use_actions` attribute that nothing ever sets, so its test() passes
+    actions to no model)."""
 import json
 import os
 import random
@@ -205,6 +212,16 @@ class VPSuite:
         run_config["opt_direction"] = "maximize" if LOSS_CLASSES[run_config["val_rec_criterion"]].BIGGER_IS_BETTER else "minimize"
         return run_config
 
+    @staticmethod
+    def _open_use_actions(run_config: dict, run_kwargs: dict, model, datasets):
+        """`run_config`, or a copy with use_actions = True when the caller left the key open, `model` is action-conditional and one of
+        `datasets` carries actions (see the module docstring)."""
+        if "use_actions" in run_kwargs or not (model.CAN_HANDLE_ACTIONS and model.config["action_conditional"]):
+            return run_config
+        if not any(d.config.get("supports_actions", False) for d in datasets):
+            return run_config
+        return {**run_config, "use_actions": True}
+
     def _set_seeds(self, seed: int):
         """The only place where the general generators are seeded."""
         random.seed(seed)
@@ -227,6 +244,7 @@ class VPSuite:
             raise ValueError("given indices for model and/or dataset are invalid")
         dataset.set_seq_len(run_config["context_frames"], run_config["pred_frames"], run_config["seq_step"])
         assert dataset.is_ready, "dataset is not ready even though set_seq_len has just been called"
+        run_config = self._open_use_actions(run_config, run_kwargs, model, [dataset])
         check_run_and_model_compat(model, run_config)
         check_model_and_data_compat(model, dataset, strict_mode=True)
         return model, dataset, run_config
@@ -365,7 +383,7 @@ class VPSuite:
         test_models = []
         for model in self.models:
             try:
-                check_run_and_model_compat(model, run_config)
+                check_run_and_model_compat(model, self._open_use_actions(run_config, run_kwargs, model, test_sets))
                 test_models.append(model)
             except ValueError as e:
                 print(f"skipping test of model '{model.NAME}' because of incompatibility with run config: {str(e)}")
@@ -415,7 +433,7 @@ class VPSuite:
                     inp, target, actions = model.unpack_data(data, config)
                     inp = preprocess(inp)  # test format to model format
                     model.eval()
-                    if getattr(model, "use_actions", False):
+                    if model.CAN_HANDLE_ACTIONS and model.config["action_conditional"]:   # (the reference: an attribute nothing sets)
                         pred, _ = model(inp, pred_frames=pred_frames, actions=actions)
                     else:
                         pred, _ = model(inp, pred_frames=pred_frames)
