@@ -130,6 +130,31 @@ def test_convlstm_reserve_offsets_are_spelled_in_one_place():
         assert "convlstm_reserve(d, L, " in text and not pointer_sum.search(text), name
 
 
+def test_stlstm_reserve_offsets_are_spelled_in_one_place():
+    """The layouts of the ST-LSTM reserves are written once each: stlstm_reserve (csrc/vpx_host.h: gates_c, gates_m, o, tanh(conv_last)) and
+    stlstm_ln_reserve (csrc/stlstm_ln_api.hip: the LayerNorm variant's plane walk). The first one's sums and the start of the second one's walk occur in one
+    function each under csrc/, all three ST-LSTM files call a reserve function, and none does arithmetic on the `reserve` pointer itself."""
+    needles = {"plain": ("align256(3 * L.n_state",), "ln": ("R.xhat_x = take(7)",)}
+    owners, n = {k: set() for k in needles}, 0
+    for path in _sources(("vp-suite_amd/csrc", (".hip", ".h"))):
+        n += 1
+        func = None
+        for ln in open(path):
+            if ln[:1] not in (" ", "\t", "\n", "/", "#", "}", "{") and "(" in ln:   # a definition starts in column 0
+                func = ln.split("(")[0].split()[-1]
+            for kind, nds in needles.items():
+                if any(nd in ln for nd in nds):
+                    owners[kind].add((os.path.basename(path), func))
+    assert n > 30 and owners == {"plain": {("vpx_host.h", "stlstm_reserve")}, "ln": {("stlstm_ln_api.hip", "stlstm_ln_reserve")}}, owners
+    pointer_sum = re.compile(r"reserve\)?\s*\+|\)\s*reserve\s*;\s*r\s*\+=|r\s*=\s*\((?:const )?char\*\)\s*reserve")
+    assert pointer_sum.search("(char*)reserve" + " + off") and pointer_sum.search("char* r = (char*)" + "reserve; r += n")
+    calls = {"stlstm_api.hip": ("stlstm_reserve(d, L, ", "stlstm_ln_reserve_bytes(d)"), "stlstm_bwd_api.hip": ("stlstm_reserve(d, L, ",),
+             "stlstm_ln_api.hip": ("stlstm_ln_reserve(d, s, ",)}
+    for name, wanted in calls.items():
+        text = open(os.path.join(ROOT, "vp-suite_amd", "csrc", name)).read()
+        assert all(w in text for w in wanted) and not pointer_sum.search(text), name
+
+
 def test_option_restores_the_previous_value_on_exception(vpx):
     """_lib.option / _lib.experiment: the value holds inside the block and the one from before comes back when the block raises — for all
     five options, nested. In a dry run: nothing here needs a GPU. vpx_set_option stores any value, named or not."""

@@ -243,6 +243,61 @@ def test_stlstm_step(L, det, prec):
                                 _ok(L, rc, tag + f" wgrad_batch T={T}", allow_unsupported=False)
 
 
+# One descriptor per route of the ST-LSTM step (csrc/stlstm_api.hip: STRoute, its conv_o sub-forms; csrc/stlstm_bwd_api.hip: STBwdChoice), as
+# the dry-run launches show; B = 2 unless given, bf16x3 unless given.
+ST_ROUTES = [  # ((Cin, Ch, H, W, k), B, layer_norm, layout, prec, experiment, deferred)
+    ((8, 32, 16, 16, 5), 2, 0, 0, 1, 0, False),                                   # C5K forward (2 pixel tiles); stw + K-split c5 backward
+    ((8, 32, 16, 16, 5), 2, 0, 0, 1, E.C5_UNSPLIT, False),                        # C5 forward; stw + unsplit c5 backward
+    ((8, 32, 16, 16, 5), 2, 0, 0, 1, E.ST_FWD_GEN1, False),                       # GEN1, conv_o K-split + pointwise gate (4 tiles * 1 < 384)
+    ((8, 128, 32, 48, 3), 8, 0, 0, 1, 0, False),                                  # GEN1, conv_o fused with the gate (96 tiles * 4 = 384)
+    ((3, 8, 12, 10, 3), 2, 1, 0, 0, 0, False),                                    # LN
+    ((3, 8, 12, 10, 3), 2, 1, 1, 0, 0, False),                                    # LN, reference layout (staging inside its carve)
+    ((8, 32, 16, 16, 5), 2, 0, 0, 1, E.ST_DGRAD_GEN1 | E.ST_WGRAD_GEN1, False),   # first-generation backward (fp32 dG7, five weight-gradient launches)
+    ((8, 32, 16, 16, 5), 2, 0, 0, 1, 0, True),                                    # deferred weight gradients (vpx_stlstm_defers_wgrad = 1)
+]
+
+
+@pytest.mark.parametrize("case", ST_ROUTES, ids=["c5k", "c5", "gen1_osplit", "gen1_fused", "ln", "ln_nchw", "bwd_gen1", "deferred"])
+def test_stlstm_routes_refuse_short_buffers_and_accept_exact_ones(L, case):
+    """Every route of the ST-LSTM step, both directions: the sizes the queries return are accepted at an aligned and at an odd base; a
+    workspace 256 bytes short, and (saving call) a reserve one byte short, are refused with VPX_ERR_WORKSPACE. The queries tell the split
+    routes from GEN1 / LN and C5 from C5K (asserted); which conv_o form a GEN1 descriptor takes shows in no query: that rests on the
+    dry-run launch log the descriptors were picked from (`st_ln_out_kernel` after conv_o: K-split)."""
+    (Cin, Ch, H, W, k), B, ln, layout, prec, exp, deferred = case
+    L.vpx_set_deterministic(0)
+    lnarr = (ctypes.c_void_p * 8)(*[0x200000000000 + i * (1 << 30) for i in range(8)]) if ln else None
+    dlnarr = (ctypes.c_void_p * 8)(*[0x300000000000 + i * (1 << 30) for i in range(8)]) if ln else None
+    sh = _lib.STLSTMShadows((ctypes.c_void_p * 5)(*[0x400000000000 + i * (1 << 34) for i in range(5)]), (ctypes.c_void_p * 3)(), 0x500000000000)
+
+    def fwd(d, rs, base, nb):
+        return L.vpx_stlstm_step_fwd(ctypes.byref(d), *[_fake(i) for i in range(1, 10)], lnarr, *[_fake(i) for i in range(10, 15)],
+                                     _fake(15), rs, ctypes.c_void_p(base), nb, None)
+
+    def bwd(d, rs, base, nb):
+        dWs = [None] * 5 if deferred else [_fake(i) for i in range(25, 30)]
+        return L.vpx_stlstm_step_bwd_ex(ctypes.byref(d), *[_fake(i) for i in range(1, 12)], lnarr, _fake(15), rs, *[_fake(i) for i in range(16, 21)],
+                                        _fake(21), _fake(22), _fake(23), _fake(24), *dWs, dlnarr, ctypes.c_void_p(base), nb, None,
+                                        ctypes.byref(sh) if deferred else None)
+    with _lib.experiment(exp):
+        for save in (0, 1):
+            d = STLSTMDesc(B, Cin, Ch, H, W, k, ln, layout, prec, _lib.FLAG_SAVE_FOR_BWD if save else 0)
+            nb, rs = L.vpx_stlstm_workspace_bytes(ctypes.byref(d)), L.vpx_stlstm_reserve_bytes(ctypes.byref(d))
+            assert nb > 256 and (rs > 0) == bool(save)
+            assert not deferred or L.vpx_stlstm_defers_wgrad(ctypes.byref(d)) == 1
+            # the forward's c5 routes are the ones on split operands; the first generation and LayerNorm are not
+            assert L.vpx_stlstm_uses_split(ctypes.byref(d)) == int(not ln and k == 5 and not (exp & E.ST_FWD_GEN1))
+            if not save and not ln and k == 5 and not (exp & ~E.C5_UNSPLIT):   # C5 against C5K: the K-split form alone carves partial sums
+                with _lib.experiment(exp ^ E.C5_UNSPLIT):
+                    other = L.vpx_stlstm_workspace_bytes(ctypes.byref(d))
+                assert (nb < other) == bool(exp & E.C5_UNSPLIT) and nb != other
+            for call in ((fwd, bwd) if save else (fwd,)):
+                assert call(d, rs, WS_BASE, nb - 256) == E_WS, (call.__name__, save)
+                if save:
+                    assert call(d, rs - 1, WS_BASE, nb) == E_WS, (call.__name__, "reserve")
+                for base in (WS_BASE, WS_BASE_ODD):
+                    _ok(L, call(d, rs, base, nb), f"{call.__name__} save={save} base={base:#x}", allow_unsupported=False)
+
+
 def test_decouple_tail(L):
     for det in (0, 1):
         L.vpx_set_deterministic(det)

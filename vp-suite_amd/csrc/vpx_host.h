@@ -382,20 +382,68 @@ static inline int plain_wgrad(hipStream_t stream, int prec, ConvGeo g, const flo
 }
 
 
-// backward workspace of one ST-LSTM step (stlstm_bwd_api.hip)
+// ---- one ST-LSTM cell step (stlstm_api.hip, stlstm_bwd_api.hip; LayerNorm variant: stlstm_ln_api.hip) ----
+// The tensors of a call, in the native layout (NHWC) once the reference layout's copies are staged.
+struct STFwdTensors {
+    const float *x, *h, *c, *m, *Wx, *Wh, *Wm, *Wo, *Wlast;
+    const float* const* ln;
+    float* out[5];   // h_new, c_new, m_new, delta_c, delta_m
+};
+struct STBwdTensors {
+    const float *x, *h, *c, *m, *c_new, *m_new, *Wx, *Wh, *Wm, *Wo, *Wlast;
+    const float* const* ln;
+    const float* g[5];   // gradients of h_new, c_new, m_new, delta_c, delta_m (null: none)
+    float *dx, *dh, *dc, *dm, *dW[5];   // dW: Wx, Wh, Wm, Wo, Wlast (null: not wanted)
+    float* const* dln;
+};
+static inline C5Plan c5_plan_of(int B, int H, int W) { C5Plan cp{}; cp.B = B; cp.H = H; cp.W = W; return cp; }   // an empty c5 launch over B maps
+// Layout adaptation (reference NCHW -> native NHWC), shared by every route of both directions. The slots: x (and dx), then nst state-sized
+// ones. st_stage_in transposes x and the listed Ch-wide inputs into slots 0.. (an absent one stays absent) and points the wanted outputs at
+// slots first.. (dx: at bdx); st_stage_out transposes those back to where the caller wants them. Under NHWC all three do nothing.
+struct STStage { float *bx, *bdx, *st[14], *caller[5], *caller_dx; int first, nout; };
+template <class WS>
+static inline void carve_st_stage(WS& ws, const vpx_stlstm_desc* d, size_t n_x, size_t n_state, bool bwd, int nst, STStage& s) {
+    if (d->layout != VPX_LAYOUT_NCHW) return;
+    s.bx = ws.take(n_x);
+    if (bwd) s.bdx = ws.take(n_x);
+    for (int i = 0; i < nst; ++i) s.st[i] = ws.take(n_state);
+}
+static inline int st_stage_in(const vpx_stlstm_desc* d, STStage& s, const float** x, std::initializer_list<const float**> ins, int first,
+                              std::initializer_list<float**> outs, float** dx, hipStream_t stream) {
+    if (d->layout != VPX_LAYOUT_NCHW) return VPX_OK;
+    VPX_CHECK_HIP(launch_nchw_to_nhwc(*x, s.bx, d->B, d->Cin, d->H, d->W, stream)); *x = s.bx;
+    int i = 0;
+    for (const float** t : ins) { if (*t) { VPX_CHECK_HIP(launch_nchw_to_nhwc(*t, s.st[i], d->B, d->Ch, d->H, d->W, stream)); *t = s.st[i]; } ++i; }
+    s.first = first;
+    for (float** o : outs) { s.caller[s.nout] = *o; if (*o) *o = s.st[first + s.nout]; ++s.nout; }
+    if (dx && *dx) { s.caller_dx = *dx; *dx = s.bdx; }
+    return VPX_OK;
+}
+static inline int st_stage_out(const vpx_stlstm_desc* d, const STStage& s, hipStream_t stream) {
+    if (d->layout != VPX_LAYOUT_NCHW) return VPX_OK;
+    if (s.caller_dx) VPX_CHECK_HIP(launch_nhwc_to_nchw(s.bdx, s.caller_dx, d->B, d->Cin, d->H, d->W, stream));
+    for (int i = 0; i < s.nout; ++i) if (s.caller[i]) VPX_CHECK_HIP(launch_nhwc_to_nchw(s.st[s.first + i], s.caller[i], d->B, d->Ch, d->H, d->W, stream));
+    return VPX_OK;
+}
+// The reserve a saving forward fills and the backward reads: gates_c (3Ch) + gates_m (3Ch) + o + tanh(conv_last), 8 state-sized planes.
+// base == nullptr: the size alone. A descriptor that does not save has none (all null, 0 bytes). L: either direction's layout.
+struct STReserve { float *gates_c, *gates_m, *o, *tl; size_t bytes; };
+template <class LAYOUT>
+static inline STReserve stlstm_reserve(const vpx_stlstm_desc* d, const LAYOUT& L, const void* base) {
+    STReserve r{};
+    if (!(d->flags & VPX_FLAG_SAVE_FOR_BWD)) return r;
+    auto slot = [&](size_t bytes) { float* p = base ? (float*)((char*)base + r.bytes) : nullptr; r.bytes += bytes; return p; };
+    r.gates_c = slot(align256(3 * L.n_state * 4)); r.gates_m = slot(align256(3 * L.n_state * 4));
+    r.o = slot(align256(L.n_state * 4)); r.tl = slot(align256(L.n_state * 4));
+    return r;
+}
+// backward workspace of one ST-LSTM step: vpx_stlstm_step_bwd's own carve, measured (stlstm_bwd_api.hip)
 size_t stlstm_bwd_workspace_bytes(const vpx_stlstm_desc* d);
-// LayerNorm variant (stlstm_ln_api.hip)
+// LayerNorm variant (stlstm_ln_api.hip): its reserve's size, the larger of its two carves (the backward's for a saving descriptor), the
+// two directions in either layout on the caller's whole workspace
 size_t stlstm_ln_reserve_bytes(const vpx_stlstm_desc* d);
 size_t stlstm_ln_workspace_bytes(const vpx_stlstm_desc* d);
-int stlstm_ln_fwd(const vpx_stlstm_desc* d, const float* x, const float* h, const float* c, const float* m,
-                  const float* Wx, const float* Wh, const float* Wm, const float* Wo, const float* Wlast,
-                  const float* const* ln, float* h_new, float* c_new, float* m_new, float* delta_c, float* delta_m,
-                  void* reserve, Carver& ws, hipStream_t stream);
-int stlstm_ln_bwd(const vpx_stlstm_desc* d, const float* x, const float* h, const float* c, const float* m,
-                  const float* Wx, const float* Wh, const float* Wm, const float* Wo, const float* Wlast,
-                  const float* const* ln, const void* reserve, const float* dh_new, const float* dc_new,
-                  const float* dm_new, const float* ddc, const float* ddm, float* dx, float* dh, float* dc, float* dm,
-                  float* dWx, float* dWh, float* dWm, float* dWo, float* dWlast, float* const* dln, Carver& ws,
-                  hipStream_t stream);
+int stlstm_ln_fwd(const vpx_stlstm_desc* d, STFwdTensors t, void* reserve, void* workspace, size_t workspace_bytes, hipStream_t stream);
+int stlstm_ln_bwd(const vpx_stlstm_desc* d, STBwdTensors t, const void* reserve, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
 }  // namespace vpx
