@@ -1,5 +1,5 @@
 """The stride-1 'same' convolution in plain float64 — vpx_conv2d_nhwc_fwd, vpx_conv2d_nhwc_fwd_ex and vpx_conv2d_nhwc_bwd (csrc/vpx_api.hip,
-csrc/conv_api.hip; plain_conv / plain_wgrad / launch_colsum in csrc/vpx_host.h) — with the case tables of tests/test_gpu_conv_same.py (GPU parity)
+csrc/conv_same_api.hip; plain_conv / plain_wgrad / launch_colsum in csrc/vpx_host.h) — with the case tables of tests/test_gpu_conv_same.py (GPU parity)
 and tests/test_conv_same_host.py (the conditions on the inputs, the dry run and the refusals, on the CPU). Nothing here touches the GPU or imports
 the package.
 

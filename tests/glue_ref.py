@@ -1,5 +1,5 @@
 """The stage glue in plain float64 — vpx_conv2d_ex_fwd / _fwd_split / _fwd_from_split / _bwd / _bwd_ex and vpx_conv2d_act_fwd / _bwd
-(csrc/conv_api.hip: stride-1/2 convolution and transposed convolution + bias + LeakyReLU / ReLU, forward and backward) — with the case
+(csrc/glue_fwd_api.hip, csrc/glue_bwd_api.hip: stride-1/2 convolution and transposed convolution + bias + LeakyReLU / ReLU, forward and backward) — with the case
 tables of tests/test_gpu_glue.py (GPU parity) and tests/test_glue_host.py (the conditions on the inputs, the routes each case takes, the
 dry run and the refusals, on the CPU). Nothing here touches the GPU or imports the package.
 

@@ -1,5 +1,5 @@
 """The stage-glue family on the CPU: the fp64 statement of tests/glue_ref.py checked against closed forms; the routes of
-csrc/conv_api.hip restated in Python, checked against the library's own answers (vpx_conv2d_ex_takes_split, vpx_conv2d_ex_bwd_uses_split)
+csrc/glue_fwd_api.hip / glue_bwd_api.hip restated in Python, checked against the library's own answers (vpx_conv2d_ex_takes_split, vpx_conv2d_ex_bwd_uses_split)
 and against the tables — every route has a case, every neighbour falls outside its gate; the conditions under which
 tests/test_gpu_glue.py may hold the kernels to the project's bars (the reference's own fp32 run stays inside a fifth of them; next to
 nothing sits on the activation's kink); and — in a dry run (VPX_OPT_DRY_RUN, as tests/test_workspace_contract.py) — every case through
@@ -87,7 +87,7 @@ def test_bias_gradient_is_the_column_sum_of_the_masked_gy():
         assert bool((t["gy"][~R.off_kink(ref["pre"], ref["y"])] == 0).all())
 
 
-# ---- the routes of csrc/conv_api.hip, restated ---------------------------------------------------------------------------------------
+# ---- the routes of csrc/glue_fwd_api.hip (glue_route) and csrc/glue_bwd_api.hip (glue_bwd_plan), restated ---------------------------------------------------------------------------------------
 def conv_small_kind(c):                                   # csrc/conv_small.hip
     tr, N, Ci, Co, kh, kw, s, p, oph, opw, H, W = c
     if s != 1 or kh != kw:
@@ -101,7 +101,7 @@ def conv_small_kind(c):                                   # csrc/conv_small.hip
     return 0
 
 
-def wgrad_small_applicable(c):                            # csrc/lstm_bwd.hip (plain convolutions only: ex_bwd_impl)
+def wgrad_small_applicable(c):                            # csrc/lstm_bwd.hip (plain convolutions only: glue_wgrad_rule)
     tr, N, Ci, Co, kh, kw, s, p, oph, opw, H, W = c
     if tr or s != 1 or kh != kw:
         return None
@@ -119,7 +119,7 @@ def c16_applicable(c, prec, exp=0):                       # csrc/conv16.hip
     return (not exp & Exp.NO_C16 and prec == "bf16x3" and (kh, kw, s, p) == (3, 3, 1, 1) and Co == 16 and Ci % 16 == 0 and 16 <= Ci <= 64)
 
 
-def ex_wgrad_split(c, prec, exp=0):                       # csrc/conv_api.hip (at the default MFMA shape)
+def ex_wgrad_split(c, prec, exp=0):                       # csrc/glue_bwd_api.hip: glue_wgrad_rule (at the default MFMA shape)
     tr, N, Ci, Co, kh, kw, s, p, oph, opw, H, W = c
     return (not exp & Exp.GLUE_WGRAD_TAPGROUP and prec == "bf16x3" and Ci % 8 == 0 and Co % 8 == 0 and kh <= 2 * s + 1 and kw <= 2 * s + 1
             and kh * kw > 1 and wgrad_small_applicable(c) is None)

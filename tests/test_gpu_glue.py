@@ -1,6 +1,6 @@
 """The stage glue on the GPU — vpx_conv2d_ex_fwd / _fwd_from_split / _bwd_ex (behind ops.conv2d_ex and ops.conv2d_ex_from_split) and
 vpx_conv2d_act_fwd / _bwd (behind stphy_ops.conv2d_act) — against the fp64 statement of tests/glue_ref.py, whose tables walk every route
-of csrc/conv_api.hip: the streaming kernels of conv_small.hip in both forms, the first-generation implicit GEMM (stride 1 and 2, flipped
+of csrc/glue_fwd_api.hip / glue_bwd_api.hip: the streaming kernels of conv_small.hip in both forms, the first-generation implicit GEMM (stride 1 and 2, flipped
 taps, the four phase launches with their tap map, 4-wave and 8-wave workgroups), conv16.hip and convq.hip on split input, launch_colsum
 in its vector and scalar form with and without a split copy, the data gradient as the adjoint layer with every output padding on the
 first generation and on convq, and the weight gradient on wgrad_small_kernel, on launch_wgrad per stride residue and on wgrad2_kernel's
@@ -24,7 +24,9 @@ writes at the end of a `-m gpu` session — under this file's test names); worst
   test_convq_forward_with_output_...    y 5.6e-6
   test_data_gradient_on_convq_...       y 7.5e-6, dx 7.6e-6 (4x4 s2 on 9x12), dw 6.5e-6; GLUE_DGRAD_GEN1 off against on 2.0e-7
   test_deterministic_mode_...           dx 7.6e-6, dw 6.1e-6; the second run equal bit for bit
-No case needed a bar other than the table's. Not measured: nothing — every test of the file ran. 296 tests; the file takes 5.4 s."""
+  test_backward_that_wants_dx_or_dw_... y 4.8e-6, dx 7.6e-6, dw 6.1e-6, db 1.0e-7 (the calls for dx or dw alone give the full call's figures);
+                                        in deterministic mode equal to the full call bit for bit
+No case needed a bar other than the table's. Not measured: nothing — every test of the file ran. 298 tests; the file takes 4.8 s."""
 import ctypes
 
 import pytest
@@ -47,15 +49,16 @@ def _hold(parity_log, name, got, ref, bar):
     return e
 
 
-def _run(vpx, table, i, prec, relu=False, grads=True):
-    """Case i through ops.conv2d_ex (relu: stphy_ops.conv2d_act) under its variant: (y, dx, dw, db or None)."""
+def _run(vpx, table, i, prec, relu=False, grads=True, need=(True, True)):
+    """Case i through ops.conv2d_ex (relu: stphy_ops.conv2d_act) under its variant: (y, dx, dw, db or None). need: whether x / w require a
+    gradient (a bias always does); what is not wanted comes back as None."""
     c, v = R.TABLES[table][i], R.variant(table, i)
     tr, N, Ci, Co, kh, kw, s, p, oph, opw, H, W = c
     t, ref, _ = R.case(table, i, relu)
     x = t["x"].cuda()
     if v["channels_last"]:
         x = x.contiguous(memory_format=torch.channels_last)
-    leaves = [x.requires_grad_(grads), t["w"].cuda().requires_grad_(grads)] + ([t["b"].cuda().requires_grad_(grads)] if v["bias"] else [])
+    leaves = [x.requires_grad_(grads and need[0]), t["w"].cuda().requires_grad_(grads and need[1])] + ([t["b"].cuda().requires_grad_(grads)] if v["bias"] else [])
     b = leaves[2] if v["bias"] else None
     with torch.set_grad_enabled(grads):
         if relu:
@@ -67,9 +70,11 @@ def _run(vpx, table, i, prec, relu=False, grads=True):
     if not grads:
         return y, None, None, None
     # torch.autograd.grad hands out what the backward returned (a leaf's .grad would be restrided to the leaf's own layout)
-    g = torch.autograd.grad(y, leaves, t["gy"].cuda())
-    assert g[0].shape == x.shape and g[0].permute(0, 2, 3, 1).is_contiguous() and g[1].shape == t["w"].shape
-    return y, g[0], g[1], (g[2] if v["bias"] else None)
+    wanted = [k for k, leaf in enumerate(leaves) if leaf.requires_grad]
+    g = dict(zip(wanted, torch.autograd.grad(y, [leaves[k] for k in wanted], t["gy"].cuda())))
+    assert 0 not in g or (g[0].shape == x.shape and g[0].permute(0, 2, 3, 1).is_contiguous())
+    assert 1 not in g or g[1].shape == t["w"].shape
+    return y, g.get(0), g.get(1), g.get(2)
 
 
 def _hold_all(parity_log, out, ref, prec, tag=""):
@@ -80,6 +85,16 @@ def _hold_all(parity_log, out, ref, prec, tag=""):
             assert not bool(torch.isnan(g).any()), k
             _hold(parity_log, k + tag, g, ref[k], grad)
     assert (out[3] is None) == (ref["db"] is None)
+
+
+def _deterministic(vpx, fn):
+    prev = torch.are_deterministic_algorithms_enabled()
+    torch.use_deterministic_algorithms(True)
+    try:
+        return fn()
+    finally:
+        torch.use_deterministic_algorithms(prev)
+        vpx.ops.sync_determinism()
 
 
 # ---- ops.conv2d_ex in both operand modes: phases, strides, flipped taps, the few-channel layers ------------------------------------------
@@ -213,14 +228,32 @@ def test_data_gradient_on_convq_with_a_padded_adjoint_vs_fp64_and_first_generati
 @pytest.mark.parametrize("table,i", R.DETERMINISTIC, ids=_ids(R.DETERMINISTIC))
 def test_deterministic_mode_gives_bit_equal_gradients(vpx, parity_log, table, i):
     ref = R.case(table, i)[1]
-    prev = torch.are_deterministic_algorithms_enabled()
-    torch.use_deterministic_algorithms(True)
-    try:
-        a = _run(vpx, table, i, "bf16x3")
-        b = _run(vpx, table, i, "bf16x3")
-    finally:
-        torch.use_deterministic_algorithms(prev)
-        vpx.ops.sync_determinism()
+    a, b = _deterministic(vpx, lambda: (_run(vpx, table, i, "bf16x3"), _run(vpx, table, i, "bf16x3")))
     _hold_all(parity_log, a, ref, "bf16x3")
     for k, g, h in zip(("y", "dx", "dw", "db"), a, b):
         assert (g is None and h is None) or torch.equal(g, h), k
+
+
+PARTIAL = [("CONVQ_BWD", 0), ("SPLIT", 1)]
+
+
+@pytest.mark.parametrize("table,i", PARTIAL, ids=_ids(PARTIAL))
+def test_backward_that_wants_dx_or_dw_alone_vs_fp64_and_the_full_call(vpx, parity_log, table, i):
+    """The backward's workspace carve depends on what is wanted (csrc/glue_bwd_api.hip: the split copy of dy and the adjoint's convq pack
+    for dx, the split copies of dy and x for dw). (x, w) requiring gradients as (1, 1), (1, 0) and (0, 1), on the layer whose data gradient
+    runs on convq and on the one whose weight gradient alone reads split operands: every gradient a call produces holds the fp64 bars,
+    and in deterministic mode equals the full call's bit for bit."""
+    ref = R.case(table, i)[1]
+    for need in ((True, True), (True, False), (False, True)):
+        out = _run(vpx, table, i, "bf16x3", need=need)
+        assert (out[1] is not None, out[2] is not None) == need
+        fwd, grad = R.BARS["bf16x3"]
+        _hold(parity_log, f"y.need{need[0]:d}{need[1]:d}", out[0], ref["y"], fwd)
+        for k, g in zip(("dx", "dw", "db"), out[1:]):
+            if g is not None:
+                assert not bool(torch.isnan(g).any()), k
+                _hold(parity_log, f"{k}.need{need[0]:d}{need[1]:d}", g, ref[k], grad)
+    full, only_dx, only_dw = _deterministic(vpx, lambda: [_run(vpx, table, i, "bf16x3", need=n) for n in ((True, True), (True, False), (False, True))])
+    assert torch.equal(only_dx[1], full[1]) and torch.equal(only_dw[2], full[2])
+    for part in (only_dx, only_dw):
+        assert (part[3] is None and full[3] is None) or torch.equal(part[3], full[3])

@@ -1,5 +1,5 @@
 """The fused training tail against plain float64 (tests/train_tail_ref.py): the decoupling term (`ops.decouple_term`,
-`ops.decouple_term_batched`: csrc/pointwise.hip behind the adapter contractions csrc/conv_api.hip chooses), the MSE value and gradient
+`ops.decouple_term_batched`: csrc/pointwise.hip behind the adapter contractions csrc/decouple_api.hip chooses), the MSE value and gradient
 (`ops.mse_loss`) and the flat-bucket Adam update (`ops.adam_step`), both csrc/train_tail.hip — at the sizes where their unrolled loops,
 remainders, block caps, alignment paths and launch choices change.
 

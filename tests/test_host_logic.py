@@ -155,6 +155,38 @@ def test_stlstm_reserve_offsets_are_spelled_in_one_place():
         assert all(w in text for w in wanted) and not pointer_sum.search(text), name
 
 
+def test_glue_gates_are_asked_in_one_place():
+    """The stage glue decides its routes once: under csrc/, each kernel gate is called from exactly one function — glue_route
+    (csrc/glue_fwd_api.hip), the weight gradient's from glue_wgrad_rule (csrc/glue_bwd_api.hip) — and the convq problem of a layer is
+    built in at most two. conv_api.hip is gone, and no glue file sizes a slot by arithmetic on a size query's result."""
+    owners = {"c16_applicable": {("glue_fwd_api.hip", "glue_route")}, "conv_small_kind": {("glue_fwd_api.hip", "glue_route")},
+              "exq_preferred": {("glue_fwd_api.hip", "glue_route")}, "wgrad_small_applicable": {("glue_bwd_api.hip", "glue_wgrad_rule")}}
+    callers, n = {k: set() for k in list(owners) + ["exq_problem"]}, 0
+    declared = re.compile(r"^(?:static\s+)?(?:inline\s+)?(?:bool|int)\s+(\w+)\(")   # its own declaration or definition, in column 0
+    for path in _sources(("vp-suite_amd/csrc", (".hip", ".h"))):
+        n += 1
+        func = None
+        for ln in open(path):
+            if ln[:1] not in (" ", "\t", "\n", "/", "#", "}", "{") and "(" in ln:   # a definition starts in column 0
+                func = ln.split("(")[0].split()[-1]
+            m = declared.match(ln)
+            for name in callers:
+                if re.search(r"\b" + name + r"\(", ln.split("//")[0]) and not (m and m.group(1) == name):
+                    callers[name].add((os.path.basename(path), func))
+    assert n > 30 and {k: callers[k] for k in owners} == owners, callers
+    assert callers["exq_problem"] and callers["exq_problem"] <= {("glue_fwd_api.hip", "glue_route"), ("glue_bwd_api.hip", "glue_bwd_plan")}, callers
+    csrc = os.path.join(ROOT, "vp-suite_amd", "csrc")
+    assert not os.path.exists(os.path.join(csrc, "conv_api.hip"))
+    query = r"vpx_\w+_workspace_bytes\([^()]*\)"
+    for name in ("glue_fwd_api.hip", "glue_bwd_api.hip", "conv_same_api.hip", "decouple_api.hip"):
+        text = "\n".join(ln.split("//")[0] for ln in open(os.path.join(csrc, name)))
+        held = "|".join([query] + [r"\b" + v + r"\b" for v in re.findall(r"(\w+)\s*=\s*vpx_\w+_workspace_bytes\(", text)])   # ... or on a variable that holds one
+        arithmetic = re.compile(r"(?:%s)\s*\)*\s*[-+*/]|[-+*/]\s*\(*\s*(?:%s)" % (held, held))
+        sample = re.compile(arithmetic.pattern.replace(query, query + r"|\bneed\b"))
+        assert sample.search("ws.take((need" + " - 512) / 4)") and arithmetic.search("take((vpx_conv2d_ex_split_workspace_bytes(d)" + " - 512) / 4)")
+        assert "ws.take(" in text and not arithmetic.search(text), (name, arithmetic.search(text))
+
+
 def test_option_restores_the_previous_value_on_exception(vpx):
     """_lib.option / _lib.experiment: the value holds inside the block and the one from before comes back when the block raises — for all
     five options, nested. In a dry run: nothing here needs a GPU. vpx_set_option stores any value, named or not."""

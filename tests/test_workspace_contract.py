@@ -367,6 +367,66 @@ def test_stage_glue(L, det):
                     _ok(L, rc, tag + " bwd_ex (dw only)")
 
 
+# One descriptor per route of the stage glue (csrc/glue_fwd_api.hip: GlueRoute; csrc/glue_bwd_api.hip: glue_bwd_plan), from the tables of
+# tests/glue_ref.py: (table, index, precision, what is called, takes_split, bwd_uses_split, names tests/test_glue_host.py::routes must give)
+GLUE_ROUTES = [
+    ("C16", 0, "bf16x3", "from_split", 2, 1, {"fwd.split.c16"}),
+    ("CONVQ_FWD", 0, "bf16x3", "from_split", 2, 1, {"fwd.split.convq"}),                 # convq, plain
+    ("CONVQ_FWD", 1, "bf16x3", "from_split", 2, 1, {"fwd.split.convq"}),                 # convq, phase form
+    ("SPLIT", 0, "bf16x3", "from_split", 1, 1, {"fwd.split.gen1.conv.s1"}),              # first generation, one launch
+    ("SPLIT", 4, "bf16x3", "from_split", 1, 1, {"fwd.split.gen1.phases"}),               # first generation, four phase launches
+    ("SMALL_KIND1", 0, "bf16x3", "fwd", 0, 0, {"fwd.small1.many"}),
+    ("SMALL_KIND2", 0, "bf16x3", "fwd", 0, 0, {"fwd.small2"}),
+    ("SMALL_KIND3", 0, "bf16x3", "fwd", 0, 0, {"fwd.small3.many"}),
+    ("FLIP", 0, "bf16x3", "fwd", 0, 0, {"fwd.gen1.flip"}),
+    ("PHASES", 0, "bf16x3", "fwd", 0, 0, {"fwd.gen1.phases"}),
+    ("CONVQ_BWD", 0, "bf16x3", "bwd", 1, 1, {"dx.convq.op01", "dw.wgrad2g", "colsum.v4.split_copy"}),   # convq data gradient
+    ("SPLIT", 1, "bf16x3", "bwd", 1, 1, {"dx.gen1.phases", "dw.wgrad2g"}),                              # split weight gradient, gen1 data gradient
+    ("SMALL_WGRAD", 0, "bf16x3", "bwd", 0, 0, {"dx.gen1.flip", "dw.small<16,1,3>"}),                    # small weight gradient
+    ("PHASES", 0, "f32", "bwd", 0, 0, {"dx.gen1.conv.s2", "dw.launch_wgrad"}),                          # neither
+]
+
+
+@pytest.mark.parametrize("case", GLUE_ROUTES, ids=[f"{c[0]}{c[1]}-{c[2]}-{c[3]}" for c in GLUE_ROUTES])
+def test_glue_routes_refuse_short_buffers_and_accept_exact_ones(L, case):
+    """Every route of the stage glue: the size its query returns is accepted at an aligned and at an odd base, one byte less is refused
+    with VPX_ERR_WORKSPACE — the backward also with dx, dw or db absent (its carve depends on what is wanted, its size test does not).
+    The queries show the route as far as they can (vpx_conv2d_ex_takes_split, vpx_conv2d_ex_bwd_uses_split: asserted); the rest is held
+    against the restatement of the routes in tests/test_glue_host.py."""
+    import glue_ref as R
+    import test_glue_host as GH
+    table, i, prec, call, takes, uses, names = case
+    c = getattr(R, table)[i] if table not in R.TABLES else R.TABLES[table][i]
+    tab, idx = (table, i) if table in R.TABLES else ("SMALL", R.SMALL.index(c))
+    v = R.variant(tab, idx)
+    tr, N, Ci, Co, kh, kw, s, p, oph, opw, H, W = c
+    L.vpx_set_deterministic(0)
+    d = ConvDesc(N, H, W, Ci, Co, kh, kw, s, p, tr, v["slope"], GH.PRECS[prec], oph, opw)
+    dp = ctypes.byref(d)
+    assert L.vpx_conv2d_ex_takes_split(dp) == takes and L.vpx_conv2d_ex_bwd_uses_split(dp) == uses
+    assert names <= GH.routes(c, prec, v, training=call == "bwd", from_split=call == "from_split"), GH.routes(c, prec, v, training=call == "bwd")
+
+    def run(base, nb, absent=None):
+        ws = ctypes.c_void_p(base)
+        if call == "fwd":
+            return [L.vpx_conv2d_ex_fwd(dp, _fake(1), _fake(2), _fake(3), _fake(4), ws, nb, None)]
+        if call == "from_split":
+            return [L.vpx_conv2d_ex_fwd_from_split(dp, _fake(8), 0, 0, 1, _fake(2), _fake(3), _fake(4), _fake(9) if Co % 8 == 0 else None, packed, ws, nb, None)
+                    for packed in (0, 1)]
+        g = {"dx": _fake(6), "dw": _fake(7), "db": _fake(10)}
+        g[absent] = None
+        return [L.vpx_conv2d_ex_bwd_ex(dp, _fake(1), x_sp, _fake(2), _fake(4), _fake(5), g["dx"], g["dw"], g["db"], ws, nb, None)
+                for x_sp in ((None, _fake(8)) if uses else (None,))]
+    query = {"fwd": L.vpx_conv2d_ex_workspace_bytes, "from_split": L.vpx_conv2d_ex_split_workspace_bytes, "bwd": L.vpx_conv2d_ex_bwd_workspace_bytes}[call]
+    nb = query(dp)
+    assert nb > 256
+    for absent in ((None, "dx", "dw", "db") if call == "bwd" else (None,)):
+        for base in (WS_BASE, WS_BASE_ODD):
+            for rc in run(base, nb, absent):
+                _ok(L, rc, f"{call} base={base:#x} absent={absent}", allow_unsupported=False)
+        assert run(WS_BASE, nb - 1, absent) == [E_WS] * len(run(WS_BASE, nb, absent)), (call, absent)
+
+
 def test_trajgru_sequence(L):
     """vpx_trajgru_seq_fwd / _bwd over the default EF-TrajGRU blocks (ef_traj_gru.py:31-75) and small / ragged shapes, every operand mode."""
     from vp_suite_amd._lib import TrajGRUDesc

@@ -1,4 +1,4 @@
-"""The fused training tail in plain float64: the decoupling term (csrc/pointwise.hip, csrc/conv_api.hip), the MSE value and gradient
+"""The fused training tail in plain float64: the decoupling term (csrc/pointwise.hip, csrc/decouple_api.hip), the MSE value and gradient
 and the flat-bucket Adam update (csrc/train_tail.hip), with the case tables of tests/test_gpu_train_tail.py (GPU parity) and
 tests/test_train_tail_host.py (the conditions on the inputs, on the CPU). Nothing here touches the GPU or imports the package.
 

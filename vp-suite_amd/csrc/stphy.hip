@@ -10,7 +10,7 @@
 //     a bias; the merge is (64, 128) at the default width and must run in f32 too.
 //     Backward: da / db = the adjoint 1x1 layers on dy, dW = the two weight gradients written side by side, dbias = column sums —
 //     all fixed-order reductions (no float atomics under vpx_set_deterministic(1)).
-// (ReLU on the convolution path — vpx_conv2d_act_fwd / _bwd — lives with the layer launchers in conv_api.hip.)
+// (ReLU on the convolution path — vpx_conv2d_act_fwd / _bwd — lives with the layer launchers in glue_fwd_api.hip / glue_bwd_api.hip.)
 #include "vpx_host.h"
 
 namespace vpx {

@@ -116,63 +116,4 @@ int vpx_split_convert(const float* x, void* x_split, long long n_pixels, int C, 
     return VPX_OK;
 }
 
-/* ---- plain conv ------------------------------------------------------------------------------------------------ */
-size_t vpx_conv2d_workspace_bytes(int Ci, int Co, int kh, int kw) {
-    if (Ci < 1 || Co < 1 || kh < 1 || kw < 1) return 0;
-    ConvStage st[MAX_STAGE];
-    int chunks = 0;
-    const int segC[1] = {Ci};
-    // one query serves vpx_conv2d_nhwc_fwd (stage size of the 4-group tile) and vpx_conv2d_nhwc_fwd_ex (plain_conv: stage size of
-    // the tiling it picks) in every operand mode: the larger of the two packs. (Round 4 sized only the first — the 5x5 layers
-    // with <= 32 outputs of the TrajGRU flow generator then packed 4 % more than the workspace held.)
-    size_t best = plain_conv_wpk_floats(Ci, Co, kh, kw) * 4;
-    for (int prec = VPX_PREC_F32; prec <= VPX_PREC_BF16; ++prec) {
-        if (build_stages(st, &chunks, segC, 1, kh * kw, pick_stage_channels(segC, 1, kh, kw, 4, prec), prec) < 0) return 0;
-        const size_t b = packed_weight_bytes(plain_tiles(Co), chunks, plain_groups(Co), prec);
-        if (b > best) best = b;
-    }
-    return align256(best) + 256;
-}
-
-int vpx_conv2d_nhwc_fwd(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Ci,
-                        int Co, int kh, int kw, int precision, void* workspace, size_t workspace_bytes, void* stream_) {
-    if (!x || !w || !y || N < 1 || H < 1 || W < 1 || Ci < 1 || Co < 1 || !(kh & 1) || !(kw & 1) || kh > 7 || kw > 7) {
-        set_error("vpx_conv2d_nhwc_fwd: bad argument");
-        return VPX_ERR_ARG;
-    }
-    if ((precision < VPX_PREC_F32 || precision > VPX_PREC_BF16)) { set_error("vpx_conv2d_nhwc_fwd: precision %d not implemented", precision); return VPX_ERR_UNSUPPORTED; }
-    hipStream_t stream = (hipStream_t)stream_;
-    ConvPlan P{};
-    int chunks = 0;
-    const int segC[1] = {Ci};
-    P.nstage = build_stages(P.stage, &chunks, segC, 1, kh * kw, pick_stage_channels(segC, 1, kh, kw, 4, precision), precision);
-    if (P.nstage < 0) { set_error("vpx_conv2d_nhwc_fwd: too many channel stages"); return VPX_ERR_UNSUPPORTED; }
-    const int n_tiles = plain_tiles(Co);
-    if (!workspace || workspace_bytes < vpx_conv2d_workspace_bytes(Ci, Co, kh, kw)) {
-        set_error("vpx_conv2d_nhwc_fwd: workspace too small");
-        return VPX_ERR_WORKSPACE;
-    }
-    Carver ws(workspace, workspace_bytes);
-    float* wpk = ws.take(packed_weight_bytes(n_tiles, chunks, plain_groups(Co), precision) / sizeof(float));
-    VPX_CHECK_CARVE(ws, "vpx_conv2d_nhwc_fwd");
-    PackDesc pd{};
-    pd.seg[0] = PackSeg{w, (long long)Ci * kh * kw, kh * kw, 0, Ci};
-    memcpy(pd.stage, P.stage, sizeof(ConvStage) * P.nstage);
-    pd.nstage = P.nstage; pd.chunks_total = chunks; pd.prec = precision; pd.taps = kh * kw;
-    fill_plain_pack(pd, Co, 0);
-    VPX_CHECK_HIP(launch_pack_weights(pd, wpk, stream));
-    P.B = N; P.H = H; P.W = W; P.kh = kh; P.kw = kw;
-    P.tiles_x = (W + TILE_W - 1) / TILE_W; P.tiles_y = (H + TILE_H - 1) / TILE_H;
-    P.nseg = 1;
-    P.seg[0] = ConvSeg{x, (long long)H * W * Ci, Ci, 0};
-    P.chunks_total = chunks; P.prec = precision;
-    P.a_bytes = conv_a_bytes(P.stage, P.nstage, kh, kw);
-    P.wpk = wpk;
-    PlainEpiArgs ea{};
-    ea.bias = bias; ea.Co = Co; ea.split = Co; ea.ng = plain_groups(Co);
-    ea.out0 = y; ea.bstride0 = (long long)H * W * Co; ea.ld0 = Co;
-    VPX_CHECK_HIP(launch_conv_plain_f32(P, ea, n_tiles, stream));
-    return VPX_OK;
-}
-
 }  // extern "C"

@@ -266,7 +266,7 @@ static inline ConvLSTMReserve convlstm_reserve(const vpx_convlstm_desc* d, const
     return r;
 }
 
-// ---- plain stride-1 'same' convolution / weight gradient on NHWC tensors (shared by conv_api, stlstm LN path) ----
+// ---- plain stride-1 'same' convolution / weight gradient on NHWC tensors (shared by conv_same_api, decouple_api, the stlstm LN path, ST-Phy, PhyDNet) ----
 struct ConvGeo { int N, H, W; };
 
 // y (+)= conv(src; w) with Co outputs; `transposed`: contraction over w's O axis (data gradient). Returns packed floats used.
@@ -445,5 +445,30 @@ size_t stlstm_ln_reserve_bytes(const vpx_stlstm_desc* d);
 size_t stlstm_ln_workspace_bytes(const vpx_stlstm_desc* d);
 int stlstm_ln_fwd(const vpx_stlstm_desc* d, STFwdTensors t, void* reserve, void* workspace, size_t workspace_bytes, hipStream_t stream);
 int stlstm_ln_bwd(const vpx_stlstm_desc* d, STBwdTensors t, const void* reserve, void* workspace, size_t workspace_bytes, hipStream_t stream);
+
+// ---- EF stage glue: general conv / transposed conv + bias + activation (glue_fwd_api.hip; its backward: glue_bwd_api.hip) ----
+struct GlueGeo { int Ho, Wo; };
+int glue_check(const vpx_conv_desc* d, GlueGeo& g);                    // the descriptor's refusals; the output shape
+int glue_act_check(const vpx_conv_desc* d, int act, const char* who);   // activation codes beyond the descriptor's LeakyReLU
+// The kernel that takes a layer. fp32 input: SMALL, or the first generation in the form the layer needs. Split input: C16 or CONVQ where
+// their gates hold (they exclude each other: Co == 16 against Co >= 64), else the first generation, or NONE (f32 operands, Ci % 8).
+enum class GlueRoute {
+    NONE,
+    SMALL,         // few-channel layers: the streaming kernels (conv_small.hip), kind 1-3
+    GEN1,          // convolution: one implicit-GEMM launch, y[o] = sum_k x[o*s - pad + k] w[k]
+    GEN1_FLIP,     // transposed, stride 1: y[o] = sum_k x[o + pad - k] w[k] == correlation with the flipped kernel, origin -(k-1-pad)
+    GEN1_PHASES,   // transposed, stride 2: output phase (py, px) is a stride-1 correlation of x with the taps k == (p + pad) mod 2 of that axis
+    C16,           // 3x3 stride-1 layers with 16 output channels: the whole K of a tile resident (conv16.hip)
+    CONVQ,         // >= 64 output channels on a grid that fills the chip: the schedule-driven K = 32 kernel (convq.hip)
+};
+static inline bool glue_on_gen1(GlueRoute r) { return r == GlueRoute::GEN1 || r == GlueRoute::GEN1_FLIP || r == GlueRoute::GEN1_PHASES; }
+// A route and what it needs: the streaming kind (SMALL), the layer's convq problem (CONVQ; built once, owned by the call) and the weight
+// pack's size in whole 256-byte units, the one workspace slot of a forward (fp32 input: the first generation's pack on every route).
+struct GlueChoice { GlueRoute route; int kind; size_t pack_bytes; ConvQProblem q; };
+void glue_route(const vpx_conv_desc* d, const GlueGeo& g, bool x_split, int act, bool y_split, GlueChoice& c);
+// The tensors of one forward. x: fp32 NHWC, or (x_split) the split format with BYTES between batch items / the nT steps of one. packed:
+// `wpk` still holds this layer's pack of an earlier call (GEN1_PHASES packs per phase and ignores it).
+struct GlueIO { const void* x; long long x_bstride, x_tstride; int x_nT; const float *w, *bias; float* y; char *y_split, *wpk; bool x_split, packed; int act; };
+int glue_forward(const vpx_conv_desc* d, const GlueGeo& g, GlueChoice& c, const GlueIO& io, hipStream_t stream);
 
 }  // namespace vpx

@@ -445,7 +445,7 @@ struct WgradArgs {
     int n_ctiles;
     WgradCTile ct[WG_MAX_CTILES];
     float* slabs;             // [n_slices][taps][N4][Ct]
-    // generalisation for strided / transposed convolutions (conv_api.hip); all 0 = the stride-1 "same" case above
+    // generalisation for strided / transposed convolutions (glue_fwd_api.hip); all 0 = the stride-1 "same" case above
     int a_sub;                // 1: the activation operand is the sub-image (gy*a_sy + a_oy, gx*a_sx + a_ox) of a larger image
     int a_sy, a_sx, a_oy, a_ox;
     int a_Hs, a_Ws;           // valid rows / columns of the sub-image

@@ -61,7 +61,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // QF: the same kernel on v_mfma_f32_16x16x32_bf16 (vpx_set_option(VPX_OPT_MFMA_SHAPE, 1)): a K = 32 step is two tile rows of the
 // item, a wave's 64 gate rows x 32 channels x tap group are 4 x 2 accumulator tiles of 16x16 per tap (the same 160 registers),
 // the same fragment bytes per MFMA cycle.
-// GLUE (round 6, QF only): the weight gradient of a stage-glue layer's stride residue (conv_api.hip, strided_wgrad) on the same machinery —
+// GLUE (round 6, QF only): the weight gradient of a stage-glue layer's stride residue (glue_bwd_api.hip, strided_wgrad) on the same machinery —
 // kh x kw <= 3 x 3 taps (a 4x4 stride-2 layer's residues have 2 x 2, a 3x3 stride-2 layer's 2 x 2 / 2 x 1 / 1 x 2), the tap (0,0) at
 // (org_y, org_x) instead of (-1,-1), and the activation operand a SUB-IMAGE of a larger one: position (y, x) of the walk reads pixel
 // (a_sy * y + a_oy, a_sx * x + a_ox) of an image a_Wfull pixels wide. All of it is linear in the position, so a copy is still a per-item

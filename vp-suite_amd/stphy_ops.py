@@ -1,6 +1,6 @@
 """ST-Phy's operators over the C ABI (include/vpx.h): a convolution layer with an activation code (ReLU in the epilogue of the launch
 that runs the layer), the encoder tail relu + L2 row normalisation, and the two-source 1x1 merge; one autograd Function each,
-forward and backward in libvpx_hip (csrc/conv_api.hip, csrc/stphy.hip).
+forward and backward in libvpx_hip (csrc/glue_fwd_api.hip, csrc/glue_bwd_api.hip, csrc/stphy.hip).
 
 As in phy_ops: activations keep the reference's logical shapes ([N,C,H,W]) and live channels-last in memory; whether a Function keeps
 its backward state is decided in the wrapper, where grad mode is visible; shapes are checked here, before any launch. CPU tensors
