@@ -222,6 +222,25 @@ size_t vpx_stlstm_wgrad_batch_workspace_bytes(const vpx_stlstm_desc* d);   /* d-
 int vpx_stlstm_wgrad_batch(const vpx_stlstm_desc* d, const void* dg8_split, const void* const* src5_split, float* dWx, float* dWh,
                            float* dWm, float* dWo, float* dWlast, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The plan of a step: which kernels a vpx_stlstm_step_fwd_ex / _bwd_ex call with this descriptor takes under the current
+ * vpx_set_deterministic / vpx_set_option state, filled by the functions that decide it for the calls themselves. No launch, no
+ * allocation. all_weight_grads: 1 = the backward is asked for all five weight gradients, 0 = at least one weight is frozen (a NULL dW).
+ *   forward   route (VPX_ST_ROUTE_*); o_split: K ranges of GEN1's conv_o as a plain convolution + pointwise gate (0: fused with the gate);
+ *             nt_o: conv_o's N-tile width in 16-column units on C5 / C5K (else 0); ks_g / ks_o: K chunks of the gate groups / of conv_o on
+ *             C5K (else 0); mw_g / mw_o: workgroup form of GEN1's gate / conv_o launch (2: 8 waves); ksplit_l: K ranges of conv_last on the
+ *             implicit-GEMM kernel; last_c1: conv_last on the streaming 1x1 kernel instead (operands 16-byte aligned)
+ *   backward  (zero with layer_norm) stw: the five weight gradients in one launch; c5: the k x k data gradients on the 16x16-tile kernel,
+ *             c5_ks[]: their K chunks (conv_o -> c_new, conv_o -> m_new, dx, dh, dm; 0 without c5); n_slices / stw_ns: K slices of the
+ *             first-generation / the one-launch weight gradients; dg_ksplit[] / dg_mw[]: K ranges and workgroup form of the
+ *             first-generation data gradients (conv_o's adjoint, conv_last's adjoint, dx, dh, dm)
+ * Returns what vpx_stlstm_workspace_bytes' checks refuse with (VPX_ERR_ARG, VPX_ERR_UNSUPPORTED), VPX_ERR_ARG for a NULL `out`. */
+enum { VPX_ST_ROUTE_LN = 0, VPX_ST_ROUTE_GEN1 = 1, VPX_ST_ROUTE_C5 = 2, VPX_ST_ROUTE_C5K = 3 };
+typedef struct vpx_stlstm_plan_info {
+    int32_t route, o_split, nt_o, ks_g, ks_o, mw_g, mw_o, ksplit_l, last_c1;
+    int32_t stw, c5, c5_ks[5], n_slices, stw_ns, dg_ksplit[5], dg_mw[5];
+} vpx_stlstm_plan_info;
+int vpx_stlstm_plan(const vpx_stlstm_desc* d, int all_weight_grads, vpx_stlstm_plan_info* out);
+
 /* Weights in reference layout: Wx [7Ch,Cin,k,k] Wh [4Ch,Ch,k,k] Wm [3Ch,Ch,k,k] Wo [Ch,2Ch,k,k] Wlast [Ch,2Ch,1,1].
  * ln: NULL or 8 pointers {x_gamma,x_beta,h_gamma,h_beta,m_gamma,m_beta,o_gamma,o_beta}, each in reference [C,H,W]. */
 int vpx_stlstm_step_fwd(const vpx_stlstm_desc* d, const float* x, const float* h, const float* c, const float* m,

@@ -93,6 +93,16 @@ class STLSTMShadows(ctypes.Structure):
     _fields_ = [("inp", ctypes.c_void_p * 5), ("out", ctypes.c_void_p * 3), ("dg8_out", ctypes.c_void_p)]
 
 
+class STLSTMPlanInfo(ctypes.Structure):
+    """vpx_stlstm_plan_info: the kernels a step with a descriptor takes (include/vpx.h), every field an int32."""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("route", "o_split", "nt_o", "ks_g", "ks_o", "mw_g", "mw_o", "ksplit_l", "last_c1", "stw", "c5")] +
+                [("c5_ks", ctypes.c_int32 * 5), ("n_slices", ctypes.c_int32), ("stw_ns", ctypes.c_int32), ("dg_ksplit", ctypes.c_int32 * 5),
+                 ("dg_mw", ctypes.c_int32 * 5)])
+
+
+ST_ROUTE_LN, ST_ROUTE_GEN1, ST_ROUTE_C5, ST_ROUTE_C5K = 0, 1, 2, 3
+
+
 class VpxError(RuntimeError):
     pass
 
@@ -127,6 +137,7 @@ SIGNATURES = {
     "vpx_stlstm_reserve_bytes": (sz, [_stlstm]),
     "vpx_stlstm_uses_split": (ci, [_stlstm]),
     "vpx_stlstm_defers_wgrad": (ci, [_stlstm]),
+    "vpx_stlstm_plan": (ci, [_stlstm, ci, vp]),
     "vpx_stlstm_wgrad_batch_workspace_bytes": (sz, [_stlstm]),
     "vpx_stlstm_wgrad_batch": (ci, [_stlstm, vp, vp] + [vp] * 5 + _ws),
     "vpx_stlstm_step_fwd": (ci, _stlstm_fwd),

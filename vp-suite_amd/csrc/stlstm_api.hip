@@ -124,6 +124,7 @@ int st_layout(const vpx_stlstm_desc* d, STLayout& L) {
     L.wpk_l = packed_weight_bytes(L.tiles128, L.chunks_l, L.ng_l, d->precision) / 4;
     L.ksplit_l = pick_ksplit(m_tiles * L.tiles128, L.nstage_l);
     L.route = st_route(d);
+    L.ks_g = L.ks_o = L.nt_o = 0;   // (C5K only)
     if (L.route == STRoute::C5) {
         L.c5_wc = align256(c5_wpk_bytes(d->Cin + d->Ch, d->Ch, 8, 4));
         L.c5_wm = align256(c5_wpk_bytes(d->Cin + d->Ch, d->Ch, 8, 3));
@@ -425,13 +426,19 @@ int gen1_out(const STFwdCtx& c) {
 }
 
 // ---- every route's launch 3: conv_last(mem) 1x1 -> lc ----
+// the streaming kernel's view of it (conv1.hip): what c1_applicable is asked about, by the call and by the plan query
+C1Args conv_last_c1(const vpx_stlstm_desc* d, const float* c_new, const float* m_new, const float* Wlast, float* lc) {
+    const int Ch = d->Ch;
+    C1Args c1{};
+    c1.x[0] = c_new; c1.x[1] = m_new; c1.xld[0] = c1.xld[1] = Ch; c1.xc[0] = c1.xc[1] = Ch;
+    c1.npix = (long long)d->B * d->H * d->W;
+    c1.w = Wlast; c1.w_sn = 2 * Ch; c1.w_sc = 1;
+    c1.y[0] = lc; c1.yld[0] = Ch; c1.ysplit = Ch; c1.Co = Ch;
+    return c1;
+}
 int conv_last(const STFwdCtx& c) {
     const STLayout& L = *c.L; const STFwdSlots& s = c.ws; const int Ch = c.d->Ch;
-    C1Args c1{};
-    c1.x[0] = c.t.out[1]; c1.x[1] = c.t.out[2]; c1.xld[0] = c1.xld[1] = Ch; c1.xc[0] = c1.xc[1] = Ch;
-    c1.npix = c.npix;
-    c1.w = c.t.Wlast; c1.w_sn = 2 * Ch; c1.w_sc = 1;
-    c1.y[0] = s.lc; c1.yld[0] = Ch; c1.ysplit = Ch; c1.Co = Ch;
+    C1Args c1 = conv_last_c1(c.d, c.t.out[1], c.t.out[2], c.t.Wlast, s.lc);
     if (c.r.last_split) {
         // the gate stage left c_new / m_new in the operand format as well: read THOSE (no fp32 -> (hi, lo) conversion in the kernel; round 6)
         c1.x[0] = reinterpret_cast<const float*>(s.cn_sp); c1.x[1] = reinterpret_cast<const float*>(s.mn_sp); c1.x_split = 1;
@@ -462,6 +469,22 @@ extern "C" {
 int vpx_stlstm_uses_split(const vpx_stlstm_desc* d) {
     if (check_st_desc(d) != VPX_OK || d->layout != VPX_LAYOUT_NHWC) return 0;
     return on_c5(st_route(d)) ? 1 : 0;
+}
+
+int vpx_stlstm_plan(const vpx_stlstm_desc* d, int all_weight_grads, vpx_stlstm_plan_info* out) {
+    int rc = check_st_desc(d);
+    if (rc != VPX_OK) return rc;
+    if (!out) { set_error("vpx_stlstm_plan: out is NULL"); return VPX_ERR_ARG; }
+    STLayout L;
+    if ((rc = st_layout(d, L)) != VPX_OK) return rc;
+    const STRouteChoice r = st_choice(d, L);
+    *out = vpx_stlstm_plan_info{};
+    out->route = (int)r.route; out->o_split = r.o_split; out->nt_o = r.nt_o; out->ks_g = L.ks_g; out->ks_o = L.ks_o;
+    out->mw_g = L.mw_g; out->mw_o = L.mw_o; out->ksplit_l = L.ksplit_l;
+    out->last_c1 = r.route != STRoute::LN && c1_applicable(conv_last_c1(d, nullptr, nullptr, nullptr, nullptr), d->precision) ? 1 : 0;
+    if (r.route == STRoute::LN) return VPX_OK;   // (the LayerNorm variant's backward has no forms to choose from)
+    rc = stlstm_bwd_plan(d, all_weight_grads != 0, out);
+    return (d->flags & VPX_FLAG_SAVE_FOR_BWD) ? rc : VPX_OK;   // (a descriptor that does not save is followed by no backward)
 }
 
 size_t vpx_stlstm_reserve_bytes(const vpx_stlstm_desc* d) {

@@ -152,6 +152,26 @@ STBwdChoice st_bwd_choice(const STBwdLayout& L, bool defer, float* const dW[5]) 
     return {stw, L.c5 && stw, defer};
 }
 
+}  // namespace
+
+namespace vpx {
+// the backward half of vpx_stlstm_plan (stlstm_api.hip): the layout and the choice as a call computes them
+int stlstm_bwd_plan(const vpx_stlstm_desc* d, bool all_weight_grads, vpx_stlstm_plan_info* out) {
+    STBwdLayout L;
+    const int rc = st_bwd_layout(d, L);
+    if (rc != VPX_OK) return rc;
+    float* const some = reinterpret_cast<float*>(out);   // (any non-NULL address: the choice asks which gradients are wanted, no more)
+    float* const dW[5] = {some, some, some, some, all_weight_grads ? some : nullptr};
+    const STBwdChoice r = st_bwd_choice(L, false, dW);
+    out->stw = r.stw; out->c5 = r.c5; out->n_slices = L.n_slices; out->stw_ns = L.stw_ns;
+    const STBwdLayout::DG* dg[5] = {&L.o, &L.l, &L.x, &L.h, &L.m};
+    for (int i = 0; i < 5; ++i) { out->c5_ks[i] = r.c5 ? L.c5_ks[i] : 0; out->dg_ksplit[i] = dg[i]->ksplit; out->dg_mw[i] = dg[i]->mw; }
+    return VPX_OK;
+}
+}  // namespace vpx
+
+namespace {
+
 // ---- what every stage's functions see of a call ----
 struct STBwdCtx {
     const vpx_stlstm_desc* d; const STBwdLayout* L; STBwdChoice r;

@@ -439,6 +439,7 @@ static inline STReserve stlstm_reserve(const vpx_stlstm_desc* d, const LAYOUT& L
 }
 // backward workspace of one ST-LSTM step: vpx_stlstm_step_bwd's own carve, measured (stlstm_bwd_api.hip)
 size_t stlstm_bwd_workspace_bytes(const vpx_stlstm_desc* d);
+int stlstm_bwd_plan(const vpx_stlstm_desc* d, bool all_weight_grads, vpx_stlstm_plan_info* out);   // vpx_stlstm_plan's backward fields
 // LayerNorm variant (stlstm_ln_api.hip): its reserve's size, the larger of its two carves (the backward's for a saving descriptor), the
 // two directions in either layout on the caller's whole workspace
 size_t stlstm_ln_reserve_bytes(const vpx_stlstm_desc* d);
