@@ -33,7 +33,8 @@
  * vpx_bn_relu_fwd / _bwd           BatchNorm + ReLU (+ MaxPool3d (1,2,2))   vp_suite/model_blocks/conv.py:22-27, models/unet3d.py:29
  * vpx_mmnist_frames                MovingMNISTOnTheFly.__getitem__ (a batch) vp_suite/datasets/mmnist_on_the_fly.py:78-104,133-147
  * vpx_frames_preprocess            VPDataset.preprocess (a batch of stored sequences)  vp_suite/base/base_dataset.py:233-273, datasets/mmnist.py:56-57
- * vpx_frames_postprocess           VPDataset.postprocess                    vp_suite/base/base_dataset.py:286-297
+ * vpx_clips_preprocess             the same for windows of long clips       vp_suite/datasets/kitti_raw.py:77-95, caltech_pedestrian.py:69-86
+ * vpx_frames_postprocess           VPDataset.postprocess                   vp_suite/base/base_dataset.py:286-297
  * vpx_actions_gather               the action rows of a batch of stored sequences  vp_suite/datasets/bair.py:60-61
  * vpx_frames_augment               the colour and erasing entries of VPDataset's augmentation list  vp_suite/base/base_dataset.py:19-23,135-141
  * vpx_frames_adapt                 ScaleToModel / ScaleToTest + TF.Resize   vp_suite/utils/compatibility.py:31-50, utils/models.py:7-64
@@ -627,6 +628,20 @@ enum { VPX_FRAMES_U8 = 0, VPX_FRAMES_U16 = 1, VPX_FRAMES_F32 = 2 };
 int vpx_frames_preprocess(const void* src, int dtype, long long N, int Tp, int H, int W, int Cs, const int* table, int B, int n_frames,
                           int seq_step, int ch, int cw, int oh, int ow, int C_out, double lo, double hi, float* out, void* stream);
 int vpx_frames_postprocess(const float* x, long long N, int C, int h, int w, double lo, double hi, unsigned char* out, void* stream);
+/* Windows of long clips (vp_suite/datasets/kitti_raw.py:77-95, caltech_pedestrian.py:69-86): src [total_frames, H, W, Cs] holds every clip
+ * of a split back to back, element types as above; clip_first [n_clips + 1] (int64, on the device) holds the first frame of each clip,
+ * its last entry total_frames; table [B, 6] (int32, on the device) holds per output sample (clip index, start frame within the clip,
+ * crop y0, crop x0, flip bits, 0). out [B, n_frames, C_out, oh, ow] is dense fp32 and output frame f of sample b is stored frame
+ * clip_first[clip] + start + f * seq_step. From the frame on, the pixels are those of vpx_frames_preprocess, computed by the same device
+ * function: the same scale, crop, resize, flips and gray repeat, bit for bit. One launch, no workspace, no atomics, no host sync; frame
+ * offsets are 64-bit (a split may hold tens of gigabytes). Return codes as vpx_frames_preprocess, with total_frames and n_clips among the
+ * sizes, n_clips > total_frames and (n_frames - 1) * seq_step >= total_frames VPX_ERR_ARG. `clip_first` and `table` live on the device, so
+ * the CALLER checks them: a row whose clip index is outside [0, n_clips), whose window leaves its clip (start < 0 or
+ * start + (n_frames - 1) * seq_step >= the clip's length), whose clip leaves src or whose box leaves the frame yields zeros and reads
+ * nothing out of bounds. */
+int vpx_clips_preprocess(const void* src, int dtype, long long total_frames, int H, int W, int Cs, const long long* clip_first, long long n_clips,
+                         const int* table, int B, int n_frames, int seq_step, int ch, int cw, int oh, int ow, int C_out, double lo, double hi,
+                         float* out, void* stream);
 /* The action rows that go with such a batch (vp_suite/datasets/bair.py:60-61): src [N, T', A] of element type VPX_ACTIONS_F32 / _F64,
  * the SAME device table [B, 4] as vpx_frames_preprocess of which only column 0 (the sequence index) is read; out [B, n_frames, A] dense
  * fp32, out[b, t, :] = float(src[table[b].seq, t * seq_step, :]). float64 is rounded to nearest even, as numpy's astype(float32) does;

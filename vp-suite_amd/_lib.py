@@ -229,6 +229,7 @@ SIGNATURES = {
     "vpx_mmnist_frames": (ci, [vp, ci, ci, vp] + [ci] * 5 + [dbl, dbl, vp, vp]),     # digits N s | params B D F C S | lo hi | out
     # stored frames to a model-ready batch and back
     "vpx_frames_preprocess": (ci, [vp, ci, ll] + [ci] * 4 + [vp] + [ci] * 8 + [dbl, dbl, vp, vp]),   # src dtype N T' H W Cs | table B F step ch cw oh ow C_out | lo hi | out
+    "vpx_clips_preprocess": (ci, [vp, ci, ll] + [ci] * 3 + [vp, ll, vp] + [ci] * 8 + [dbl, dbl, vp, vp]),  # src dtype frames H W Cs | clip_first n_clips table B F step ch cw oh ow C_out | lo hi | out
     "vpx_frames_postprocess": (ci, [vp, ll] + [ci] * 3 + [dbl, dbl, vp, vp]),                       # x N C h w | lo hi | out
     "vpx_actions_gather": (ci, [vp, ci, ll, ci, ci, vp] + [ci] * 3 + [vp, vp]),                     # src dtype N T' A | table B F step | out
     "vpx_frames_augment": (ci, [vp, vp] + [ci] * 6 + [vp]),                                           # x programs | B F C h w max_ops

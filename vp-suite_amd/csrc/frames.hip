@@ -2,6 +2,9 @@
 // repeat of vp_suite/datasets/mmnist.py:56), one launch each.
 //   vpx_frames_preprocess    src [N][T'][H][W][Cs] (uint8 / uint16 / float32, channels last as the files hold them) and a device table
 //                            int32 [B][4] = (sequence, crop y0, crop x0, flip bits) -> out float32 [B][F][C_out][oh][ow]
+//   vpx_clips_preprocess     src [frames][H][W][Cs]: every clip of a split back to back, clip_first int64 [n_clips + 1] (on the device) and a
+//                            device table int32 [B][6] = (clip, start frame within it, crop y0, crop x0, flip bits, 0) -> the same output,
+//                            out[b][t] from frame clip_first[clip] + start + t * step; the SAME per-pixel code (fr_group)
 //   vpx_frames_postprocess   x float32 [N][C][h][w] -> out uint8 [N][h][w][C]; x is only read
 //   vpx_actions_gather       src [N][T'][A] (float32 / float64) and the same device table -> out float32 [B][F][A]: the action rows that go
 //                            with the frames of a batch, out[b][t][:] = float(src[table[b].seq][t * step][:]); a conversion, no arithmetic
@@ -66,24 +69,11 @@ template <typename T> __device__ __forceinline__ float fr_value(const FramesArgs
 // fr_coord(): ATen's source coordinate of destination index d (area_pixel_compute_source_index, align_corners = False) — frames_coord.h,
 // shared with adapt.hip.
 
-// thread = (sample b, frame f, output row y, group of four output pixels). RESIZE = 0: crop size == output size.
+// The four neighbouring output pixels (row y, columns x0 .. x0 + 3) of output frame (b, f) in every channel, from the stored frame
+// `frame` [H][W][Cs] and the row's box and flips: the pixel contract above, once, for every kernel that gathers stored frames
+// (frames_preprocess_kernel: equal-length sequences; clips_preprocess_kernel: windows of long clips). !valid: zeros, nothing is read.
 template <typename T, int RESIZE>
-__global__ __launch_bounds__(FR_THREADS) void frames_preprocess_kernel(FramesArgs a) {
-    const long long item = (long long)blockIdx.x * FR_THREADS + threadIdx.x;
-    if (item >= a.items) return;
-    const int q = (int)(item % a.Q);
-    long long r = item / a.Q;
-    const int y = (int)(r % a.oh);
-    r /= a.oh;
-    const int f = (int)(r % a.F);
-    const int b = (int)(r / a.F);
-    const int x0 = q << 2;
-    const int* row = a.table + (size_t)b * 4;
-    const long long seq = row[0];
-    const int cy = row[1], cx = row[2], flip = row[3];
-    // a row the caller did not check (the table lives on the device) reads nothing out of bounds: it yields zeros
-    const bool valid = seq >= 0 && seq < a.N && cy >= 0 && cx >= 0 && (long long)cy + a.ch <= a.H && (long long)cx + a.cw <= a.W;
-    const T* frame = (const T*)a.src + ((size_t)(valid ? seq : 0) * a.Tp + (size_t)f * a.step) * ((size_t)a.H * a.W * a.Cs);   // 64-bit offsets throughout
+__device__ __forceinline__ void fr_group(const FramesArgs& a, const T* frame, bool valid, int cy, int cx, int flip, int b, int f, int y, int x0) {
     const int yr = (flip & 2) ? a.oh - 1 - y : y;
     float v[FR_MAX_CS][4];
 #pragma unroll
@@ -145,6 +135,62 @@ __global__ __launch_bounds__(FR_THREADS) void frames_preprocess_kernel(FramesArg
             for (int k = 0; k < 4 && x0 + k < a.ow; ++k) dst[k] = o[k];
         dst += plane;
     }
+}
+
+// thread = (sample b, frame f, output row y, group of four output pixels). RESIZE = 0: crop size == output size.
+template <typename T, int RESIZE>
+__global__ __launch_bounds__(FR_THREADS) void frames_preprocess_kernel(FramesArgs a) {
+    const long long item = (long long)blockIdx.x * FR_THREADS + threadIdx.x;
+    if (item >= a.items) return;
+    const int q = (int)(item % a.Q);
+    long long r = item / a.Q;
+    const int y = (int)(r % a.oh);
+    r /= a.oh;
+    const int f = (int)(r % a.F);
+    const int b = (int)(r / a.F);
+    const int* row = a.table + (size_t)b * 4;
+    const long long seq = row[0];
+    const int cy = row[1], cx = row[2], flip = row[3];
+    // a row the caller did not check (the table lives on the device) reads nothing out of bounds: it yields zeros
+    const bool valid = seq >= 0 && seq < a.N && cy >= 0 && cx >= 0 && (long long)cy + a.ch <= a.H && (long long)cx + a.cw <= a.W;
+    const T* frame = (const T*)a.src + ((size_t)(valid ? seq : 0) * a.Tp + (size_t)f * a.step) * ((size_t)a.H * a.W * a.Cs);   // 64-bit offsets throughout
+    fr_group<T, RESIZE>(a, frame, valid, cy, cx, flip, b, f, y, q << 2);
+}
+
+// Windows of long clips: src holds every clip of a split back to back, clip c being frames clip_first[c] .. clip_first[c + 1] - 1;
+// a table row is (clip, start frame within the clip, crop y0, crop x0, flip bits, 0) and output frame f of sample b is stored frame
+// clip_first[clip] + start + f * step. Everything after the frame pointer is fr_group(), so the pixels are those of the kernel above.
+struct ClipsArgs {
+    FramesArgs fr;                     // src, out and the geometry; table, N and Tp are not used
+    const long long* clip_first;       // [n_clips + 1], on the device; the last entry is the number of frames in src
+    const int* table;                  // [B][6]
+    long long n_clips, total;          // total: frames in src
+};
+
+template <typename T, int RESIZE>
+__global__ __launch_bounds__(FR_THREADS) void clips_preprocess_kernel(ClipsArgs c) {
+    const FramesArgs& a = c.fr;
+    const long long item = (long long)blockIdx.x * FR_THREADS + threadIdx.x;
+    if (item >= a.items) return;
+    const int q = (int)(item % a.Q);
+    long long r = item / a.Q;
+    const int y = (int)(r % a.oh);
+    r /= a.oh;
+    const int f = (int)(r % a.F);
+    const int b = (int)(r / a.F);
+    const int* row = c.table + (size_t)b * 6;
+    const long long clip = row[0], start = row[1];
+    const int cy = row[2], cx = row[3], flip = row[4];
+    // as above: a row (or an offset table) the caller did not check yields zeros and reads nothing outside src
+    bool valid = clip >= 0 && clip < c.n_clips && start >= 0 && cy >= 0 && cx >= 0 && (long long)cy + a.ch <= a.H && (long long)cx + a.cw <= a.W;
+    long long first = 0;
+    if (valid) {
+        first = c.clip_first[clip];
+        const long long end = c.clip_first[clip + 1];
+        valid = first >= 0 && end <= c.total && first + start + (long long)(a.F - 1) * a.step < end;
+    }
+    const T* frame = (const T*)a.src + (size_t)(valid ? first + start + (long long)f * a.step : 0) * ((size_t)a.H * a.W * a.Cs);   // 64-bit offsets throughout
+    fr_group<T, RESIZE>(a, frame, valid, cy, cx, flip, b, f, y, q << 2);
 }
 
 struct PostArgs {
@@ -232,6 +278,29 @@ static void launch_preprocess(const FramesArgs& a, int resize, unsigned blocks, 
     else VPX_LAUNCH((frames_preprocess_kernel<T, 0>), dim3(blocks), dim3(FR_THREADS), 0, stream, a);
 }
 
+template <typename T>
+static void launch_clips(const ClipsArgs& c, int resize, unsigned blocks, hipStream_t stream) {
+    if (resize) VPX_LAUNCH((clips_preprocess_kernel<T, 1>), dim3(blocks), dim3(FR_THREADS), 0, stream, c);
+    else VPX_LAUNCH((clips_preprocess_kernel<T, 0>), dim3(blocks), dim3(FR_THREADS), 0, stream, c);
+}
+
+// What both gathers hand fr_group(): the geometry, the value map and the destination (checked by the entry points).
+static FramesArgs frames_args(const void* src, float* out, int H, int W, int Cs, int B, int n_frames, int seq_step, int ch, int cw, int oh, int ow,
+                              int C_out, double lo, double hi) {
+    FramesArgs a;
+    a.src = src; a.table = nullptr; a.out = out;
+    a.N = 0; a.Tp = 0; a.H = H; a.W = W; a.Cs = Cs; a.B = B; a.F = n_frames; a.step = seq_step;
+    a.ch = ch; a.cw = cw; a.oh = oh; a.ow = ow; a.Cout = C_out; a.Q = (ow + 3) / 4;
+    a.items = (long long)B * n_frames * oh * a.Q;
+    a.vec = (ow % 4 == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
+    a.scaled = (lo != 0.0 || hi != 1.0) ? 1 : 0;
+    a.scale = (float)(hi - lo);
+    a.lo = (float)lo;
+    a.sy = (float)ch / (float)oh;
+    a.sx = (float)cw / (float)ow;
+    return a;
+}
+
 }  // namespace vpx
 
 using namespace vpx;
@@ -255,22 +324,43 @@ int vpx_frames_preprocess(const void* src, int dtype, long long N, int Tp, int H
     const int Q = (ow + 3) / 4;
     const double items_d = (double)B * n_frames * oh * Q;
     if (items_d / FR_THREADS + 1.0 > 2147483647.0) { set_error("%s: %d samples of %d %dx%d frames exceed one launch", who, B, n_frames, oh, ow); return VPX_ERR_UNSUPPORTED; }
-    FramesArgs a;
-    a.src = src; a.table = table; a.out = out;
-    a.N = N; a.Tp = Tp; a.H = H; a.W = W; a.Cs = Cs; a.B = B; a.F = n_frames; a.step = seq_step;
-    a.ch = ch; a.cw = cw; a.oh = oh; a.ow = ow; a.Cout = C_out; a.Q = Q;
-    a.items = (long long)B * n_frames * oh * Q;
-    a.vec = (ow % 4 == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
-    a.scaled = (lo != 0.0 || hi != 1.0) ? 1 : 0;
-    a.scale = (float)(hi - lo);
-    a.lo = (float)lo;
-    a.sy = (float)ch / (float)oh;
-    a.sx = (float)cw / (float)ow;
+    FramesArgs a = frames_args(src, out, H, W, Cs, B, n_frames, seq_step, ch, cw, oh, ow, C_out, lo, hi);
+    a.table = table; a.N = N; a.Tp = Tp;
     const int resize = (ch != oh || cw != ow) ? 1 : 0;
     const unsigned blocks = (unsigned)((a.items + FR_THREADS - 1) / FR_THREADS);
     if (dtype == VPX_FRAMES_U8) launch_preprocess<unsigned char>(a, resize, blocks, (hipStream_t)stream);
     else if (dtype == VPX_FRAMES_U16) launch_preprocess<unsigned short>(a, resize, blocks, (hipStream_t)stream);
     else launch_preprocess<float>(a, resize, blocks, (hipStream_t)stream);
+    VPX_CHECK_HIP(vpx_hip_last_error());
+    return VPX_OK;
+}
+
+int vpx_clips_preprocess(const void* src, int dtype, long long total_frames, int H, int W, int Cs, const long long* clip_first, long long n_clips,
+                         const int* table, int B, int n_frames, int seq_step, int ch, int cw, int oh, int ow, int C_out, double lo, double hi,
+                         float* out, void* stream) {
+    const char* who = "vpx_clips_preprocess";
+    if (!src || !clip_first || !table || !out) { set_error("%s: NULL tensor argument", who); return VPX_ERR_ARG; }
+    if (dtype != VPX_FRAMES_U8 && dtype != VPX_FRAMES_U16 && dtype != VPX_FRAMES_F32) { set_error("%s: unknown element type %d (uint8, uint16 and float32 are stored)", who, dtype); return VPX_ERR_ARG; }
+    if (total_frames < 1 || n_clips < 1 || H < 1 || W < 1 || Cs < 1) { set_error("%s: every source size must be >= 1 (got frames=%lld clips=%lld H=%d W=%d Cs=%d)", who, total_frames, n_clips, H, W, Cs); return VPX_ERR_ARG; }
+    if (B < 1 || n_frames < 1 || seq_step < 1) { set_error("%s: B, n_frames and seq_step must be >= 1 (got %d, %d, %d)", who, B, n_frames, seq_step); return VPX_ERR_ARG; }
+    if (ch < 1 || cw < 1 || oh < 1 || ow < 1) { set_error("%s: crop and output sizes must be >= 1 (got crop %dx%d, output %dx%d)", who, ch, cw, oh, ow); return VPX_ERR_ARG; }
+    if (n_clips > total_frames) { set_error("%s: %lld clips in %lld stored frames (a clip holds at least one)", who, n_clips, total_frames); return VPX_ERR_ARG; }
+    if ((long long)(n_frames - 1) * seq_step >= total_frames) { set_error("%s: frame %d at step %d lies past the %lld stored frames", who, n_frames - 1, seq_step, total_frames); return VPX_ERR_ARG; }
+    if (ch > H || cw > W) { set_error("%s: the %dx%d crop box lies outside the %dx%d frame (there is no padding)", who, ch, cw, H, W); return VPX_ERR_ARG; }
+    if (C_out != Cs && !(Cs == 1 && C_out == 3)) { set_error("%s: %d output channels from %d stored ones (equal, or 3 from 1)", who, C_out, Cs); return VPX_ERR_ARG; }
+    if (hi == lo) { set_error("%s: empty value range [%g, %g]", who, lo, hi); return VPX_ERR_ARG; }
+    if (Cs > FR_MAX_CS) { set_error("%s: %d stored channels exceed the kernel's %d", who, Cs, FR_MAX_CS); return VPX_ERR_UNSUPPORTED; }
+    if (H > FR_MAX_SIDE || W > FR_MAX_SIDE || oh > FR_MAX_SIDE || ow > FR_MAX_SIDE) { set_error("%s: a side beyond %d (frame %dx%d, output %dx%d)", who, FR_MAX_SIDE, H, W, oh, ow); return VPX_ERR_UNSUPPORTED; }
+    const double items_d = (double)B * n_frames * oh * ((ow + 3) / 4);
+    if (items_d / FR_THREADS + 1.0 > 2147483647.0) { set_error("%s: %d samples of %d %dx%d frames exceed one launch", who, B, n_frames, oh, ow); return VPX_ERR_UNSUPPORTED; }
+    ClipsArgs c;
+    c.fr = frames_args(src, out, H, W, Cs, B, n_frames, seq_step, ch, cw, oh, ow, C_out, lo, hi);
+    c.clip_first = clip_first; c.table = table; c.n_clips = n_clips; c.total = total_frames;
+    const int resize = (ch != oh || cw != ow) ? 1 : 0;
+    const unsigned blocks = (unsigned)((c.fr.items + FR_THREADS - 1) / FR_THREADS);
+    if (dtype == VPX_FRAMES_U8) launch_clips<unsigned char>(c, resize, blocks, (hipStream_t)stream);
+    else if (dtype == VPX_FRAMES_U16) launch_clips<unsigned short>(c, resize, blocks, (hipStream_t)stream);
+    else launch_clips<float>(c, resize, blocks, (hipStream_t)stream);
     VPX_CHECK_HIP(vpx_hip_last_error());
     return VPX_OK;
 }

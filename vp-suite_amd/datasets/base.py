@@ -359,13 +359,20 @@ class _PinnedStage:
         self.buffer = self.event = None
 
     def to_device(self, raw, indices, steps, device):
-        n = len(indices)
+        return self._stage([raw[i, :steps] for i in indices], device)
+
+    def spans_to_device(self, flat, firsts, steps, device):
+        """The same for long clips stored back to back, flat [frames, ...]: row k of the staged block is flat[firsts[k]:firsts[k] + steps]."""
+        return self._stage([flat[f:f + steps] for f in firsts], device)
+
+    def _stage(self, pieces, device):
+        n, steps = len(pieces), pieces[0].shape[0]
         if self.buffer is None or self.buffer.shape[0] < n or self.buffer.shape[1] != steps:
-            self.buffer = torch.empty((n, steps) + tuple(raw.shape[2:]), dtype=raw.dtype).pin_memory()
+            self.buffer = torch.empty((n,) + tuple(pieces[0].shape), dtype=pieces[0].dtype).pin_memory()
         elif self.event is not None:
             self.event.synchronize()                              # the previous batch's copy has left the buffer
-        for k, i in enumerate(indices):
-            self.buffer[k].copy_(raw[i, :steps])
+        for k, piece in enumerate(pieces):
+            self.buffer[k].copy_(piece)
         dev = self.buffer[:n].to(device, non_blocking=True)
         self.event = torch.cuda.Event()
         self.event.record()
@@ -471,11 +478,14 @@ class StoredVPDataset(VPDataset):
             raise ValueError(f"stored sequences must be [N, T', H, W] or [N, T', H, W, C], nothing empty (got {raw.shape})")
         self._raw_host = np.ascontiguousarray(raw)
         N, Tp, H, W = raw.shape[:4]
-        Cs = raw.shape[4] if raw.ndim == 5 else 1
+        self.MIN_SEQ_LEN = int(Tp)
+        self._set_frame_geometry(H, W, raw.shape[4] if raw.ndim == 5 else 1)
+
+    def _set_frame_geometry(self, H, W, Cs):
+        """Everything that depends on the stored frame shape [H, W, Cs]: the returned channels, the crop box and the returned size."""
         c_out = self.OUT_CHANNELS or Cs
         if c_out != Cs and not (Cs == 1 and c_out == 3):
             raise ValueError(f"{c_out} channels cannot be returned from {Cs} stored ones (equal, or 3 from 1)")
-        self.MIN_SEQ_LEN = int(Tp)
         self.DATASET_FRAME_SHAPE = (int(H), int(W), int(c_out))
         self._crop_hw = (H, W) if self.crop is None else tuple(self.crop[-2:])
         if self._crop_hw[0] > H or self._crop_hw[1] > W:

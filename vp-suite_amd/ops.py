@@ -1417,6 +1417,82 @@ def frames_preprocess(src, table, n_frames, seq_step=1, crop_size=None, out_size
     return out
 
 
+def check_clips_table(table, clip_first, n_frames, seq_step, frame_hw, crop_hw):
+    """The offsets and the table a clips launch is handed, checked where they can be read (the host). clip_first: integers
+    [n_clips + 1], the first frame of every clip in the buffer, starting at 0 and strictly increasing (a clip holds at least one frame);
+    its last entry is the number of frames. table: integer [B, 6] rows (clip index, start frame within the clip, crop y0, crop x0, flip
+    bits, 0) with the index inside [0, n_clips), the window inside its clip (0 <= start, start + (n_frames - 1) * seq_step < the clip's
+    length), the box inside the frame (there is no padding), flip bits in 0 ... 3 and a zero last column.
+    Returns (int64 clip_first, int32 table), both contiguous."""
+    import numpy as np
+    first = clip_first.cpu().numpy() if torch.is_tensor(clip_first) else np.asarray(clip_first)
+    if first.ndim != 1 or first.shape[0] < 2 or not np.issubdtype(first.dtype, np.integer):
+        raise ValueError(f"clip_first must be an integer vector [n_clips + 1] (got {first.dtype} {first.shape})")
+    first = np.ascontiguousarray(first, dtype=np.int64)
+    if first[0] != 0 or np.diff(first).min() < 1:
+        raise ValueError("clip_first must start at 0 and increase strictly (every clip holds at least one frame)")
+    t = table.cpu().numpy() if torch.is_tensor(table) else np.asarray(table)
+    if t.ndim != 2 or t.shape[1] != 6 or t.shape[0] < 1 or not np.issubdtype(t.dtype, np.integer):
+        raise ValueError(f"table must be an integer table [B, 6] (got {t.dtype} {t.shape})")
+    t = t.astype(np.int64)
+    n_clips = first.shape[0] - 1
+    (H, W), (ch, cw) = frame_hw, crop_hw
+    if t[:, 0].min() < 0 or t[:, 0].max() >= n_clips:
+        raise ValueError(f"clip index outside [0, {n_clips})")
+    length = first[t[:, 0] + 1] - first[t[:, 0]]
+    if t[:, 1].min() < 0 or (t[:, 1] + (int(n_frames) - 1) * int(seq_step) >= length).any():
+        raise ValueError(f"a window of {n_frames} frames at step {seq_step} leaves its clip")
+    if t[:, 2].min() < 0 or t[:, 3].min() < 0 or t[:, 2].max() + ch > H or t[:, 3].max() + cw > W:
+        raise ValueError(f"a {ch}x{cw} crop box leaves the {H}x{W} frame (there is no padding)")
+    if t[:, 4].min() < 0 or t[:, 4].max() > 3:
+        raise ValueError("flip bits outside 0 ... 3 (bit 0 horizontal, bit 1 vertical)")
+    if (t[:, 5] != 0).any():
+        raise ValueError("the last column of a clips table is reserved: zeros")
+    return first, np.ascontiguousarray(t, dtype=np.int32)
+
+
+def clips_preprocess(src, clip_first, table, n_frames, seq_step=1, crop_size=None, out_size=None, c_out=None, value_range=(0.0, 1.0), out=None):
+    """float32 [B, n_frames, C_out, oh, ow] from windows of long clips in ONE launch. `src` [frames, H, W(, Cs)] (a uint8 / uint16 /
+    float32 GPU tensor, channels last) holds every clip back to back; `clip_first`: host integers [n_clips + 1], the first frame of each
+    clip, the last entry = frames; `table`: host rows [B, 6] = (clip index, start frame within the clip, crop y0, crop x0, flip bits, 0).
+    out[b, t] comes from frame clip_first[clip] + start + t * seq_step, through the pixel arithmetic of frames_preprocess (the same device
+    function: scale, crop, bilinear resize, flips, gray repeat — see include/vpx.h). Both host arguments are checked here
+    (check_clips_table) and copied to the device once. The defaults are those of frames_preprocess."""
+    if not (torch.is_tensor(src) and src.is_cuda):
+        raise _lib.VpxError("clips_preprocess: src must be a GPU tensor; frames are converted by a HIP kernel, there is no CPU fallback")
+    if src.dtype not in FRAME_DTYPES:
+        raise ValueError(f"clips_preprocess: stored element type {src.dtype} is unknown (uint8, uint16 and float32 are)")
+    if src.ndim not in (3, 4):
+        raise ValueError(f"clips_preprocess: src must be [frames, H, W] or [frames, H, W, C] (got {tuple(src.shape)})")
+    src = src.contiguous()
+    total, H, W = (int(s) for s in src.shape[:3])
+    Cs = int(src.shape[3]) if src.ndim == 4 else 1
+    ch, cw = (H, W) if crop_size is None else (int(s) for s in crop_size)
+    oh, ow = (ch, cw) if out_size is None else (int(s) for s in out_size)
+    c_out = Cs if c_out is None else int(c_out)
+    n_frames, seq_step = int(n_frames), int(seq_step)
+    if min(ch, cw, oh, ow, n_frames, seq_step) < 1:
+        raise ValueError(f"clips_preprocess: every size must be >= 1 (crop {ch}x{cw}, output {oh}x{ow}, {n_frames} frames, step {seq_step})")
+    first, host = check_clips_table(table, clip_first, n_frames, seq_step, (H, W), (ch, cw))
+    if int(first[-1]) != total:
+        raise ValueError(f"clips_preprocess: clip_first ends at {int(first[-1])} but src holds {total} frames")
+    B = host.shape[0]
+    lo, hi = float(value_range[0]), float(value_range[1])
+    shape = (B, n_frames, c_out, oh, ow)
+    if out is None:
+        if min(shape) < 1:
+            raise ValueError(f"clips_preprocess: empty output {shape}")
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+        raise ValueError(f"clips_preprocess: out must be a contiguous float32 GPU tensor {shape}")
+    dev_first = torch.from_numpy(first).to(src.device)
+    dev_table = torch.from_numpy(host).to(src.device)
+    with torch.cuda.device(src.device):
+        check(_lib.lib().vpx_clips_preprocess(ptr(src), FRAME_DTYPES[src.dtype], total, H, W, Cs, ptr(dev_first), first.shape[0] - 1, ptr(dev_table), B,
+                                              n_frames, seq_step, ch, cw, oh, ow, c_out, lo, hi, ptr(out), stream()), "vpx_clips_preprocess")
+    return out
+
+
 ACTION_DTYPES = {torch.float32: _lib.ACTIONS_F32, torch.float64: _lib.ACTIONS_F64}
 
 
