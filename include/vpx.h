@@ -34,8 +34,10 @@
  * vpx_mmnist_frames                MovingMNISTOnTheFly.__getitem__ (a batch) vp_suite/datasets/mmnist_on_the_fly.py:78-104,133-147
  * vpx_frames_preprocess            VPDataset.preprocess (a batch of stored sequences)  vp_suite/base/base_dataset.py:233-273, datasets/mmnist.py:56-57
  * vpx_clips_preprocess             the same for windows of long clips       vp_suite/datasets/kitti_raw.py:77-95, caltech_pedestrian.py:69-86
+ * vpx_clips_preprocess_var         the same for clips of mixed frame sizes  vp_suite/datasets/human36m.py:30,80-83 (the resize at load), physics101.py, synpick.py
  * vpx_frames_postprocess           VPDataset.postprocess                   vp_suite/base/base_dataset.py:286-297
  * vpx_actions_gather               the action rows of a batch of stored sequences  vp_suite/datasets/bair.py:60-61
+ * vpx_actions_diff_gather          action rows as differences of stored positions  vp_suite/datasets/synpick.py:110-113,135-137
  * vpx_frames_augment               the colour and erasing entries of VPDataset's augmentation list  vp_suite/base/base_dataset.py:19-23,135-141
  * vpx_frames_adapt                 ScaleToModel / ScaleToTest + TF.Resize   vp_suite/utils/compatibility.py:31-50, utils/models.py:7-64
  * vpx_nchw_to_nhwc / nhwc_to_nchw  (layout adaptors at the boundary; the reference is NCHW throughout)
@@ -642,6 +644,23 @@ int vpx_frames_postprocess(const float* x, long long N, int C, int h, int w, dou
 int vpx_clips_preprocess(const void* src, int dtype, long long total_frames, int H, int W, int Cs, const long long* clip_first, long long n_clips,
                          const int* table, int B, int n_frames, int seq_step, int ch, int cw, int oh, int ow, int C_out, double lo, double hi,
                          float* out, void* stream);
+/* Windows of clips whose FRAME SIZES differ (vp_suite/datasets/human36m.py: 1002 x 1000 videos among 1000 x 1000 ones, resized while
+ * they load; here in the launch): src is one element buffer of total_elems elements (element types as above, Cs channels, channels last)
+ * that holds every clip back to back; clip_geom [n_clips, 4] (int64, on the device) holds per clip (element offset of its first frame,
+ * frame count, H_i, W_i); table [B, 8] (int32, on the device) holds per output sample (clip index, start frame within the clip, box y0,
+ * box x0, box h, box w, flip bits, 0). out [B, n_frames, C_out, oh, ow] is dense fp32; output frame f of sample b is frame
+ * start + f * seq_step of its clip, and the box of that frame goes to oh x ow through the device function of the two launches above
+ * with the sample's sizes in place of the launch's: a box of the output's size is copied (the bits of vpx_clips_preprocess), any other
+ * is resized by the same bilinear rule with s = float(box) / float(out) per axis; flips after the resize; the gray repeat. One launch,
+ * no workspace, no atomics, no host sync; offsets are 64-bit.
+ * VPX_ERR_ARG: a NULL pointer, an unknown element type, a size < 1, n_clips > total_elems / Cs, (n_frames - 1) * seq_step >=
+ * total_elems / Cs, C_out neither Cs nor 3 from 1, hi == lo. VPX_ERR_UNSUPPORTED: Cs > 4, an output side beyond 32768, more workgroups
+ * than one launch holds. Both tables live on the device, so the CALLER checks them: a row whose clip index is outside [0, n_clips), whose
+ * window leaves its clip, whose box is empty or leaves the clip's H_i x W_i frame, or whose clip (a negative offset or a size < 1, a side
+ * beyond 32768, offset + count * H_i * W_i * Cs > total_elems) leaves src yields zeros and reads nothing out of bounds. */
+int vpx_clips_preprocess_var(const void* src, int dtype, long long total_elems, int Cs, const long long* clip_geom, long long n_clips,
+                             const int* table, int B, int n_frames, int seq_step, int oh, int ow, int C_out, double lo, double hi, float* out,
+                             void* stream);
 /* The action rows that go with such a batch (vp_suite/datasets/bair.py:60-61): src [N, T', A] of element type VPX_ACTIONS_F32 / _F64,
  * the SAME device table [B, 4] as vpx_frames_preprocess of which only column 0 (the sequence index) is read; out [B, n_frames, A] dense
  * fp32, out[b, t, :] = float(src[table[b].seq, t * seq_step, :]). float64 is rounded to nearest even, as numpy's astype(float32) does;
@@ -652,6 +671,17 @@ int vpx_clips_preprocess(const void* src, int dtype, long long total_frames, int
 enum { VPX_ACTIONS_F32 = 0, VPX_ACTIONS_F64 = 1 };
 int vpx_actions_gather(const void* src, int dtype, long long N, int Tp, int A, const int* table, int B, int n_frames, int seq_step,
                        float* out, void* stream);
+/* Action rows that are DIFFERENCES of stored positions (vp_suite/datasets/synpick.py:110-113, 135-137): src [total_frames, A] of element
+ * type VPX_ACTIONS_F32 / _F64 holds one position row per stored frame, every clip back to back; clip_first [n_clips + 1] (int64, on the
+ * device) the first row of each clip; table [B, 8] is the device table of vpx_clips_preprocess_var, of which columns 0 (clip) and 1
+ * (start frame) are read. out [B, n_frames - 1, A] dense fp32, out[b, j, :] = float(src[g(j + 1), :] - src[g(j), :]) with
+ * g(j) = clip_first[clip] + start + j * seq_step: the subtraction in the source's precision, then ONE rounding to fp32 (nearest even) —
+ * numpy's (new - old) followed by .float(). One launch, no workspace, no atomics, no host sync, 64-bit offsets.
+ * VPX_ERR_ARG: a NULL pointer, an unknown element type, a size < 1, n_frames == 1, n_clips > total_frames, (n_frames - 1) * seq_step >=
+ * total_frames. VPX_ERR_UNSUPPORTED: more workgroups than one launch holds. The CALLER checks the tables: a clip index outside
+ * [0, n_clips), a window that leaves its clip or a clip that leaves src yields zeros and reads nothing out of bounds. */
+int vpx_actions_diff_gather(const void* src, int dtype, long long total_frames, int A, const long long* clip_first, long long n_clips,
+                            const int* table, int B, int n_frames, int seq_step, float* out, void* stream);
 
 /* ---- photometric augmentations and erasing of a preprocessed batch, in place (torchvision's tensor transforms, restated) ----
  * x [B, n_frames, C, h, w] dense fp32, changed in place by ONE launch; programs [B, max_ops, VPX_FRAMES_AUG_ROW] (fp32, on the device):

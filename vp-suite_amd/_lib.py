@@ -230,8 +230,10 @@ SIGNATURES = {
     # stored frames to a model-ready batch and back
     "vpx_frames_preprocess": (ci, [vp, ci, ll] + [ci] * 4 + [vp] + [ci] * 8 + [dbl, dbl, vp, vp]),   # src dtype N T' H W Cs | table B F step ch cw oh ow C_out | lo hi | out
     "vpx_clips_preprocess": (ci, [vp, ci, ll] + [ci] * 3 + [vp, ll, vp] + [ci] * 8 + [dbl, dbl, vp, vp]),  # src dtype frames H W Cs | clip_first n_clips table B F step ch cw oh ow C_out | lo hi | out
+    "vpx_clips_preprocess_var": (ci, [vp, ci, ll, ci, vp, ll, vp] + [ci] * 6 + [dbl, dbl, vp, vp]),   # src dtype elems Cs | clip_geom n_clips table B F step oh ow C_out | lo hi | out
     "vpx_frames_postprocess": (ci, [vp, ll] + [ci] * 3 + [dbl, dbl, vp, vp]),                       # x N C h w | lo hi | out
     "vpx_actions_gather": (ci, [vp, ci, ll, ci, ci, vp] + [ci] * 3 + [vp, vp]),                     # src dtype N T' A | table B F step | out
+    "vpx_actions_diff_gather": (ci, [vp, ci, ll, ci, vp, ll, vp] + [ci] * 3 + [vp, vp]),           # src dtype frames A | clip_first n_clips table B F step | out
     "vpx_frames_augment": (ci, [vp, vp] + [ci] * 6 + [vp]),                                           # x programs | B F C h w max_ops
     # frame adapter between a model and a test set
     "vpx_frames_adapt": (ci, [vp, ll] + [ci] * 5 + [dbl] * 4 + [vp, vp]),                            # x N C H W oh ow | src lo hi, dst lo hi | out

@@ -1534,6 +1534,143 @@ def actions_gather(raw_actions, table, n_frames, seq_step=1):
     return out
 
 
+def check_clips_var_table(table, clip_geom, total_elems, channels, n_frames, seq_step):
+    """The tables a mixed-shape clips launch is handed, checked where they can be read (the host). clip_geom: integers [n_clips, 4] rows
+    (element offset of the clip's first frame, frame count, H_i, W_i), every clip inside the total_elems elements of the buffer (offset
+    >= 0, count, H_i, W_i >= 1, sides up to 32768, offset + count * H_i * W_i * channels <= total_elems). table: integer [B, 8] rows (clip
+    index, start frame within the clip, box y0, box x0, box h, box w, flip bits, 0) with the index inside [0, n_clips), the window inside
+    its clip, a box of at least one pixel inside the clip's own H_i x W_i frame (there is no padding), flip bits in 0 ... 3 and a zero
+    last column. Returns (int64 clip_geom, int32 table), both contiguous."""
+    import numpy as np
+    geom = clip_geom.cpu().numpy() if torch.is_tensor(clip_geom) else np.asarray(clip_geom)
+    if geom.ndim != 2 or geom.shape[1] != 4 or geom.shape[0] < 1 or not np.issubdtype(geom.dtype, np.integer):
+        raise ValueError(f"clip_geom must be an integer table [n_clips, 4] (got {geom.dtype} {geom.shape})")
+    geom = np.ascontiguousarray(geom, dtype=np.int64)
+    if geom[:, 0].min() < 0 or geom[:, 1:].min() < 1 or geom[:, 2:].max() > 32768:
+        raise ValueError("clip_geom: an offset below 0, a frame count or a side below 1, or a side beyond 32768")
+    if (geom[:, 0] + geom[:, 1] * geom[:, 2] * geom[:, 3] * int(channels) > int(total_elems)).any():
+        raise ValueError(f"a clip leaves the {int(total_elems)} stored elements")
+    t = table.cpu().numpy() if torch.is_tensor(table) else np.asarray(table)
+    if t.ndim != 2 or t.shape[1] != 8 or t.shape[0] < 1 or not np.issubdtype(t.dtype, np.integer):
+        raise ValueError(f"table must be an integer table [B, 8] (got {t.dtype} {t.shape})")
+    t = t.astype(np.int64)
+    n_clips = geom.shape[0]
+    if t[:, 0].min() < 0 or t[:, 0].max() >= n_clips:
+        raise ValueError(f"clip index outside [0, {n_clips})")
+    count, H, W = (geom[t[:, 0], k] for k in (1, 2, 3))
+    if t[:, 1].min() < 0 or (t[:, 1] + (int(n_frames) - 1) * int(seq_step) >= count).any():
+        raise ValueError(f"a window of {n_frames} frames at step {seq_step} leaves its clip")
+    if t[:, 2:6].min() < 0 or t[:, 4:6].min() < 1 or (t[:, 2] + t[:, 4] > H).any() or (t[:, 3] + t[:, 5] > W).any():
+        raise ValueError("a crop box is empty or leaves its clip's frame (there is no padding)")
+    if t[:, 6].min() < 0 or t[:, 6].max() > 3:
+        raise ValueError("flip bits outside 0 ... 3 (bit 0 horizontal, bit 1 vertical)")
+    if (t[:, 7] != 0).any():
+        raise ValueError("the last column of a clips table is reserved: zeros")
+    return geom, np.ascontiguousarray(t, dtype=np.int32)
+
+
+def clips_preprocess_var(src, clip_geom, table, n_frames, seq_step=1, out_size=None, channels=1, c_out=None, value_range=(0.0, 1.0), out=None):
+    """float32 [B, n_frames, C_out, oh, ow] from windows of clips of MIXED frame sizes in ONE launch. `src`: a contiguous uint8 / uint16 /
+    float32 GPU tensor (any shape; read as one element buffer) holding every clip [T_i, H_i, W_i, channels] back to back; `clip_geom`:
+    host integers [n_clips, 4] = (element offset, frame count, H_i, W_i); `table`: host rows [B, 8] = (clip index, start frame within the
+    clip, box y0, box x0, box h, box w, flip bits, 0). The box of frame start + t * seq_step goes to out_size = (oh, ow) through the pixel
+    arithmetic of frames_preprocess (the same device function, with the sample's sizes): a box of that size is copied, any other resized
+    (bilinear, align_corners=False, no antialiasing); flips after the resize; c_out = 3 repeats one stored channel. Host tables are
+    checked here (check_clips_var_table) and copied to the device once. Both may also be GPU tensors (int64 [n_clips, 4], int32 [B, 8])
+    that the caller has checked: the launch reads nothing outside `src` for any row, and a row that was not valid yields zeros."""
+    if not (torch.is_tensor(src) and src.is_cuda):
+        raise _lib.VpxError("clips_preprocess_var: src must be a GPU tensor; frames are converted by a HIP kernel, there is no CPU fallback")
+    if src.dtype not in FRAME_DTYPES:
+        raise ValueError(f"clips_preprocess_var: stored element type {src.dtype} is unknown (uint8, uint16 and float32 are)")
+    src = src.contiguous()
+    total, Cs = int(src.numel()), int(channels)
+    n_frames, seq_step = int(n_frames), int(seq_step)
+    if out_size is None:
+        raise ValueError("clips_preprocess_var: out_size=(oh, ow) is required (the clips have no common frame size)")
+    oh, ow = (int(s) for s in out_size)
+    c_out = Cs if c_out is None else int(c_out)
+    if min(oh, ow, n_frames, seq_step, Cs, total) < 1:
+        raise ValueError(f"clips_preprocess_var: every size must be >= 1 (output {oh}x{ow}, {n_frames} frames, step {seq_step}, {Cs} channels, {total} elements)")
+    on_device = [torch.is_tensor(t) and t.is_cuda for t in (clip_geom, table)]
+    if all(on_device):
+        if (clip_geom.dtype != torch.int64 or clip_geom.ndim != 2 or clip_geom.shape[1] != 4 or clip_geom.shape[0] < 1 or not clip_geom.is_contiguous()
+                or table.dtype != torch.int32 or table.ndim != 2 or table.shape[1] != 8 or table.shape[0] < 1 or not table.is_contiguous()
+                or clip_geom.device != src.device or table.device != src.device):
+            raise ValueError("clips_preprocess_var: device tables must be contiguous int64 [n_clips, 4] and int32 [B, 8] on the frames' GPU")
+        dev_geom, dev_table = clip_geom, table
+    elif any(on_device):
+        raise ValueError("clips_preprocess_var: clip_geom and table must both be host tables or both be GPU tensors")
+    else:
+        geom, host = check_clips_var_table(table, clip_geom, total, Cs, n_frames, seq_step)
+        dev_geom, dev_table = torch.from_numpy(geom).to(src.device), torch.from_numpy(host).to(src.device)
+    B, n_clips = int(dev_table.shape[0]), int(dev_geom.shape[0])
+    lo, hi = float(value_range[0]), float(value_range[1])
+    shape = (B, n_frames, c_out, oh, ow)
+    if out is None:
+        if min(shape) < 1:
+            raise ValueError(f"clips_preprocess_var: empty output {shape}")
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+        raise ValueError(f"clips_preprocess_var: out must be a contiguous float32 GPU tensor {shape}")
+    with torch.cuda.device(src.device):
+        check(_lib.lib().vpx_clips_preprocess_var(ptr(src), FRAME_DTYPES[src.dtype], total, Cs, ptr(dev_geom), n_clips, ptr(dev_table), B, n_frames,
+                                                  seq_step, oh, ow, c_out, lo, hi, ptr(out), stream()), "vpx_clips_preprocess_var")
+    return out
+
+
+def actions_diff_gather(positions, clip_first, table, n_frames, seq_step=1):
+    """float32 [B, n_frames - 1, A] from per-frame positions `positions` [frames, A] (a float32 / float64 GPU tensor, every clip back to
+    back) in ONE launch: out[b, j] = float32(positions[g(j + 1)] - positions[g(j)]) with g(j) = clip_first[clip] + start + j * seq_step,
+    the subtraction in the stored precision — see include/vpx.h. `clip_first`: host integers [n_clips + 1]; `table`: host rows [B, 8] of a
+    mixed-shape clips launch (or any integer [B, >= 2] rows: only the clip index and the start frame are read), checked here; or both as
+    GPU tensors (int64 [n_clips + 1], int32 [B, 8]) that the caller has checked."""
+    import numpy as np
+    if not (torch.is_tensor(positions) and positions.is_cuda):
+        raise _lib.VpxError("actions_diff_gather: positions must be a GPU tensor; the rows are gathered by a HIP kernel, there is no CPU fallback")
+    if positions.dtype not in ACTION_DTYPES:
+        raise ValueError(f"actions_diff_gather: stored element type {positions.dtype} is unknown (float32 and float64 are)")
+    if positions.ndim != 2 or min(positions.shape) < 1:
+        raise ValueError(f"actions_diff_gather: positions must be [frames, A], nothing empty (got {tuple(positions.shape)})")
+    src = positions.contiguous()
+    total, A = (int(s) for s in src.shape)
+    n_frames, seq_step = int(n_frames), int(seq_step)
+    if n_frames < 2 or seq_step < 1:
+        raise ValueError(f"actions_diff_gather: n_frames must be >= 2 (a difference needs two frames) and seq_step >= 1 (got {n_frames}, {seq_step})")
+    on_device = [torch.is_tensor(t) and t.is_cuda for t in (clip_first, table)]
+    if all(on_device):
+        if (clip_first.dtype != torch.int64 or clip_first.ndim != 1 or clip_first.shape[0] < 2 or not clip_first.is_contiguous()
+                or table.dtype != torch.int32 or table.ndim != 2 or table.shape[1] != 8 or table.shape[0] < 1 or not table.is_contiguous()
+                or clip_first.device != src.device or table.device != src.device):
+            raise ValueError("actions_diff_gather: device tables must be contiguous int64 [n_clips + 1] and int32 [B, 8] on the positions' GPU")
+        dev_first, dev_table = clip_first, table
+    elif any(on_device):
+        raise ValueError("actions_diff_gather: clip_first and table must both be host tables or both be GPU tensors")
+    else:
+        first = clip_first.numpy() if torch.is_tensor(clip_first) else np.asarray(clip_first)
+        if first.ndim != 1 or first.shape[0] < 2 or not np.issubdtype(first.dtype, np.integer):
+            raise ValueError(f"clip_first must be an integer vector [n_clips + 1] (got {first.dtype} {first.shape})")
+        first = np.ascontiguousarray(first, dtype=np.int64)
+        if first[0] != 0 or np.diff(first).min() < 1 or int(first[-1]) != total:
+            raise ValueError(f"clip_first must start at 0, increase strictly and end at the {total} stored rows")
+        t = table.numpy() if torch.is_tensor(table) else np.asarray(table)
+        if t.ndim != 2 or t.shape[1] < 2 or t.shape[1] > 8 or t.shape[0] < 1 or not np.issubdtype(t.dtype, np.integer):
+            raise ValueError(f"table must be an integer table [B, 8] (got {t.dtype} {t.shape})")
+        t = t.astype(np.int64)
+        if t[:, 0].min() < 0 or t[:, 0].max() >= first.shape[0] - 1:
+            raise ValueError(f"clip index outside [0, {first.shape[0] - 1})")
+        if t[:, 1].min() < 0 or (t[:, 1] + (n_frames - 1) * seq_step >= first[t[:, 0] + 1] - first[t[:, 0]]).any():
+            raise ValueError(f"a window of {n_frames} frames at step {seq_step} leaves its clip")
+        host = np.zeros((t.shape[0], 8), dtype=np.int32)
+        host[:, :2] = t[:, :2]
+        dev_first, dev_table = torch.from_numpy(first).to(src.device), torch.from_numpy(host).to(src.device)
+    B = int(dev_table.shape[0])
+    out = torch.empty((B, n_frames - 1, A), dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        check(_lib.lib().vpx_actions_diff_gather(ptr(src), ACTION_DTYPES[src.dtype], total, A, ptr(dev_first), int(dev_first.shape[0]) - 1, ptr(dev_table), B,
+                                                 n_frames, seq_step, ptr(out), stream()), "vpx_actions_diff_gather")
+    return out
+
+
 def frames_postprocess(x, lo=0.0, hi=1.0):
     """uint8 [..., h, w, C] on the GPU from float32 [..., C, h, w] in one launch: ((x - lo) / (hi - lo)) * 255 in float32, clamped to
     [0, 255], truncated; NaN gives 0. `x` is left as it is (the reference subtracts in place)."""
