@@ -40,6 +40,7 @@
  * vpx_actions_diff_gather          action rows as differences of stored positions  vp_suite/datasets/synpick.py:110-113,135-137
  * vpx_frames_augment               the colour and erasing entries of VPDataset's augmentation list  vp_suite/base/base_dataset.py:19-23,135-141
  * vpx_frames_adapt                 ScaleToModel / ScaleToTest + TF.Resize   vp_suite/utils/compatibility.py:31-50, utils/models.py:7-64
+ * vpx_vis_compose                  add_borders + side-by-side video, save_frame_compare_img  vp_suite/utils/visualization.py:37-79,133,220-258
  * vpx_nchw_to_nhwc / nhwc_to_nchw  (layout adaptors at the boundary; the reference is NCHW throughout)
  *
  * Layouts. VPX_LAYOUT_NHWC ("channels last", the library's native layout):
@@ -714,6 +715,22 @@ int vpx_frames_augment(float* x, const float* programs, int B, int n_frames, int
  * VPX_ERR_ARG: a NULL pointer, a size < 1, src_hi == src_lo. VPX_ERR_UNSUPPORTED: a side beyond 32768, more workgroups than one launch holds. */
 int vpx_frames_adapt(const float* x, long long N, int C, int H, int W, int oh, int ow, double src_lo, double src_hi, double dst_lo,
                      double dst_hi, float* out, void* stream);
+
+/* ---- prediction visualizations: bordered tiles composed into a canvas (vp_suite/utils/visualization.py: add_borders, the side-by-side
+ * video of save_vid_vis, the sheet of save_frame_compare_img) ----
+ * src [S, T, C, h, w] planar fp32 (only read; C = 1 or 3) holds S sequences in the value range [lo, hi]; tiles [n_tiles, 8] (int32, on the
+ * device) holds rows (s, t, f, y0, x0, b, colour 0xRRGGBB, 0); canvas [F, Hc, Wc, 3] is bytes. A tile paints the (h + 2b) x (w + 2b)
+ * rectangle at (y0, x0) of canvas frame f: the outer ring of width b in the colour, the inner h x w with frame (s, t) turned into bytes by
+ * the device function of vpx_frames_postprocess (the same bytes); a one-channel source goes to all three channels. Bytes that no tile covers
+ * hold `background` (a grey level 0 ... 255: one asynchronous fill of the canvas before the launch), or are left as they are for
+ * background = -1 (the caller knows that the tiles cover the canvas). max_border is the largest b of the table (it sizes the launch).
+ * One launch over the tiles on the caller's stream, no workspace, no atomics, no host sync, 64-bit offsets: two runs give equal bytes.
+ * VPX_ERR_ARG: a NULL pointer, C neither 1 nor 3, hi <= lo, n_tiles < 0, max_border < 0, background outside [-1, 255], with n_tiles > 0 a
+ * size < 1. VPX_ERR_UNSUPPORTED: a side or border beyond 32768, more work than one launch holds. `tiles` lives on the device, so the CALLER
+ * checks it: a row whose s, t or f is out of range, whose b is outside [0, max_border] or whose rectangle leaves the canvas is skipped as
+ * a whole (nothing of it is read or written); two overlapping tiles of one canvas frame stay in bounds and show either. */
+int vpx_vis_compose(const float* src, int S, int T, int C, int h, int w, double lo, double hi, const int* tiles, int n_tiles, int max_border,
+                    unsigned char* canvas, int F, int Hc, int Wc, int background, void* stream);
 
 /* ---- layout adaptors: src [N,C,H,W] <-> dst [N,H,W,C] -------------------------------------------------------- */
 int vpx_nchw_to_nhwc(const float* src, float* dst, int N, int C, int H, int W, void* stream);

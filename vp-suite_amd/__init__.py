@@ -6,6 +6,7 @@ from . import _lib  # noqa: F401
 from ._lib import VpxError, build as build_extension  # noqa: F401
 from . import ops  # noqa: F401
 from .datasets import AVAILABLE_DATASETS, DATASET_CLASSES  # noqa: F401
+from . import visualization  # noqa: F401
 from .vpsuite import DEFAULT_RUN_CONFIG, VPSuite  # noqa: F401
 
 __version__ = "0.1.0"

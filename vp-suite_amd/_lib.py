@@ -26,6 +26,7 @@ FLAG_OUT_SPLIT = 8
 FRAMES_U8, FRAMES_U16, FRAMES_F32 = 0, 1, 2
 ACTIONS_F32, ACTIONS_F64 = 0, 1
 FRAMES_AUG_ROW, FRAMES_AUG_MIN_OPS, FRAMES_AUG_MAX_OPS = 9, 16, 64   # a program row: opcode + 8 parameters; rows per program
+VIS_TILE_ROW = 8     # a visualization tile: (s, t, f, y0, x0, b, colour 0xRRGGBB, 0)
 
 OPT_CELL2 = 1
 OPT_CELL3 = 2
@@ -237,6 +238,8 @@ SIGNATURES = {
     "vpx_frames_augment": (ci, [vp, vp] + [ci] * 6 + [vp]),                                           # x programs | B F C h w max_ops
     # frame adapter between a model and a test set
     "vpx_frames_adapt": (ci, [vp, ll] + [ci] * 5 + [dbl] * 4 + [vp, vp]),                            # x N C H W oh ow | src lo hi, dst lo hi | out
+    # prediction visualizations
+    "vpx_vis_compose": (ci, [vp] + [ci] * 5 + [dbl, dbl, vp, ci, ci, vp] + [ci] * 4 + [vp]),          # src S T C h w | lo hi | tiles n_tiles max_border | canvas F Hc Wc background
     # layout adaptors
     "vpx_nchw_to_nhwc": (ci, [vp, vp] + [ci] * 4 + [vp]),
     "vpx_nhwc_to_nchw": (ci, [vp, vp] + [ci] * 4 + [vp]),

@@ -34,6 +34,7 @@
 #pragma clang fp contract(off)
 
 #include "frames_coord.h"
+#include "frames_byte.h"   // fr_byte: the float -> byte rule of the postprocess, shared with vis.hip
 
 namespace vpx {
 
@@ -259,15 +260,6 @@ struct PostArgs {
     float scale, lo;                   // float(hi - lo), float(lo)
 };
 
-__device__ __forceinline__ unsigned fr_byte(const PostArgs& a, float x) {
-    float v = x - a.lo;
-    v = v / a.scale;
-    v = v * 255.0f;
-    if (!(v == v)) return 0u;                                          // NaN: 0 by definition (the reference's conversion is undefined)
-    v = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);
-    return (unsigned)v;                                                // truncation toward zero
-}
-
 // thread = (image n, row y, group of four pixels): reads its four pixels of every plane, writes their 4 * C interleaved bytes
 __global__ __launch_bounds__(FR_THREADS) void frames_postprocess_kernel(PostArgs a) {
     const long long item = (long long)blockIdx.x * FR_THREADS + threadIdx.x;
@@ -289,7 +281,7 @@ __global__ __launch_bounds__(FR_THREADS) void frames_postprocess_kernel(PostArgs
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int j = k * a.C + c;
-                const unsigned byte = fr_byte(a, p[k]) << ((j & 3) * 8);
+                const unsigned byte = fr_byte(a.lo, a.scale, p[k]) << ((j & 3) * 8);
 #pragma unroll
                 for (int wd = 0; wd < 4; ++wd)
                     if ((j >> 2) == wd) words[wd] |= byte;
@@ -300,7 +292,7 @@ __global__ __launch_bounds__(FR_THREADS) void frames_postprocess_kernel(PostArgs
             if (wd < a.C) reinterpret_cast<unsigned*>(dst)[wd] = words[wd];
     } else {
         for (int k = 0; k < 4 && x0 + k < a.w; ++k)
-            for (int c = 0; c < a.C; ++c) dst[k * a.C + c] = (unsigned char)fr_byte(a, src[(size_t)c * plane + k]);
+            for (int c = 0; c < a.C; ++c) dst[k * a.C + c] = (unsigned char)fr_byte(a.lo, a.scale, src[(size_t)c * plane + k]);
     }
 }
 

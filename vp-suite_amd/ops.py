@@ -1764,3 +1764,84 @@ def frames_adapt(x, out_hw=None, src_range=(0.0, 1.0), dst_range=(0.0, 1.0)):
         check(_lib.lib().vpx_frames_adapt(ptr(xc), N, C, H, W, oh, ow, float(src_range[0]), float(src_range[1]), float(dst_range[0]),
                                           float(dst_range[1]), ptr(out), stream()), "vpx_frames_adapt")
     return out
+
+
+# ---- prediction visualizations: bordered tiles composed into a canvas (csrc/vis.hip) ----
+def check_vis_tiles(tiles, n_seqs, n_frames, frame_hw, canvas_shape):
+    """The table a compose launch is handed, checked where it can be read (the host): int32 [n_tiles, 8] rows (s, t, f, y0, x0, b, colour
+    0xRRGGBB, 0) with s inside [0, n_seqs), t inside [0, n_frames), f inside the canvas's frames, b >= 0, the (h + 2b) x (w + 2b) rectangle
+    inside the canvas frame and no two rectangles of one canvas frame overlapping. Returns (the table as contiguous int32, the largest b,
+    whether the tiles cover the canvas exactly)."""
+    import numpy as np
+    t = tiles.cpu().numpy() if torch.is_tensor(tiles) else np.asarray(tiles)
+    if t.ndim != 2 or t.shape[1] != _lib.VIS_TILE_ROW or t.shape[0] < 1 or not np.issubdtype(t.dtype, np.integer):
+        raise ValueError(f"tiles must be an integer table [n_tiles, {_lib.VIS_TILE_ROW}] (got {t.dtype} {t.shape})")
+    if len(canvas_shape) != 4 or int(canvas_shape[3]) != 3 or min(int(v) for v in canvas_shape) < 1:
+        raise ValueError(f"the canvas is [F, Hc, Wc, 3] with every size >= 1 (got {tuple(canvas_shape)})")
+    t = t.astype(np.int64)
+    (h, w), (F, Hc, Wc) = frame_hw, (int(v) for v in canvas_shape[:3])
+    s, tt, f, y0, x0, b, colour, rest = (t[:, i] for i in range(8))
+    if s.min() < 0 or s.max() >= n_seqs:
+        raise ValueError(f"sequence index s outside [0, {n_seqs})")
+    if tt.min() < 0 or tt.max() >= n_frames:
+        raise ValueError(f"frame index t outside [0, {n_frames})")
+    if f.min() < 0 or f.max() >= F:
+        raise ValueError(f"canvas frame f outside [0, {F})")
+    if b.min() < 0:
+        raise ValueError("negative border width b")
+    y1, x1 = y0 + h + 2 * b, x0 + w + 2 * b
+    if y0.min() < 0 or x0.min() < 0 or (y1 > Hc).any() or (x1 > Wc).any():
+        raise ValueError(f"a tile leaves the {Hc}x{Wc} canvas")
+    if colour.min() < 0 or colour.max() > 0xFFFFFF:
+        raise ValueError("border colour outside 0x000000 ... 0xFFFFFF")
+    if rest.any():
+        raise ValueError("column 7 is reserved and must be 0")
+    for frame in np.unique(f):
+        i = np.nonzero(f == frame)[0]
+        if i.size > 1:
+            meet = (np.minimum(y1[i, None], y1[None, i]) > np.maximum(y0[i, None], y0[None, i])) & \
+                   (np.minimum(x1[i, None], x1[None, i]) > np.maximum(x0[i, None], x0[None, i]))
+            np.fill_diagonal(meet, False)
+            if meet.any():
+                a, c = (int(v[0]) for v in np.nonzero(meet))
+                raise ValueError(f"tiles {int(i[a])} and {int(i[c])} of canvas frame {int(frame)} overlap")
+    covered = int(((y1 - y0) * (x1 - x0)).sum()) == F * Hc * Wc           # (in bounds and disjoint: equal areas mean an exact cover)
+    return np.ascontiguousarray(t, dtype=np.int32), int(b.max()), covered
+
+
+def vis_compose(src, tiles, canvas_shape, lo=0.0, hi=1.0, background=255, *, max_border=None):
+    """uint8 [F, Hc, Wc, 3] on the GPU, composed in ONE launch (csrc/vis.hip) from src [S, T, C, h, w] (a float32 GPU tensor in the value
+    range [lo, hi], C = 1 or 3) and the tile table [n_tiles, 8] = (s, t, f, y0, x0, b, colour 0xRRGGBB, 0): each tile is frame (s, t) as
+    frames_postprocess's bytes inside a ring of width b in its colour, at (y0, x0) of canvas frame f; the rest is `background` (a grey
+    level). A host table is checked here (check_vis_tiles) and copied to the device once, and the canvas fill is skipped when its tiles
+    cover the canvas exactly. A GPU tensor (int32, contiguous) is taken as it is, with max_border = the largest b it holds given by the
+    caller: the kernel skips a row it cannot run and writes nothing outside the canvas. A non-contiguous `src` is read through one dense copy."""
+    if not (torch.is_tensor(src) and src.is_cuda):
+        raise _lib.VpxError("vis_compose: src must be a GPU tensor; visualizations are composed by a HIP kernel, there is no CPU fallback")
+    if src.dtype != torch.float32:
+        raise ValueError(f"vis_compose: expected float32, got {src.dtype}")
+    if src.ndim != 5:
+        raise ValueError(f"vis_compose: src must be [S, T, C, h, w] (got {tuple(src.shape)})")
+    S, T, C, h, w = (int(v) for v in src.shape)
+    if min(S, T, C, h, w) < 1:
+        raise ValueError(f"vis_compose: empty input {tuple(src.shape)}")
+    if len(canvas_shape) != 4 or int(canvas_shape[3]) != 3 or min(int(v) for v in canvas_shape) < 1:
+        raise ValueError(f"vis_compose: the canvas is [F, Hc, Wc, 3] with every size >= 1 (got {tuple(canvas_shape)})")
+    if not 0 <= int(background) <= 255:
+        raise ValueError(f"vis_compose: background {background} is not a grey level 0 ... 255")
+    F, Hc, Wc = (int(v) for v in canvas_shape[:3])
+    if torch.is_tensor(tiles) and tiles.is_cuda:
+        if tiles.dtype != torch.int32 or tiles.ndim != 2 or tiles.shape[1] != _lib.VIS_TILE_ROW or tiles.shape[0] < 1 or not tiles.is_contiguous():
+            raise ValueError(f"vis_compose: tiles must be a contiguous int32 table [n_tiles, {_lib.VIS_TILE_ROW}] (got {tiles.dtype} {tuple(tiles.shape)})")
+        if max_border is None:
+            raise ValueError("vis_compose: a table on the device needs max_border, the largest b it holds")
+        dev, bmax, fill = tiles, int(max_border), int(background)
+    else:
+        host, bmax, covered = check_vis_tiles(tiles, S, T, (h, w), (F, Hc, Wc, 3))
+        dev, fill = torch.from_numpy(host).to(src.device), (-1 if covered else int(background))
+    xc = src.detach().contiguous()
+    canvas = torch.empty((F, Hc, Wc, 3), dtype=torch.uint8, device=src.device)
+    with torch.cuda.device(src.device):
+        check(_lib.lib().vpx_vis_compose(ptr(xc), S, T, C, h, w, float(lo), float(hi), ptr(dev), int(dev.shape[0]), bmax, ptr(canvas), F, Hc, Wc,
+                                         fill, stream()), "vpx_vis_compose")
+    return canvas

@@ -7,10 +7,16 @@ models, train one model on one dataset, test every loaded model on every loaded 
     suite.train(epochs=10)
     suite.load_dataset("MMF", split="test", digits=procedural_digits())
     results = suite.test()
+    suite.visualize("vis_out", vis_idx=[0, 1, 2], vis_context_frame_idx=[0, 9])
 
 DEFAULT_RUN_CONFIG is the reference's DefaultRunConfig (defaults.py:37-64) key for key. WHAT DIFFERS FROM THE REFERENCE, all of it here:
-  * no_vis = True and no_wandb = True by default, and setting either to False raises NotImplementedError: rendering (gif / mp4) and
-    wandb logging are not part of this build. The vis_* / n_vis keys are kept so that a reference configuration is accepted.
+  * no_vis = True and no_wandb = True by default, and setting either to False raises NotImplementedError: train() and test() render
+    nothing and log nothing to wandb. The vis_* / n_vis keys are kept so that a reference configuration is accepted.
+  * Visualizations are made on request instead: suite.visualize(out_dir, vis_idx, ...) writes, for every loaded test set, what the
+    reference's test() writes under no_vis=False — visualization.visualize_sequences over the models test() would evaluate: a bordered
+    ground truth / prediction GIF per datapoint and model, a comparison PNG per datapoint, vis_info.txt. Each output is one canvas
+    composed by one HIP launch (ops.vis_compose, csrc/vis.hip). GIFs carry no matplotlib titles, one-channel frames are shown as grey
+    RGB, and there is no mp4 (visualization.py lists the departures).
   * metrics = ["mse", "psnr", "ssim"]: "lpips" needs pretrained weights this build does not ship.
   * One added key, test_batch_size = 1: test() may evaluate several datapoints per launch. Per-horizon means stay means over
     DATAPOINTS (batch means weighted by batch size), so a ragged last batch changes nothing.
@@ -52,6 +58,7 @@ from .datasets import DATASET_CLASSES
 from .measure import LOSS_CLASSES, PredictionLossProvider, PredictionMetricProvider
 from .models import AVAILABLE_MODELS, MODEL_CLASSES
 from .models.copy_last_frame import CopyLastFrame
+from .visualization import visualize_sequences
 
 OUT_PATH = Path("vp_suite_out")   #: trained models go to a timestamped directory below it unless `out_dir` is given
 
@@ -468,3 +475,28 @@ class VPSuite:
         for test_set, model_info_list in test_sets_and_model_lists:
             results[test_set.NAME] = self._test_on_dataset(model_info_list, test_set, run_config, brief_test)
         return results
+
+    # ===== VISUALIZATION ================================================================
+
+    def visualize(self, out_dir, vis_idx, vis_context_frame_idx=None, vis_vid_mode: str = "gif", **run_kwargs):
+        """Saves prediction visualizations of the datapoints `vis_idx` of every loaded test set, for the models test() would evaluate on
+        it (the same compatibility checks, the same frame adapters; models without a model_dir, such as the copy baseline, are left
+        out): per datapoint i and model j the bordered side-by-side video vis_<i>_model_<j>.gif of ground truth and prediction, and — if
+        vis_context_frame_idx is given — the comparison image vis_<i>.png of all models against the ground truth, plus vis_info.txt.
+        With one test set the files go to out_dir, with several to out_dir/<k> for the k-th. run_kwargs as for test(). Returns the
+        directories written, one per test set."""
+        if vis_vid_mode != "gif":
+            raise NotImplementedError(f"vis mode '{vis_vid_mode}': this build has no video encoder -> use the gif-mode for visualization")
+        test_sets_and_model_lists, run_config = self._prepare_testing(**run_kwargs)
+        test_sets_and_model_lists = list(test_sets_and_model_lists)
+        written = []
+        for k, (test_set, model_info_list) in enumerate(test_sets_and_model_lists):
+            test_data = test_set.test_data
+            out_path = Path(out_dir) if len(test_sets_and_model_lists) == 1 else Path(out_dir) / str(k)
+            out_path.mkdir(parents=True, exist_ok=True)
+            if getattr(test_data, "ON_THE_FLY", False):
+                test_data.reset_rng()   # the same sequences in every run
+            visualize_sequences(test_data, run_config["context_frames"], run_config["pred_frames"], model_info_list, self.device, out_path,
+                                vis_idx, vis_context_frame_idx, vis_vid_mode)
+            written.append(str(out_path))
+        return written
