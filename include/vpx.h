@@ -31,6 +31,10 @@
  * vpx_sigmoid_head_fwd / _bwd      sigmoid output + stack of frames         vp_suite/models/phydnet.py (encoder_fwd, forward)
  * vpx_rconv_fwd / _bwd             Conv2d / Conv3d, padding_mode='replicate'; time3ds  vp_suite/model_blocks/conv.py:9-55, models/unet3d.py:45
  * vpx_bn_relu_fwd / _bwd           BatchNorm + ReLU (+ MaxPool3d (1,2,2))   vp_suite/model_blocks/conv.py:22-27, models/unet3d.py:29
+ * vpx_dense_fwd / _bwd             nn.Linear (+ ReLU), strided rows         vp_suite/models/lstm.py:41,45,50 (to_linear, action_inflate, from_linear)
+ * vpx_lstm_cell_fwd / _bwd         nn.LSTMCell.forward                      vp_suite/models/lstm.py:46-49,95,108
+ * vpx_replicate_pad_fwd / _bwd     padding_mode="replicate" of a strided Conv2d   vp_suite/models/lstm.py:30-31 (enc2, enc3)
+ * vpx_resize_bilinear_fwd / _bwd   TF.Resize at the decoder's end, differentiable  vp_suite/models/lstm.py:57
  * vpx_mmnist_frames                MovingMNISTOnTheFly.__getitem__ (a batch) vp_suite/datasets/mmnist_on_the_fly.py:78-104,133-147
  * vpx_frames_preprocess            VPDataset.preprocess (a batch of stored sequences)  vp_suite/base/base_dataset.py:233-273, datasets/mmnist.py:56-57
  * vpx_clips_preprocess             the same for windows of long clips       vp_suite/datasets/kitti_raw.py:77-95, caltech_pedestrian.py:69-86
@@ -596,6 +600,70 @@ int vpx_bn_relu_fwd(const float* x, const float* stats, const float* gamma, cons
 size_t vpx_bn_relu_bwd_workspace_bytes(long long N, int H, int W, int C);
 int vpx_bn_relu_bwd(const float* x, const float* act, const float* stats, const float* gamma, const float* dact, const float* dpool, float* dx,
                     float* dgamma, float* dbeta, long long N, int H, int W, int C, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- NonConvLSTM (models/lstm.py): dense layer, LSTM cell, replicate padding, differentiable resize ------------------------------------ *
+ * Everything is fp32 FMA. Every sum runs in a fixed order and no launch uses float atomics: equal bits run to run in every mode.
+ *
+ * Dense layer: y [M][N] = x [M][K] * w [N][K]^T + bias [N] (nullable), then ReLU when relu != 0. x and y have row strides ldx >= K and
+ * ldy >= N in elements (a result may be a column slice of a wider buffer; the elements between the rows are never touched); w is the
+ * Linear's weight as stored. The launch is planned from (M, N, K) alone: a tile form from M (8 x 128 for M <= 8, 32 x 32 for M <= 32,
+ * else 128 x 32 rows x columns; all rows of M <= 128 are one workgroup's, so a weight element is read from memory by one workgroup) and
+ * a K split where the tiles alone leave CUs idle: min(ceil(512 / tiles), K / 256, 64) chunks of a length rounded up to 32; the partial
+ * sums [chunk][M][N] live in the workspace and a second launch adds them in chunk order, adds the bias and applies ReLU.
+ * vpx_dense_plan answers the plan of a forward (for the data gradient call it with N and K exchanged): it is filled by the function
+ * that plans the launches.
+ * Backward: dx [M][K] (row stride lddx) = dy' * w, dw [N][K] = dy'^T * x, db [N] = column sums of dy', where dy' = dy (row stride lddy)
+ * or, with relu != 0, dy masked by y > 0 (y: the forward's output, row stride ldy; otherwise y may be NULL). dx, dw, db are each nullable.
+ * accumulate != 0 ADDS to dw and db (the parameter gradients) instead of overwriting them; dx is always overwritten.
+ * One workspace query covers both directions. VPX_ERR_ARG: a size < 1, a NULL operand, a row stride shorter than its row.
+ * VPX_ERR_UNSUPPORTED: sizes beyond one launch. VPX_ERR_WORKSPACE: workspace NULL or smaller than the query's answer. */
+typedef struct vpx_dense_plan_info {
+    int32_t split;       /* 0: single pass (bias / ReLU in the epilogue); 1: K split + reduction */
+    int32_t chunks;      /* K chunks (1 without a split) */
+    int32_t chunk_len;   /* elements of K per chunk, a multiple of 32; the last chunk may be shorter */
+    int32_t form;        /* tile form 0 / 1 / 2 */
+    int32_t tile_m, tile_n, m_tiles, n_tiles;
+} vpx_dense_plan_info;
+int vpx_dense_plan(long long M, long long N, long long K, vpx_dense_plan_info* out);
+size_t vpx_dense_workspace_bytes(long long M, long long N, long long K);
+int vpx_dense_fwd(const float* x, long long ldx, const float* w, const float* bias, float* y, long long ldy, long long M, long long N, long long K,
+                  int relu, void* workspace, size_t workspace_bytes, void* stream);
+int vpx_dense_bwd(const float* x, long long ldx, const float* w, const float* y, long long ldy, const float* dy, long long lddy, float* dx,
+                  long long lddx, float* dw, float* db, long long M, long long N, long long K, int relu, int accumulate, void* workspace,
+                  size_t workspace_bytes, void* stream);
+/* LSTM cell (torch.nn.LSTMCell, gate order i, f, g, o): gates = x [M][Kx] * w_ih [4H][Kx]^T + h [M][H] * w_hh [4H][H]^T + b_ih + b_hh;
+ * c_new = sigmoid(f) * c + sigmoid(i) * tanh(g); h_new = sigmoid(o) * tanh(c_new). One call per layer-step: the two products are ONE K loop
+ * over [x | h] on the dense layer's launch, whose columns are walked gate-interleaved so that a thread holds the four gates of a hidden
+ * unit; the gate arithmetic is that launch's epilogue, or the reduction's where the plan of (M, 4H, Kx + H) splits K.
+ * x has a row stride ldx >= Kx; h, c, h_new, c_new are dense [M][H]. h == NULL means a zero hidden state: the h * w_hh^T half is skipped
+ * (the plan is that of (M, 4H, Kx)); c == NULL a zero cell state. The biases are nullable. `gates` (nullable) receives the ACTIVATED gates
+ * [M][4H] = [i | f | g | o]: the reserve the backward needs.
+ * Backward: from dh_new and dc_new (either may be NULL = zero), the reserve and c, it writes the gate gradient dgates [M][4H] (required:
+ * it is also the operand of everything below), dc = dc_total * f, dx = dgates * w_ih (dense [M][Kx]), dh = dgates * w_hh, dw_ih = dgates^T x,
+ * dw_hh = dgates^T h (zero for h == NULL), db_ih = db_hh = column sums of dgates; every output but dgates is nullable. accumulate != 0 ADDS
+ * to the four parameter gradients, so the steps of a pass can sum into one buffer. One workspace query covers both directions.
+ * Error codes as for the dense layer. */
+size_t vpx_lstm_cell_workspace_bytes(long long M, long long Kx, long long H);
+int vpx_lstm_cell_fwd(const float* x, long long ldx, const float* h, const float* c, const float* w_ih, const float* w_hh, const float* b_ih,
+                      const float* b_hh, float* h_new, float* c_new, float* gates, long long M, long long Kx, long long H, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int vpx_lstm_cell_bwd(const float* x, long long ldx, const float* h, const float* c, const float* w_ih, const float* w_hh, const float* gates,
+                      const float* dh_new, const float* dc_new, float* dx, float* dh, float* dc, float* dw_ih, float* dw_hh, float* db_ih,
+                      float* db_hh, float* dgates, long long M, long long Kx, long long H, int accumulate, void* workspace,
+                      size_t workspace_bytes, void* stream);
+/* Replicate padding of channels-last maps: y [N][H + 2 pad][W + 2 pad][C] with y[.., yy, xx, ..] = x[.., clamp(yy - pad), clamp(xx - pad), ..]
+ * (F.pad(mode="replicate")); a Conv2d with padding_mode="replicate" is this followed by the unpadded convolution. The backward is the
+ * adjoint as a gather: dx [N][H][W][C] sums, row by row, the padded cells that copied each pixel. One launch each, no workspace.
+ * VPX_ERR_ARG: a NULL pointer, a size < 1, pad < 0. VPX_ERR_UNSUPPORTED: a side beyond 32768, more work than one launch holds. */
+int vpx_replicate_pad_fwd(const float* x, float* y, long long N, int H, int W, int C, int pad, void* stream);
+int vpx_replicate_pad_bwd(const float* dy, float* dx, long long N, int H, int W, int C, int pad, void* stream);
+/* Differentiable bilinear resize: x channels-last [N][H][W][C] -> y planar [N][C][oh][ow], align_corners = False, no antialiasing (the model
+ * only enlarges; a side that shrinks is point-sampled between two taps as F.interpolate does, not averaged), the fp32 source coordinates of vpx_frames_preprocess and vpx_frames_adapt, horizontally first, every operation
+ * rounded on its own (held to a bound, not to bits). The backward takes dy planar and writes dx channels-last as a gather per source pixel
+ * over the output pixels whose taps name it, in row-major order. One launch each, no workspace.
+ * VPX_ERR_ARG: a NULL pointer, a size < 1. VPX_ERR_UNSUPPORTED: a side beyond 32768, more work than one launch holds. */
+int vpx_resize_bilinear_fwd(const float* x, float* y, long long N, int C, int H, int W, int oh, int ow, void* stream);
+int vpx_resize_bilinear_bwd(const float* dy, float* dx, long long N, int C, int H, int W, int oh, int ow, void* stream);
 
 /* ---- Moving MNIST generated on the device (vp_suite/datasets/mmnist_on_the_fly.py) ------------------------------
  * out [B, n_frames, C, S, S] (dense fp32, the reference's layout) from digits [n_glyphs, glyph_size, glyph_size] (bytes) and

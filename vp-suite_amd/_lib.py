@@ -104,6 +104,11 @@ class STLSTMPlanInfo(ctypes.Structure):
 ST_ROUTE_LN, ST_ROUTE_GEN1, ST_ROUTE_C5, ST_ROUTE_C5K = 0, 1, 2, 3
 
 
+class DensePlanInfo(ctypes.Structure):
+    """vpx_dense_plan_info: the launch a dense layer of (M, N, K) takes (include/vpx.h), every field an int32."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("split", "chunks", "chunk_len", "form", "tile_m", "tile_n", "m_tiles", "n_tiles")]
+
+
 class VpxError(RuntimeError):
     pass
 
@@ -226,6 +231,18 @@ SIGNATURES = {
     "vpx_bn_relu_fwd": (ci, [vp] * 6 + [ll, ci, ci, ci, vp]),
     "vpx_bn_relu_bwd_workspace_bytes": (sz, [ll, ci, ci, ci]),
     "vpx_bn_relu_bwd": (ci, [vp] * 9 + [ll, ci, ci, ci] + _ws),
+    # NonConvLSTM: dense layer, LSTM cell, replicate padding, differentiable resize
+    "vpx_dense_plan": (ci, [ll, ll, ll, vp]),
+    "vpx_dense_workspace_bytes": (sz, [ll, ll, ll]),
+    "vpx_dense_fwd": (ci, [vp, ll, vp, vp, vp, ll] + [ll] * 3 + [ci] + _ws),                          # x ldx w bias y ldy | M N K | relu
+    "vpx_dense_bwd": (ci, [vp, ll, vp, vp, ll, vp, ll, vp, ll, vp, vp] + [ll] * 3 + [ci, ci] + _ws),  # x ldx w y ldy dy lddy dx lddx dw db | M N K | relu accumulate
+    "vpx_lstm_cell_workspace_bytes": (sz, [ll, ll, ll]),
+    "vpx_lstm_cell_fwd": (ci, [vp, ll] + [vp] * 6 + [vp] * 3 + [ll] * 3 + _ws),                       # x ldx h c w_ih w_hh b_ih b_hh | h_new c_new gates | M Kx H
+    "vpx_lstm_cell_bwd": (ci, [vp, ll] + [vp] * 5 + [vp, vp] + [vp] * 8 + [ll] * 3 + [ci] + _ws),     # x ldx h c w_ih w_hh gates | dh_new dc_new | dx dh dc dw_ih dw_hh db_ih db_hh dgates | M Kx H | accumulate
+    "vpx_replicate_pad_fwd": (ci, [vp, vp, ll] + [ci] * 4 + [vp]),
+    "vpx_replicate_pad_bwd": (ci, [vp, vp, ll] + [ci] * 4 + [vp]),
+    "vpx_resize_bilinear_fwd": (ci, [vp, vp, ll] + [ci] * 5 + [vp]),
+    "vpx_resize_bilinear_bwd": (ci, [vp, vp, ll] + [ci] * 5 + [vp]),
     # Moving MNIST generated on the device
     "vpx_mmnist_frames": (ci, [vp, ci, ci, vp] + [ci] * 5 + [dbl, dbl, vp, vp]),     # digits N s | params B D F C S | lo hi | out
     # stored frames to a model-ready batch and back
