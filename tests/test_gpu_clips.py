@@ -143,6 +143,52 @@ def test_refusals_come_before_any_launch(vpx):
     assert vpx.ops.clips_preprocess(src, first, C.table([(0, 0)]), 4, out=out) is out
 
 
+@pytest.mark.parametrize("out_hw", [(6, 6), (11, 7)], ids=["copy", "resize"])
+def test_unchecked_rows_yield_zeros(vpx, out_hw):
+    """Rows that the host check refuses, handed to vpx_frames_preprocess and vpx_clips_preprocess as device tables (ops always checks a
+    host table, so the calls go through the library): every pointer and size of the call is valid, the kernel reads nothing for such a
+    row and writes zeros, and the rows beside it are computed. The suite's guard bands around `src` and `out` are checked after the test."""
+    L, lib, ops = vpx._lib, vpx._lib.lib(), vpx.ops
+    stream = torch.cuda.current_stream().cuda_stream
+    corners = [(4, 0), (0, 5), (-1, 0)]                                                            # below, right of, above the 9 x 10 frame
+
+    def launch(fn, name, src, args, rows):
+        out = torch.full((len(rows), 4, 3) + out_hw, 7.0, device="cuda")
+        dev = torch.tensor(rows, dtype=torch.int32).cuda()
+        L.check(fn(L.ptr(src), L.FRAMES_U8, *args, L.ptr(dev), len(rows), 4, 1, 6, 6, *out_hw, 3, 0.0, 1.0, L.ptr(out), stream), name)
+        return out
+
+    def judge(got, want, n_bad):
+        assert want.abs().sum() > 0 and torch.equal(got[0], want[0]) and torch.equal(got[-1], want[0]) and len(got) == n_bad + 2
+        for k in range(1, n_bad + 1):
+            assert not got[k].any(), k
+
+    # stored sequences
+    seqs = torch.from_numpy(np.stack(_clips("u8_rgb", lengths=(6, 6, 6), seed=2))).cuda()         # [3, 6, 9, 10, 3]
+    good = (2, 3, 4, 3)
+    bad = [(3, 0, 0, 0), (-1, 0, 0, 0)] + [(0, y, x, 0) for y, x in corners]
+    for row in bad:
+        with pytest.raises(ValueError):
+            ops.check_frames_table(np.array([row]), 3, (9, 10), (6, 6))
+    want = ops.frames_preprocess(seqs, np.array([good]), 4, crop_size=(6, 6), out_size=out_hw)
+    judge(launch(lib.vpx_frames_preprocess, "vpx_frames_preprocess", seqs, (3, 6, 9, 10, 3), [good] + bad + [good]), want, len(bad))
+    # clips back to back
+    src = torch.from_numpy(np.concatenate(_clips("u8_rgb"))).cuda()                               # [24, 9, 10, 3]
+    first = C.clip_first(LENGTHS)
+    good = (1, 8, 3, 4, 3, 0)
+    bad = [(3, 0, 0, 0, 0, 0), (-1, 0, 0, 0, 0, 0), (0, 4, 0, 0, 0, 0), (1, -1, 0, 0, 0, 0)] + [(0, 0, y, x, 0, 0) for y, x in corners]
+    for row in bad:
+        with pytest.raises(ValueError):
+            ops.check_clips_table(np.array([row]), first, 4, 1, (9, 10), (6, 6))
+    want = ops.clips_preprocess(src, first, np.array([good]), 4, crop_size=(6, 6), out_size=out_hw)
+    dev_first = torch.from_numpy(first).cuda()
+    judge(launch(lib.vpx_clips_preprocess, "vpx_clips_preprocess", src, (24, 9, 10, 3, L.ptr(dev_first), 3), [good] + bad + [good]), want, len(bad))
+    # an offset table whose last clip leaves src: that clip's row yields zeros, the other clips' rows are computed
+    late = torch.tensor([0, 7, 19, 25], dtype=torch.int64).cuda()
+    got = launch(lib.vpx_clips_preprocess, "vpx_clips_preprocess", src, (24, 9, 10, 3, L.ptr(late), 3), [good, (2, 0, 0, 0, 0, 0), good])
+    judge(got, want, 1)
+
+
 def test_a_clip_beyond_two_to_the_31_bytes(vpx, parity_log):
     """64-bit frame offsets: a 12-frame clip at the end of a buffer of 8 150 000 uint8 RGB frames of 9 x 10 (2.2 GB, allocated but only
     written at the two clips that are read); its first byte lies at 2 200 496 760 > 2^31. A 32-bit offset would read the unwritten

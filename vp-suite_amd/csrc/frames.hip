@@ -44,18 +44,17 @@ constexpr int FR_THREADS = 256;
 constexpr int FR_MAX_CS = 4;          // source channels a thread keeps in registers (gray, gray + alpha, RGB, RGBA)
 constexpr int FR_MAX_SIDE = 32768;    // frame, crop and output sides: coordinates and their float32 images stay exact
 
+// What every gather hands fr_group(): the stored elements, the destination and the value map. Where a frame lies in src, and which box of
+// it is taken, is the business of the launch's locator (below).
 struct FramesArgs {
-    const void* src;                   // [N][Tp][H][W][Cs]
-    const int* table;                  // [B][4] = (sequence, crop y0, crop x0, flip bits)
+    const void* src;                   // stored frames [H][W][Cs], channels last
     float* out;                        // [B][F][C_out][oh][ow]
-    long long N;
     long long items;                   // B * F * oh * Q: one thread each
-    int Tp, H, W, Cs, B, F, step, ch, cw, oh, ow, Cout;
+    int Cs, F, step, oh, ow, Cout;
     int Q;                             // groups of four pixels per output row (the last one partial if ow % 4)
     int vec;                           // 1: ow % 4 == 0 and `out` 16-byte aligned — every group is one 16-byte store per plane
     int scaled;                        // 1: (lo, hi) != (0, 1)
     float scale, lo;                   // float(hi - lo), float(lo)
-    float sy, sx;                      // float(ch) / float(oh), float(cw) / float(ow)
 };
 
 template <typename T> __device__ __forceinline__ float fr_unit(T raw);
@@ -76,10 +75,10 @@ template <typename T> __device__ __forceinline__ float fr_value(const FramesArgs
 // shared with adapt.hip.
 
 // The four neighbouring output pixels (row y, columns x0 .. x0 + 3) of output frame (b, f) in every channel, from the stored frame
-// `frame` [H][W][Cs] and the row's box and flips: the pixel contract above, once, for every kernel that gathers stored frames
-// (frames_preprocess_kernel: equal-length sequences; clips_preprocess_kernel: windows of long clips; clips_var_kernel: clips of mixed
-// frame sizes). The row stride W, the box ch x cw and its scales sy, sx are arguments: the first two kernels hand over the launch's,
-// the third its sample's. !valid: zeros, nothing is read.
+// `frame` [H][W][Cs] and the row's box and flips: the pixel contract above, once, for every launch that gathers stored frames
+// (SeqSource: equal-length sequences; ClipSource: windows of long clips; VarClipSource: clips of mixed frame sizes). The row stride W,
+// the box ch x cw and its scales sy, sx are arguments: the first two locators hand over the launch's, the third its sample's.
+// !valid: zeros, nothing is read.
 template <typename T, int RESIZE>
 __device__ __forceinline__ void fr_group(const FramesArgs& a, const T* frame, bool valid, int W, int ch, int cw, float sy, float sx, int cy, int cx, int flip,
                                          int b, int f, int y, int x0) {
@@ -146,77 +145,102 @@ __device__ __forceinline__ void fr_group(const FramesArgs& a, const T* frame, bo
     }
 }
 
-// thread = (sample b, frame f, output row y, group of four output pixels). RESIZE = 0: crop size == output size.
-template <typename T, int RESIZE>
-__global__ __launch_bounds__(FR_THREADS) void frames_preprocess_kernel(FramesArgs a) {
-    const long long item = (long long)blockIdx.x * FR_THREADS + threadIdx.x;
-    if (item >= a.items) return;
-    const int q = (int)(item % a.Q);
-    long long r = item / a.Q;
-    const int y = (int)(r % a.oh);
-    r /= a.oh;
-    const int f = (int)(r % a.F);
-    const int b = (int)(r / a.F);
-    const int* row = a.table + (size_t)b * 4;
-    const long long seq = row[0];
-    const int cy = row[1], cx = row[2], flip = row[3];
-    // a row the caller did not check (the table lives on the device) reads nothing out of bounds: it yields zeros
-    const bool valid = seq >= 0 && seq < a.N && cy >= 0 && cx >= 0 && (long long)cy + a.ch <= a.H && (long long)cx + a.cw <= a.W;
-    const T* frame = (const T*)a.src + ((size_t)(valid ? seq : 0) * a.Tp + (size_t)f * a.step) * ((size_t)a.H * a.W * a.Cs);   // 64-bit offsets throughout
-    fr_group<T, RESIZE>(a, frame, valid, a.W, a.ch, a.cw, a.sy, a.sx, cy, cx, flip, b, f, y, q << 2);
-}
+// A locator says where the frames of a launch lie: locate(a, b, f) yields, for output frame (b, f), the arguments of fr_group().
+// PER_SAMPLE: the locator, not the launch, chooses between copy and resize (FrSample::resize; otherwise not read).
+template <typename T>
+struct FrSample { const T* frame; int W, ch, cw; float sy, sx; int cy, cx, flip; bool valid, resize; };
+
+// Stored sequences of equal length: src [N][Tp][H][W][Cs], a table row is (sequence, crop y0, crop x0, flip bits) and output frame f of
+// sample b is stored frame f * step of that sequence. The crop box and its scales are the launch's.
+struct SeqSource {
+    static constexpr bool PER_SAMPLE = false;
+    const int* table;                  // [B][4]
+    long long N;
+    int Tp, H, W, ch, cw;
+    float sy, sx;                      // float(ch) / float(oh), float(cw) / float(ow)
+
+    template <typename T> __device__ __forceinline__ FrSample<T> locate(const FramesArgs& a, int b, int f) const {
+        const int* row = table + (size_t)b * 4;
+        const long long seq = row[0];
+        const int cy = row[1], cx = row[2], flip = row[3];
+        // a row the caller did not check (the table lives on the device) reads nothing out of bounds: it yields zeros
+        const bool valid = seq >= 0 && seq < N && cy >= 0 && cx >= 0 && (long long)cy + ch <= H && (long long)cx + cw <= W;
+        const T* frame = (const T*)a.src + ((size_t)(valid ? seq : 0) * Tp + (size_t)f * a.step) * ((size_t)H * W * a.Cs);   // 64-bit offsets throughout
+        return {frame, W, ch, cw, sy, sx, cy, cx, flip, valid, false};
+    }
+};
 
 // Windows of long clips: src holds every clip of a split back to back, clip c being frames clip_first[c] .. clip_first[c + 1] - 1;
 // a table row is (clip, start frame within the clip, crop y0, crop x0, flip bits, 0) and output frame f of sample b is stored frame
-// clip_first[clip] + start + f * step. Everything after the frame pointer is fr_group(), so the pixels are those of the kernel above.
-struct ClipsArgs {
-    FramesArgs fr;                     // src, out and the geometry; table, N and Tp are not used
+// clip_first[clip] + start + f * step. Everything after the frame pointer is fr_group(), so the pixels are those of the locator above.
+struct ClipSource {
+    static constexpr bool PER_SAMPLE = false;
     const long long* clip_first;       // [n_clips + 1], on the device; the last entry is the number of frames in src
     const int* table;                  // [B][6]
     long long n_clips, total;          // total: frames in src
-};
+    int H, W, ch, cw;
+    float sy, sx;                      // float(ch) / float(oh), float(cw) / float(ow)
 
-template <typename T, int RESIZE>
-__global__ __launch_bounds__(FR_THREADS) void clips_preprocess_kernel(ClipsArgs c) {
-    const FramesArgs& a = c.fr;
-    const long long item = (long long)blockIdx.x * FR_THREADS + threadIdx.x;
-    if (item >= a.items) return;
-    const int q = (int)(item % a.Q);
-    long long r = item / a.Q;
-    const int y = (int)(r % a.oh);
-    r /= a.oh;
-    const int f = (int)(r % a.F);
-    const int b = (int)(r / a.F);
-    const int* row = c.table + (size_t)b * 6;
-    const long long clip = row[0], start = row[1];
-    const int cy = row[2], cx = row[3], flip = row[4];
-    // as above: a row (or an offset table) the caller did not check yields zeros and reads nothing outside src
-    bool valid = clip >= 0 && clip < c.n_clips && start >= 0 && cy >= 0 && cx >= 0 && (long long)cy + a.ch <= a.H && (long long)cx + a.cw <= a.W;
-    long long first = 0;
-    if (valid) {
-        first = c.clip_first[clip];
-        const long long end = c.clip_first[clip + 1];
-        valid = first >= 0 && end <= c.total && first + start + (long long)(a.F - 1) * a.step < end;
+    template <typename T> __device__ __forceinline__ FrSample<T> locate(const FramesArgs& a, int b, int f) const {
+        const int* row = table + (size_t)b * 6;
+        const long long clip = row[0], start = row[1];
+        const int cy = row[2], cx = row[3], flip = row[4];
+        // as above: a row (or an offset table) the caller did not check yields zeros and reads nothing outside src
+        bool valid = clip >= 0 && clip < n_clips && start >= 0 && cy >= 0 && cx >= 0 && (long long)cy + ch <= H && (long long)cx + cw <= W;
+        long long first = 0;
+        if (valid) {
+            first = clip_first[clip];
+            const long long end = clip_first[clip + 1];
+            valid = first >= 0 && end <= total && first + start + (long long)(a.F - 1) * a.step < end;
+        }
+        const T* frame = (const T*)a.src + (size_t)(valid ? first + start + (long long)f * a.step : 0) * ((size_t)H * W * a.Cs);   // 64-bit offsets throughout
+        return {frame, W, ch, cw, sy, sx, cy, cx, flip, valid, false};
     }
-    const T* frame = (const T*)a.src + (size_t)(valid ? first + start + (long long)f * a.step : 0) * ((size_t)a.H * a.W * a.Cs);   // 64-bit offsets throughout
-    fr_group<T, RESIZE>(a, frame, valid, a.W, a.ch, a.cw, a.sy, a.sx, cy, cx, flip, b, f, y, q << 2);
-}
+};
 
 // Windows of clips whose frame sizes differ: src is ONE element buffer holding every clip back to back and clip_geom [n_clips][4] =
 // (element offset of the clip's first frame, frame count, H_i, W_i) says where each lies. A table row is (clip, start frame, box y0,
 // box x0, box h, box w, flip bits, 0): the box of stored frame start + f * step goes to oh x ow through fr_group(), with the sample's row
-// stride, box and scales where the kernels above hand over the launch's. A box of the output's size takes the path without resize, so
-// equal shapes give the bits of clips_preprocess_kernel; the choice is per sample (uniform over a sample's threads).
-struct ClipsVarArgs {
-    FramesArgs fr;                     // src, out, Cs, F, step, oh, ow, Cout and the value map; H, W, ch, cw, sy, sx are not used
+// stride, box and scales where the locators above hand over the launch's. A box of the output's size takes the path without resize, so
+// equal shapes give the bits of ClipSource; the choice is per sample (uniform over a sample's threads).
+struct VarClipSource {
+    static constexpr bool PER_SAMPLE = true;
     const long long* geom;             // [n_clips][4], on the device
     const int* table;                  // [B][8]
     long long n_clips, total;          // total: elements in src
+
+    template <typename T> __device__ __forceinline__ FrSample<T> locate(const FramesArgs& a, int b, int f) const {
+        const int* row = table + (size_t)b * 8;
+        const long long clip = row[0], start = row[1];
+        const int cy = row[2], cx = row[3], bh = row[4], bw = row[5], flip = row[6];
+        // as above: a row (or a geometry table) the caller did not check yields zeros and reads nothing outside src
+        bool valid = clip >= 0 && clip < n_clips && start >= 0 && cy >= 0 && cx >= 0 && bh >= 1 && bw >= 1;
+        long long first = 0, frame_elems = 0;
+        int W = 1;
+        if (valid) {
+            const long long* g = geom + (size_t)clip * 4;
+            const long long count = g[1], H = g[2], Wl = g[3];
+            first = g[0];
+            valid = first >= 0 && first <= total && count >= 1 && H >= 1 && Wl >= 1 && H <= FR_MAX_SIDE && Wl <= FR_MAX_SIDE &&
+                    (long long)cy + bh <= H && (long long)cx + bw <= Wl && start + (long long)(a.F - 1) * a.step < count;
+            if (valid) {
+                frame_elems = H * Wl * a.Cs;                                                          // <= 2^32: no overflow
+                valid = count <= (total - first) / frame_elems;                                       // the whole clip lies inside src
+                W = (int)Wl;
+            }
+        }
+        const T* frame = (const T*)a.src + (size_t)(valid ? first + (start + (long long)f * a.step) * frame_elems : 0);   // 64-bit offsets throughout
+        const bool resize = valid && (bh != a.oh || bw != a.ow);
+        return {frame, W, bh, bw, resize ? (float)bh / (float)a.oh : 1.0f, resize ? (float)bw / (float)a.ow : 1.0f, cy, cx, flip, valid, resize};
+    }
 };
 
-template <typename T>
-__global__ __launch_bounds__(FR_THREADS) void clips_var_kernel(ClipsVarArgs c) {
-    const FramesArgs& a = c.fr;
+// thread = (sample b, frame f, output row y, group of four output pixels). RESIZE = 0: crop size == output size; 1: bilinear resize;
+// FR_PER_SAMPLE: the locator says which, sample by sample.
+constexpr int FR_PER_SAMPLE = 2;
+
+template <typename T, typename Source, int RESIZE>
+__global__ __launch_bounds__(FR_THREADS) void frames_gather_kernel(FramesArgs a, Source s) {
     const long long item = (long long)blockIdx.x * FR_THREADS + threadIdx.x;
     if (item >= a.items) return;
     const int q = (int)(item % a.Q);
@@ -225,30 +249,11 @@ __global__ __launch_bounds__(FR_THREADS) void clips_var_kernel(ClipsVarArgs c) {
     r /= a.oh;
     const int f = (int)(r % a.F);
     const int b = (int)(r / a.F);
-    const int* row = c.table + (size_t)b * 8;
-    const long long clip = row[0], start = row[1];
-    const int cy = row[2], cx = row[3], bh = row[4], bw = row[5], flip = row[6];
-    // as above: a row (or a geometry table) the caller did not check yields zeros and reads nothing outside src
-    bool valid = clip >= 0 && clip < c.n_clips && start >= 0 && cy >= 0 && cx >= 0 && bh >= 1 && bw >= 1;
-    long long first = 0, frame_elems = 0;
-    int W = 1;
-    if (valid) {
-        const long long* g = c.geom + (size_t)clip * 4;
-        const long long count = g[1], H = g[2], Wl = g[3];
-        first = g[0];
-        valid = first >= 0 && first <= c.total && count >= 1 && H >= 1 && Wl >= 1 && H <= FR_MAX_SIDE && Wl <= FR_MAX_SIDE &&
-                (long long)cy + bh <= H && (long long)cx + bw <= Wl && start + (long long)(a.F - 1) * a.step < count;
-        if (valid) {
-            frame_elems = H * Wl * a.Cs;                                                              // <= 2^32: no overflow
-            valid = count <= (c.total - first) / frame_elems;                                         // the whole clip lies inside src
-            W = (int)Wl;
-        }
-    }
-    const T* frame = (const T*)a.src + (size_t)(valid ? first + (start + (long long)f * a.step) * frame_elems : 0);   // 64-bit offsets throughout
-    if (valid && (bh != a.oh || bw != a.ow))
-        fr_group<T, 1>(a, frame, true, W, bh, bw, (float)bh / (float)a.oh, (float)bw / (float)a.ow, cy, cx, flip, b, f, y, q << 2);
+    const FrSample<T> p = s.template locate<T>(a, b, f);
+    if (RESIZE == FR_PER_SAMPLE ? p.resize : RESIZE != 0)
+        fr_group<T, 1>(a, p.frame, p.valid, p.W, p.ch, p.cw, p.sy, p.sx, p.cy, p.cx, p.flip, b, f, y, q << 2);
     else
-        fr_group<T, 0>(a, frame, valid, W, bh, bw, 1.0f, 1.0f, cy, cx, flip, b, f, y, q << 2);
+        fr_group<T, 0>(a, p.frame, p.valid, p.W, p.ch, p.cw, p.sy, p.sx, p.cy, p.cx, p.flip, b, f, y, q << 2);
 }
 
 struct PostArgs {
@@ -324,7 +329,7 @@ __global__ __launch_bounds__(FR_THREADS) void actions_gather_kernel(ActionsArgs 
 struct ActionsDiffArgs {
     const void* src;                   // [total][A]: per-frame positions, every clip back to back
     const long long* clip_first;       // [n_clips + 1], on the device
-    const int* table;                  // [B][8], the table of clips_var_kernel: columns 0 (clip) and 1 (start frame) are all that is read
+    const int* table;                  // [B][8], the table of VarClipSource: columns 0 (clip) and 1 (start frame) are all that is read
     float* out;                        // [B][F - 1][A]
     long long n_clips, total;          // total: rows in src
     long long items;                   // B * (F - 1) * A: one thread each
@@ -356,33 +361,85 @@ __global__ __launch_bounds__(FR_THREADS) void actions_diff_kernel(ActionsDiffArg
     a.out[item] = v;
 }
 
-template <typename T>
-static void launch_preprocess(const FramesArgs& a, int resize, unsigned blocks, hipStream_t stream) {
-    if (resize) VPX_LAUNCH((frames_preprocess_kernel<T, 1>), dim3(blocks), dim3(FR_THREADS), 0, stream, a);
-    else VPX_LAUNCH((frames_preprocess_kernel<T, 0>), dim3(blocks), dim3(FR_THREADS), 0, stream, a);
+static unsigned fr_blocks(long long items) { return (unsigned)((items + FR_THREADS - 1) / FR_THREADS); }
+
+// RESIZE of frames_gather_kernel for one element type: the launch's `resize` (crop size != output size), or the locator's own choice.
+template <typename T, typename Source>
+static void launch_gather(const FramesArgs& a, const Source& s, bool resize, hipStream_t stream) {
+    const dim3 grid(fr_blocks(a.items)), block(FR_THREADS);
+    if constexpr (Source::PER_SAMPLE) VPX_LAUNCH((frames_gather_kernel<T, Source, FR_PER_SAMPLE>), grid, block, 0, stream, a, s);
+    else if (resize) VPX_LAUNCH((frames_gather_kernel<T, Source, 1>), grid, block, 0, stream, a, s);
+    else VPX_LAUNCH((frames_gather_kernel<T, Source, 0>), grid, block, 0, stream, a, s);
 }
 
-template <typename T>
-static void launch_clips(const ClipsArgs& c, int resize, unsigned blocks, hipStream_t stream) {
-    if (resize) VPX_LAUNCH((clips_preprocess_kernel<T, 1>), dim3(blocks), dim3(FR_THREADS), 0, stream, c);
-    else VPX_LAUNCH((clips_preprocess_kernel<T, 0>), dim3(blocks), dim3(FR_THREADS), 0, stream, c);
-}
-
-// What both gathers hand fr_group(): the geometry, the value map and the destination (checked by the entry points).
-static FramesArgs frames_args(const void* src, float* out, int H, int W, int Cs, int B, int n_frames, int seq_step, int ch, int cw, int oh, int ow,
-                              int C_out, double lo, double hi) {
+// The launch of every frame gather, its arguments checked by the entry point: what fr_group() reads, then the element type by RESIZE
+// dispatch over the locator `s`.
+template <typename Source>
+static int gather_frames(const void* src, int dtype, int Cs, const Source& s, int B, int n_frames, int seq_step, bool resize, int oh, int ow, int C_out,
+                         double lo, double hi, float* out, void* stream) {
     FramesArgs a;
-    a.src = src; a.table = nullptr; a.out = out;
-    a.N = 0; a.Tp = 0; a.H = H; a.W = W; a.Cs = Cs; a.B = B; a.F = n_frames; a.step = seq_step;
-    a.ch = ch; a.cw = cw; a.oh = oh; a.ow = ow; a.Cout = C_out; a.Q = (ow + 3) / 4;
+    a.src = src; a.out = out;
+    a.Cs = Cs; a.F = n_frames; a.step = seq_step; a.oh = oh; a.ow = ow; a.Cout = C_out; a.Q = (ow + 3) / 4;
     a.items = (long long)B * n_frames * oh * a.Q;
     a.vec = (ow % 4 == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
     a.scaled = (lo != 0.0 || hi != 1.0) ? 1 : 0;
     a.scale = (float)(hi - lo);
     a.lo = (float)lo;
-    a.sy = (float)ch / (float)oh;
-    a.sx = (float)cw / (float)ow;
-    return a;
+    if (dtype == VPX_FRAMES_U8) launch_gather<unsigned char>(a, s, resize, (hipStream_t)stream);
+    else if (dtype == VPX_FRAMES_U16) launch_gather<unsigned short>(a, s, resize, (hipStream_t)stream);
+    else launch_gather<float>(a, s, resize, (hipStream_t)stream);
+    VPX_CHECK_HIP(vpx_hip_last_error());
+    return VPX_OK;
+}
+
+// ---- the refusals several entry points share, once: VPX_OK, or the code after set_error() ----
+#define FR_TRY(check) do { const int rc__ = (check); if (rc__ != VPX_OK) return rc__; } while (0)
+
+static int check_dtype(const char* who, int dtype, bool known, const char* stored) {
+    if (!known) { set_error("%s: unknown element type %d (%s are stored)", who, dtype, stored); return VPX_ERR_ARG; }
+    return VPX_OK;
+}
+static int check_frame_dtype(const char* who, int dtype) { return check_dtype(who, dtype, dtype == VPX_FRAMES_U8 || dtype == VPX_FRAMES_U16 || dtype == VPX_FRAMES_F32, "uint8, uint16 and float32"); }
+static int check_action_dtype(const char* who, int dtype) { return check_dtype(who, dtype, dtype == VPX_ACTIONS_F32 || dtype == VPX_ACTIONS_F64, "float32 and float64"); }
+static int check_counts(const char* who, int B, int n_frames, int seq_step) {
+    if (B < 1 || n_frames < 1 || seq_step < 1) { set_error("%s: B, n_frames and seq_step must be >= 1 (got %d, %d, %d)", who, B, n_frames, seq_step); return VPX_ERR_ARG; }
+    return VPX_OK;
+}
+static int check_clips_in_frames(const char* who, long long n_clips, long long total_frames, int n_frames, int seq_step) {
+    if (n_clips > total_frames) { set_error("%s: %lld clips in %lld stored frames (a clip holds at least one)", who, n_clips, total_frames); return VPX_ERR_ARG; }
+    if ((long long)(n_frames - 1) * seq_step >= total_frames) { set_error("%s: frame %d at step %d lies past the %lld stored frames", who, n_frames - 1, seq_step, total_frames); return VPX_ERR_ARG; }
+    return VPX_OK;
+}
+static int check_value_range(const char* who, double lo, double hi) {
+    if (hi == lo) { set_error("%s: empty value range [%g, %g]", who, lo, hi); return VPX_ERR_ARG; }
+    return VPX_OK;
+}
+// one thread per item, FR_THREADS per block: the block count must fit a grid's 31 bits (the product in double: it may pass 2^63)
+static bool fits_one_launch(double items) { return items / FR_THREADS + 1.0 <= 2147483647.0; }
+static int check_rows_launch(const char* who, int B, int rows, int A) {
+    if (!fits_one_launch((double)B * rows * A)) { set_error("%s: %d samples of %d rows of %d exceed one launch", who, B, rows, A); return VPX_ERR_UNSUPPORTED; }
+    return VPX_OK;
+}
+static int check_crop_sizes(const char* who, int ch, int cw, int oh, int ow) {
+    if (ch < 1 || cw < 1 || oh < 1 || ow < 1) { set_error("%s: crop and output sizes must be >= 1 (got crop %dx%d, output %dx%d)", who, ch, cw, oh, ow); return VPX_ERR_ARG; }
+    return VPX_OK;
+}
+static int check_value_map(const char* who, int Cs, int C_out, double lo, double hi) {
+    if (C_out != Cs && !(Cs == 1 && C_out == 3)) { set_error("%s: %d output channels from %d stored ones (equal, or 3 from 1)", who, C_out, Cs); return VPX_ERR_ARG; }
+    FR_TRY(check_value_range(who, lo, hi));
+    if (Cs > FR_MAX_CS) { set_error("%s: %d stored channels exceed the kernel's %d", who, Cs, FR_MAX_CS); return VPX_ERR_UNSUPPORTED; }
+    return VPX_OK;
+}
+static int check_frames_launch(const char* who, int B, int n_frames, int oh, int ow) {
+    if (!fits_one_launch((double)B * n_frames * oh * ((ow + 3) / 4))) { set_error("%s: %d samples of %d %dx%d frames exceed one launch", who, B, n_frames, oh, ow); return VPX_ERR_UNSUPPORTED; }
+    return VPX_OK;
+}
+// a launch with one crop box (sequences, clips back to back): the box inside the frame, the value map, the sides, the launch size
+static int check_boxed_gather(const char* who, int H, int W, int Cs, int B, int n_frames, int ch, int cw, int oh, int ow, int C_out, double lo, double hi) {
+    if (ch > H || cw > W) { set_error("%s: the %dx%d crop box lies outside the %dx%d frame (there is no padding)", who, ch, cw, H, W); return VPX_ERR_ARG; }
+    FR_TRY(check_value_map(who, Cs, C_out, lo, hi));
+    if (H > FR_MAX_SIDE || W > FR_MAX_SIDE || oh > FR_MAX_SIDE || ow > FR_MAX_SIDE) { set_error("%s: a side beyond %d (frame %dx%d, output %dx%d)", who, FR_MAX_SIDE, H, W, oh, ow); return VPX_ERR_UNSUPPORTED; }
+    return check_frames_launch(who, B, n_frames, oh, ow);
 }
 
 }  // namespace vpx
@@ -395,28 +452,14 @@ int vpx_frames_preprocess(const void* src, int dtype, long long N, int Tp, int H
                           int seq_step, int ch, int cw, int oh, int ow, int C_out, double lo, double hi, float* out, void* stream) {
     const char* who = "vpx_frames_preprocess";
     if (!src || !table || !out) { set_error("%s: NULL tensor argument", who); return VPX_ERR_ARG; }
-    if (dtype != VPX_FRAMES_U8 && dtype != VPX_FRAMES_U16 && dtype != VPX_FRAMES_F32) { set_error("%s: unknown element type %d (uint8, uint16 and float32 are stored)", who, dtype); return VPX_ERR_ARG; }
+    FR_TRY(check_frame_dtype(who, dtype));
     if (N < 1 || Tp < 1 || H < 1 || W < 1 || Cs < 1) { set_error("%s: every source size must be >= 1 (got N=%lld T'=%d H=%d W=%d Cs=%d)", who, N, Tp, H, W, Cs); return VPX_ERR_ARG; }
-    if (B < 1 || n_frames < 1 || seq_step < 1) { set_error("%s: B, n_frames and seq_step must be >= 1 (got %d, %d, %d)", who, B, n_frames, seq_step); return VPX_ERR_ARG; }
-    if (ch < 1 || cw < 1 || oh < 1 || ow < 1) { set_error("%s: crop and output sizes must be >= 1 (got crop %dx%d, output %dx%d)", who, ch, cw, oh, ow); return VPX_ERR_ARG; }
+    FR_TRY(check_counts(who, B, n_frames, seq_step));
+    FR_TRY(check_crop_sizes(who, ch, cw, oh, ow));
     if ((long long)(n_frames - 1) * seq_step >= Tp) { set_error("%s: frame %d at step %d lies past the %d stored frames", who, n_frames - 1, seq_step, Tp); return VPX_ERR_ARG; }
-    if (ch > H || cw > W) { set_error("%s: the %dx%d crop box lies outside the %dx%d frame (there is no padding)", who, ch, cw, H, W); return VPX_ERR_ARG; }
-    if (C_out != Cs && !(Cs == 1 && C_out == 3)) { set_error("%s: %d output channels from %d stored ones (equal, or 3 from 1)", who, C_out, Cs); return VPX_ERR_ARG; }
-    if (hi == lo) { set_error("%s: empty value range [%g, %g]", who, lo, hi); return VPX_ERR_ARG; }
-    if (Cs > FR_MAX_CS) { set_error("%s: %d stored channels exceed the kernel's %d", who, Cs, FR_MAX_CS); return VPX_ERR_UNSUPPORTED; }
-    if (H > FR_MAX_SIDE || W > FR_MAX_SIDE || oh > FR_MAX_SIDE || ow > FR_MAX_SIDE) { set_error("%s: a side beyond %d (frame %dx%d, output %dx%d)", who, FR_MAX_SIDE, H, W, oh, ow); return VPX_ERR_UNSUPPORTED; }
-    const int Q = (ow + 3) / 4;
-    const double items_d = (double)B * n_frames * oh * Q;
-    if (items_d / FR_THREADS + 1.0 > 2147483647.0) { set_error("%s: %d samples of %d %dx%d frames exceed one launch", who, B, n_frames, oh, ow); return VPX_ERR_UNSUPPORTED; }
-    FramesArgs a = frames_args(src, out, H, W, Cs, B, n_frames, seq_step, ch, cw, oh, ow, C_out, lo, hi);
-    a.table = table; a.N = N; a.Tp = Tp;
-    const int resize = (ch != oh || cw != ow) ? 1 : 0;
-    const unsigned blocks = (unsigned)((a.items + FR_THREADS - 1) / FR_THREADS);
-    if (dtype == VPX_FRAMES_U8) launch_preprocess<unsigned char>(a, resize, blocks, (hipStream_t)stream);
-    else if (dtype == VPX_FRAMES_U16) launch_preprocess<unsigned short>(a, resize, blocks, (hipStream_t)stream);
-    else launch_preprocess<float>(a, resize, blocks, (hipStream_t)stream);
-    VPX_CHECK_HIP(vpx_hip_last_error());
-    return VPX_OK;
+    FR_TRY(check_boxed_gather(who, H, W, Cs, B, n_frames, ch, cw, oh, ow, C_out, lo, hi));
+    const SeqSource s{table, N, Tp, H, W, ch, cw, (float)ch / (float)oh, (float)cw / (float)ow};
+    return gather_frames(src, dtype, Cs, s, B, n_frames, seq_step, ch != oh || cw != ow, oh, ow, C_out, lo, hi, out, stream);
 }
 
 int vpx_clips_preprocess(const void* src, int dtype, long long total_frames, int H, int W, int Cs, const long long* clip_first, long long n_clips,
@@ -424,77 +467,50 @@ int vpx_clips_preprocess(const void* src, int dtype, long long total_frames, int
                          float* out, void* stream) {
     const char* who = "vpx_clips_preprocess";
     if (!src || !clip_first || !table || !out) { set_error("%s: NULL tensor argument", who); return VPX_ERR_ARG; }
-    if (dtype != VPX_FRAMES_U8 && dtype != VPX_FRAMES_U16 && dtype != VPX_FRAMES_F32) { set_error("%s: unknown element type %d (uint8, uint16 and float32 are stored)", who, dtype); return VPX_ERR_ARG; }
+    FR_TRY(check_frame_dtype(who, dtype));
     if (total_frames < 1 || n_clips < 1 || H < 1 || W < 1 || Cs < 1) { set_error("%s: every source size must be >= 1 (got frames=%lld clips=%lld H=%d W=%d Cs=%d)", who, total_frames, n_clips, H, W, Cs); return VPX_ERR_ARG; }
-    if (B < 1 || n_frames < 1 || seq_step < 1) { set_error("%s: B, n_frames and seq_step must be >= 1 (got %d, %d, %d)", who, B, n_frames, seq_step); return VPX_ERR_ARG; }
-    if (ch < 1 || cw < 1 || oh < 1 || ow < 1) { set_error("%s: crop and output sizes must be >= 1 (got crop %dx%d, output %dx%d)", who, ch, cw, oh, ow); return VPX_ERR_ARG; }
-    if (n_clips > total_frames) { set_error("%s: %lld clips in %lld stored frames (a clip holds at least one)", who, n_clips, total_frames); return VPX_ERR_ARG; }
-    if ((long long)(n_frames - 1) * seq_step >= total_frames) { set_error("%s: frame %d at step %d lies past the %lld stored frames", who, n_frames - 1, seq_step, total_frames); return VPX_ERR_ARG; }
-    if (ch > H || cw > W) { set_error("%s: the %dx%d crop box lies outside the %dx%d frame (there is no padding)", who, ch, cw, H, W); return VPX_ERR_ARG; }
-    if (C_out != Cs && !(Cs == 1 && C_out == 3)) { set_error("%s: %d output channels from %d stored ones (equal, or 3 from 1)", who, C_out, Cs); return VPX_ERR_ARG; }
-    if (hi == lo) { set_error("%s: empty value range [%g, %g]", who, lo, hi); return VPX_ERR_ARG; }
-    if (Cs > FR_MAX_CS) { set_error("%s: %d stored channels exceed the kernel's %d", who, Cs, FR_MAX_CS); return VPX_ERR_UNSUPPORTED; }
-    if (H > FR_MAX_SIDE || W > FR_MAX_SIDE || oh > FR_MAX_SIDE || ow > FR_MAX_SIDE) { set_error("%s: a side beyond %d (frame %dx%d, output %dx%d)", who, FR_MAX_SIDE, H, W, oh, ow); return VPX_ERR_UNSUPPORTED; }
-    const double items_d = (double)B * n_frames * oh * ((ow + 3) / 4);
-    if (items_d / FR_THREADS + 1.0 > 2147483647.0) { set_error("%s: %d samples of %d %dx%d frames exceed one launch", who, B, n_frames, oh, ow); return VPX_ERR_UNSUPPORTED; }
-    ClipsArgs c;
-    c.fr = frames_args(src, out, H, W, Cs, B, n_frames, seq_step, ch, cw, oh, ow, C_out, lo, hi);
-    c.clip_first = clip_first; c.table = table; c.n_clips = n_clips; c.total = total_frames;
-    const int resize = (ch != oh || cw != ow) ? 1 : 0;
-    const unsigned blocks = (unsigned)((c.fr.items + FR_THREADS - 1) / FR_THREADS);
-    if (dtype == VPX_FRAMES_U8) launch_clips<unsigned char>(c, resize, blocks, (hipStream_t)stream);
-    else if (dtype == VPX_FRAMES_U16) launch_clips<unsigned short>(c, resize, blocks, (hipStream_t)stream);
-    else launch_clips<float>(c, resize, blocks, (hipStream_t)stream);
-    VPX_CHECK_HIP(vpx_hip_last_error());
-    return VPX_OK;
+    FR_TRY(check_counts(who, B, n_frames, seq_step));
+    FR_TRY(check_crop_sizes(who, ch, cw, oh, ow));
+    FR_TRY(check_clips_in_frames(who, n_clips, total_frames, n_frames, seq_step));
+    FR_TRY(check_boxed_gather(who, H, W, Cs, B, n_frames, ch, cw, oh, ow, C_out, lo, hi));
+    const ClipSource s{clip_first, table, n_clips, total_frames, H, W, ch, cw, (float)ch / (float)oh, (float)cw / (float)ow};
+    return gather_frames(src, dtype, Cs, s, B, n_frames, seq_step, ch != oh || cw != ow, oh, ow, C_out, lo, hi, out, stream);
 }
 
 int vpx_clips_preprocess_var(const void* src, int dtype, long long total_elems, int Cs, const long long* clip_geom, long long n_clips, const int* table,
                              int B, int n_frames, int seq_step, int oh, int ow, int C_out, double lo, double hi, float* out, void* stream) {
     const char* who = "vpx_clips_preprocess_var";
     if (!src || !clip_geom || !table || !out) { set_error("%s: NULL tensor argument", who); return VPX_ERR_ARG; }
-    if (dtype != VPX_FRAMES_U8 && dtype != VPX_FRAMES_U16 && dtype != VPX_FRAMES_F32) { set_error("%s: unknown element type %d (uint8, uint16 and float32 are stored)", who, dtype); return VPX_ERR_ARG; }
+    FR_TRY(check_frame_dtype(who, dtype));
     if (total_elems < 1 || n_clips < 1 || Cs < 1) { set_error("%s: every source size must be >= 1 (got elements=%lld clips=%lld Cs=%d)", who, total_elems, n_clips, Cs); return VPX_ERR_ARG; }
-    if (B < 1 || n_frames < 1 || seq_step < 1) { set_error("%s: B, n_frames and seq_step must be >= 1 (got %d, %d, %d)", who, B, n_frames, seq_step); return VPX_ERR_ARG; }
+    FR_TRY(check_counts(who, B, n_frames, seq_step));
     if (oh < 1 || ow < 1) { set_error("%s: output sizes must be >= 1 (got output %dx%d)", who, oh, ow); return VPX_ERR_ARG; }
     if (n_clips > total_elems / Cs) { set_error("%s: %lld clips in %lld stored elements of %d channels (a clip holds at least one frame of one pixel)", who, n_clips, total_elems, Cs); return VPX_ERR_ARG; }
     if ((long long)(n_frames - 1) * seq_step >= total_elems / Cs) { set_error("%s: frame %d at step %d lies past the %lld stored elements", who, n_frames - 1, seq_step, total_elems); return VPX_ERR_ARG; }
-    if (C_out != Cs && !(Cs == 1 && C_out == 3)) { set_error("%s: %d output channels from %d stored ones (equal, or 3 from 1)", who, C_out, Cs); return VPX_ERR_ARG; }
-    if (hi == lo) { set_error("%s: empty value range [%g, %g]", who, lo, hi); return VPX_ERR_ARG; }
-    if (Cs > FR_MAX_CS) { set_error("%s: %d stored channels exceed the kernel's %d", who, Cs, FR_MAX_CS); return VPX_ERR_UNSUPPORTED; }
+    FR_TRY(check_value_map(who, Cs, C_out, lo, hi));
     if (oh > FR_MAX_SIDE || ow > FR_MAX_SIDE) { set_error("%s: a side beyond %d (output %dx%d)", who, FR_MAX_SIDE, oh, ow); return VPX_ERR_UNSUPPORTED; }
-    const double items_d = (double)B * n_frames * oh * ((ow + 3) / 4);
-    if (items_d / FR_THREADS + 1.0 > 2147483647.0) { set_error("%s: %d samples of %d %dx%d frames exceed one launch", who, B, n_frames, oh, ow); return VPX_ERR_UNSUPPORTED; }
-    ClipsVarArgs c;
-    c.fr = frames_args(src, out, 0, 0, Cs, B, n_frames, seq_step, oh, ow, oh, ow, C_out, lo, hi);   // (frame and box sizes come per sample)
-    c.geom = clip_geom; c.table = table; c.n_clips = n_clips; c.total = total_elems;
-    const unsigned blocks = (unsigned)((c.fr.items + FR_THREADS - 1) / FR_THREADS);
-    if (dtype == VPX_FRAMES_U8) VPX_LAUNCH(clips_var_kernel<unsigned char>, dim3(blocks), dim3(FR_THREADS), 0, (hipStream_t)stream, c);
-    else if (dtype == VPX_FRAMES_U16) VPX_LAUNCH(clips_var_kernel<unsigned short>, dim3(blocks), dim3(FR_THREADS), 0, (hipStream_t)stream, c);
-    else VPX_LAUNCH(clips_var_kernel<float>, dim3(blocks), dim3(FR_THREADS), 0, (hipStream_t)stream, c);
-    VPX_CHECK_HIP(vpx_hip_last_error());
-    return VPX_OK;
+    FR_TRY(check_frames_launch(who, B, n_frames, oh, ow));
+    const VarClipSource s{clip_geom, table, n_clips, total_elems};   // frame and box sizes come per sample, and with them the choice to resize (not the launch's `false`)
+    return gather_frames(src, dtype, Cs, s, B, n_frames, seq_step, false, oh, ow, C_out, lo, hi, out, stream);
 }
 
 int vpx_actions_diff_gather(const void* src, int dtype, long long total_frames, int A, const long long* clip_first, long long n_clips, const int* table,
                             int B, int n_frames, int seq_step, float* out, void* stream) {
     const char* who = "vpx_actions_diff_gather";
     if (!src || !clip_first || !table || !out) { set_error("%s: NULL tensor argument", who); return VPX_ERR_ARG; }
-    if (dtype != VPX_ACTIONS_F32 && dtype != VPX_ACTIONS_F64) { set_error("%s: unknown element type %d (float32 and float64 are stored)", who, dtype); return VPX_ERR_ARG; }
+    FR_TRY(check_action_dtype(who, dtype));
     if (total_frames < 1 || n_clips < 1 || A < 1) { set_error("%s: every source size must be >= 1 (got frames=%lld clips=%lld A=%d)", who, total_frames, n_clips, A); return VPX_ERR_ARG; }
-    if (B < 1 || n_frames < 1 || seq_step < 1) { set_error("%s: B, n_frames and seq_step must be >= 1 (got %d, %d, %d)", who, B, n_frames, seq_step); return VPX_ERR_ARG; }
+    FR_TRY(check_counts(who, B, n_frames, seq_step));
     if (n_frames < 2) { set_error("%s: a difference needs two frames (n_frames = %d)", who, n_frames); return VPX_ERR_ARG; }
-    if (n_clips > total_frames) { set_error("%s: %lld clips in %lld stored frames (a clip holds at least one)", who, n_clips, total_frames); return VPX_ERR_ARG; }
-    if ((long long)(n_frames - 1) * seq_step >= total_frames) { set_error("%s: frame %d at step %d lies past the %lld stored frames", who, n_frames - 1, seq_step, total_frames); return VPX_ERR_ARG; }
-    const double items_d = (double)B * (n_frames - 1) * A;
-    if (items_d / FR_THREADS + 1.0 > 2147483647.0) { set_error("%s: %d samples of %d rows of %d exceed one launch", who, B, n_frames - 1, A); return VPX_ERR_UNSUPPORTED; }
+    FR_TRY(check_clips_in_frames(who, n_clips, total_frames, n_frames, seq_step));
+    FR_TRY(check_rows_launch(who, B, n_frames - 1, A));
     ActionsDiffArgs a;
     a.src = src; a.clip_first = clip_first; a.table = table; a.out = out;
     a.n_clips = n_clips; a.total = total_frames; a.A = A; a.F = n_frames; a.step = seq_step;
     a.items = (long long)B * (n_frames - 1) * A;
-    const unsigned blocks = (unsigned)((a.items + FR_THREADS - 1) / FR_THREADS);
-    if (dtype == VPX_ACTIONS_F32) VPX_LAUNCH(actions_diff_kernel<float>, dim3(blocks), dim3(FR_THREADS), 0, (hipStream_t)stream, a);
-    else VPX_LAUNCH(actions_diff_kernel<double>, dim3(blocks), dim3(FR_THREADS), 0, (hipStream_t)stream, a);
+    const dim3 grid(fr_blocks(a.items)), block(FR_THREADS);
+    if (dtype == VPX_ACTIONS_F32) VPX_LAUNCH(actions_diff_kernel<float>, grid, block, 0, (hipStream_t)stream, a);
+    else VPX_LAUNCH(actions_diff_kernel<double>, grid, block, 0, (hipStream_t)stream, a);
     VPX_CHECK_HIP(vpx_hip_last_error());
     return VPX_OK;
 }
@@ -503,19 +519,17 @@ int vpx_frames_postprocess(const float* x, long long N, int C, int h, int w, dou
     const char* who = "vpx_frames_postprocess";
     if (!x || !out) { set_error("%s: NULL tensor argument", who); return VPX_ERR_ARG; }
     if (N < 1 || C < 1 || h < 1 || w < 1) { set_error("%s: every size must be >= 1 (got N=%lld C=%d h=%d w=%d)", who, N, C, h, w); return VPX_ERR_ARG; }
-    if (hi == lo) { set_error("%s: empty value range [%g, %g]", who, lo, hi); return VPX_ERR_ARG; }
+    FR_TRY(check_value_range(who, lo, hi));
     if (h > FR_MAX_SIDE || w > FR_MAX_SIDE) { set_error("%s: a side beyond %d (%dx%d)", who, FR_MAX_SIDE, h, w); return VPX_ERR_UNSUPPORTED; }
     const int Q = (w + 3) / 4;
-    const double items_d = (double)N * h * Q;
-    if (items_d / FR_THREADS + 1.0 > 2147483647.0) { set_error("%s: %lld images of %dx%d exceed one launch", who, N, h, w); return VPX_ERR_UNSUPPORTED; }
+    if (!fits_one_launch((double)N * h * Q)) { set_error("%s: %lld images of %dx%d exceed one launch", who, N, h, w); return VPX_ERR_UNSUPPORTED; }
     PostArgs a;
     a.x = x; a.out = out; a.C = C; a.h = h; a.w = w; a.Q = Q;
     a.items = N * h * Q;
     a.vec = (w % 4 == 0 && C <= 4 && ((uintptr_t)out & 3) == 0 && ((uintptr_t)x & 15) == 0) ? 1 : 0;
     a.scale = (float)(hi - lo);
     a.lo = (float)lo;
-    const unsigned blocks = (unsigned)((a.items + FR_THREADS - 1) / FR_THREADS);
-    VPX_LAUNCH(frames_postprocess_kernel, dim3(blocks), dim3(FR_THREADS), 0, (hipStream_t)stream, a);
+    VPX_LAUNCH(frames_postprocess_kernel, dim3(fr_blocks(a.items)), dim3(FR_THREADS), 0, (hipStream_t)stream, a);
     VPX_CHECK_HIP(vpx_hip_last_error());
     return VPX_OK;
 }
@@ -524,19 +538,18 @@ int vpx_actions_gather(const void* src, int dtype, long long N, int Tp, int A, c
                        float* out, void* stream) {
     const char* who = "vpx_actions_gather";
     if (!src || !table || !out) { set_error("%s: NULL tensor argument", who); return VPX_ERR_ARG; }
-    if (dtype != VPX_ACTIONS_F32 && dtype != VPX_ACTIONS_F64) { set_error("%s: unknown element type %d (float32 and float64 are stored)", who, dtype); return VPX_ERR_ARG; }
+    FR_TRY(check_action_dtype(who, dtype));
     if (N < 1 || Tp < 1 || A < 1) { set_error("%s: every source size must be >= 1 (got N=%lld T'=%d A=%d)", who, N, Tp, A); return VPX_ERR_ARG; }
-    if (B < 1 || n_frames < 1 || seq_step < 1) { set_error("%s: B, n_frames and seq_step must be >= 1 (got %d, %d, %d)", who, B, n_frames, seq_step); return VPX_ERR_ARG; }
+    FR_TRY(check_counts(who, B, n_frames, seq_step));
     if ((long long)(n_frames - 1) * seq_step + 1 > Tp) { set_error("%s: frame %d at step %d lies past the %d stored frames", who, n_frames - 1, seq_step, Tp); return VPX_ERR_ARG; }
-    const double items_d = (double)B * n_frames * A;
-    if (items_d / FR_THREADS + 1.0 > 2147483647.0) { set_error("%s: %d samples of %d rows of %d exceed one launch", who, B, n_frames, A); return VPX_ERR_UNSUPPORTED; }
+    FR_TRY(check_rows_launch(who, B, n_frames, A));
     ActionsArgs a;
     a.src = src; a.table = table; a.out = out;
     a.N = N; a.Tp = Tp; a.A = A; a.F = n_frames; a.step = seq_step;
     a.items = (long long)B * n_frames * A;
-    const unsigned blocks = (unsigned)((a.items + FR_THREADS - 1) / FR_THREADS);
-    if (dtype == VPX_ACTIONS_F32) VPX_LAUNCH(actions_gather_kernel<float>, dim3(blocks), dim3(FR_THREADS), 0, (hipStream_t)stream, a);
-    else VPX_LAUNCH(actions_gather_kernel<double>, dim3(blocks), dim3(FR_THREADS), 0, (hipStream_t)stream, a);
+    const dim3 grid(fr_blocks(a.items)), block(FR_THREADS);
+    if (dtype == VPX_ACTIONS_F32) VPX_LAUNCH(actions_gather_kernel<float>, grid, block, 0, (hipStream_t)stream, a);
+    else VPX_LAUNCH(actions_gather_kernel<double>, grid, block, 0, (hipStream_t)stream, a);
     VPX_CHECK_HIP(vpx_hip_last_error());
     return VPX_OK;
 }

@@ -5,7 +5,7 @@ Identical hyper-parameter names/defaults, module tree and state_dict keys
 (`encoder.stage{n}.conv{n}_leaky_1.*`, `encoder.rnn{n}.{_conv.weight,_conv.bias,Wci,Wcf,Wco}`,
 `forecaster.rnn{n}.*`, `forecaster.stage{n}.deconv*_leaky_1.*`, `forecaster.stage1.conv3_3.*`), so reference
 checkpoints load unchanged. The six recurrent blocks run as fused HIP kernels; activations stay channels-last (NHWC)
-between the glue convolutions (MIOpen) and the recurrent kernels, so no layout round trips happen inside the model."""
+between the glue convolutions (HIP kernels too) and the recurrent kernels, so no layout round trips happen inside the model."""
 from collections import OrderedDict
 
 import torch

@@ -1,6 +1,6 @@
 """torch-level operators over the C ABI (include/vpx.h). Tensors keep the reference's LOGICAL shapes
 ([B,T,C,H,W], [B,C,H,W]) but live channels-last in memory (NHWC) so that kernels get coalesced channel rows and the
-glue convolutions of the models (MIOpen, channels_last) exchange activations with them without a copy."""
+glue convolutions of the models (HIP kernels of this library too, csrc/glue_fwd_api.hip) exchange activations with them without a copy."""
 import collections
 import contextlib
 import ctypes
@@ -1364,21 +1364,113 @@ def acstlstm_step(x, h, c, m, a, params, ln=(), precision="f32", forget_bias=1.0
 FRAME_DTYPES = {torch.uint8: _lib.FRAMES_U8, torch.uint16: _lib.FRAMES_U16, torch.float32: _lib.FRAMES_F32}
 
 
+def _stored_source(who, name, t, dtypes, work):
+    """`t`, the stored data of a gather, contiguous: a GPU tensor of one of the stored element types `dtypes`."""
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise _lib.VpxError(f"{who}: {name} must be a GPU tensor; {work} by a HIP kernel, there is no CPU fallback")
+    if t.dtype not in dtypes:
+        kinds = [str(d).split(".")[-1] for d in dtypes]
+        raise ValueError(f"{who}: stored element type {t.dtype} is unknown ({', '.join(kinds[:-1])} and {kinds[-1]} are)")
+    return t.contiguous()
+
+
+def _boxed_sizes(who, frame_hw, Cs, crop_size, out_size, c_out, n_frames, seq_step):
+    """(ch, cw, oh, ow, c_out) of a launch with one crop box: crop_size defaults to the frame, out_size to the crop, c_out to Cs."""
+    ch, cw = frame_hw if crop_size is None else (int(s) for s in crop_size)
+    oh, ow = (ch, cw) if out_size is None else (int(s) for s in out_size)
+    c_out = Cs if c_out is None else int(c_out)
+    if min(ch, cw, oh, ow, n_frames, seq_step) < 1:
+        raise ValueError(f"{who}: every size must be >= 1 (crop {ch}x{cw}, output {oh}x{ow}, {n_frames} frames, step {seq_step})")
+    return ch, cw, oh, ow, c_out
+
+
+def _gather_out(who, out, shape, device):
+    """The destination of a preprocess launch: `out` if it is a contiguous float32 GPU tensor of `shape`, a new one for None."""
+    if out is None:
+        if min(shape) < 1:
+            raise ValueError(f"{who}: empty output {shape}")
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+        raise ValueError(f"{who}: out must be a contiguous float32 GPU tensor {shape}")
+    return out
+
+
+def _host_table(table, cols, name="table", shape=None, min_cols=None):
+    """An integer host table of at least one row and `cols` (or min_cols ... cols) columns, as an int64 array."""
+    import numpy as np
+    t = table.cpu().numpy() if torch.is_tensor(table) else np.asarray(table)
+    if t.ndim != 2 or not (min_cols or cols) <= t.shape[1] <= cols or t.shape[0] < 1 or not np.issubdtype(t.dtype, np.integer):
+        raise ValueError(f"{name} must be an integer table {shape or f'[B, {cols}]'} (got {t.dtype} {t.shape})")
+    return t.astype(np.int64)
+
+
+def _host_clip_first(clip_first, ends_at=None):
+    """int64 clip_first [n_clips + 1] from host integers: it starts at 0, increases strictly and (ends_at given) ends there."""
+    import numpy as np
+    first = clip_first.cpu().numpy() if torch.is_tensor(clip_first) else np.asarray(clip_first)
+    if first.ndim != 1 or first.shape[0] < 2 or not np.issubdtype(first.dtype, np.integer):
+        raise ValueError(f"clip_first must be an integer vector [n_clips + 1] (got {first.dtype} {first.shape})")
+    first = np.ascontiguousarray(first, dtype=np.int64)
+    if first[0] != 0 or np.diff(first).min() < 1 or (ends_at is not None and int(first[-1]) != ends_at):
+        raise ValueError("clip_first must start at 0 and increase strictly (every clip holds at least one frame)" if ends_at is None else
+                         f"clip_first must start at 0, increase strictly and end at the {ends_at} stored rows")
+    return first
+
+
+# the checks of a table's rows, one each (t: _host_table's array, or columns of it)
+def _check_index(index, n, what):
+    if index.min() < 0 or index.max() >= n:
+        raise ValueError(f"{what} index outside [0, {n})")
+
+
+def _check_windows(t, lengths, n_frames, seq_step):
+    """Columns 0 and 1 of a clips table: the clip index inside `lengths` (frames per clip), the window inside its clip."""
+    _check_index(t[:, 0], len(lengths), "clip")
+    if t[:, 1].min() < 0 or (t[:, 1] + (int(n_frames) - 1) * int(seq_step) >= lengths[t[:, 0]]).any():
+        raise ValueError(f"a window of {n_frames} frames at step {seq_step} leaves its clip")
+
+
+def _boxes_leave(y0, x0, h, w, H, W):
+    return bool(y0.min() < 0 or x0.min() < 0 or (y0 + h > H).any() or (x0 + w > W).any())
+
+
+def _check_flips(flips, reserved=None):
+    if flips.min() < 0 or flips.max() > 3:
+        raise ValueError("flip bits outside 0 ... 3 (bit 0 horizontal, bit 1 vertical)")
+    if reserved is not None and (reserved != 0).any():
+        raise ValueError("the last column of a clips table is reserved: zeros")
+
+
+def _int32(t):
+    import numpy as np
+    return np.ascontiguousarray(t, dtype=np.int32)
+
+
+def _on_device(who, src, whose, index, index_name, index_cols, table):
+    """True: `index` (clip_geom [n_clips, 4] or clip_first [n_clips + 1]) and `table` [B, 8] are GPU tensors of the launch's types on
+    src's GPU, which the caller has checked; False: both are host tables, to be checked here. One of each is refused."""
+    on_device = [torch.is_tensor(t) and t.is_cuda for t in (index, table)]
+    if all(on_device):
+        tail, rows, shape = ((index_cols,), 1, f"[n_clips, {index_cols}]") if index_cols else ((), 2, "[n_clips + 1]")
+        if (index.dtype != torch.int64 or index.ndim != 1 + len(tail) or tuple(index.shape[1:]) != tail or index.shape[0] < rows or not index.is_contiguous()
+                or table.dtype != torch.int32 or table.ndim != 2 or table.shape[1] != 8 or table.shape[0] < 1 or not table.is_contiguous()
+                or index.device != src.device or table.device != src.device):
+            raise ValueError(f"{who}: device tables must be contiguous int64 {shape} and int32 [B, 8] on the {whose} GPU")
+    elif any(on_device):
+        raise ValueError(f"{who}: {index_name} and table must both be host tables or both be GPU tensors")
+    return all(on_device)
+
+
 def check_frames_table(table, n_seqs, frame_hw, crop_hw):
     """The table a preprocess launch is handed, checked where it can be read (the host): int32 [B, 4] rows (sequence index, crop y0,
     crop x0, flip bits) with the index inside [0, n_seqs), the box inside the frame (there is no padding) and flip bits in 0 ... 3."""
-    import numpy as np
-    t = table.cpu().numpy() if torch.is_tensor(table) else np.asarray(table)
-    if t.ndim != 2 or t.shape[1] != 4 or t.shape[0] < 1 or not np.issubdtype(t.dtype, np.integer):
-        raise ValueError(f"table must be an integer table [B, 4] (got {t.dtype} {t.shape})")
+    t = _host_table(table, 4)
     (H, W), (ch, cw) = frame_hw, crop_hw
-    if t[:, 0].min() < 0 or t[:, 0].max() >= n_seqs:
-        raise ValueError(f"sequence index outside [0, {n_seqs})")
-    if t[:, 1].min() < 0 or t[:, 2].min() < 0 or t[:, 1].max() + ch > H or t[:, 2].max() + cw > W:
+    _check_index(t[:, 0], n_seqs, "sequence")
+    if _boxes_leave(t[:, 1], t[:, 2], ch, cw, H, W):
         raise ValueError(f"a {ch}x{cw} crop box leaves the {H}x{W} frame (there is no padding)")
-    if t[:, 3].min() < 0 or t[:, 3].max() > 3:
-        raise ValueError("flip bits outside 0 ... 3 (bit 0 horizontal, bit 1 vertical)")
-    return np.ascontiguousarray(t, dtype=np.int32)
+    _check_flips(t[:, 3])
+    return _int32(t)
 
 
 def frames_preprocess(src, table, n_frames, seq_step=1, crop_size=None, out_size=None, c_out=None, value_range=(0.0, 1.0), out=None):
@@ -1386,30 +1478,16 @@ def frames_preprocess(src, table, n_frames, seq_step=1, crop_size=None, out_size
     channels last) in ONE launch: scale, crop, bilinear resize (align_corners=False, no antialiasing), flip — see include/vpx.h.
     `table`: host rows [B, 4] = (sequence index, crop y0, crop x0, flip bits), checked here, copied to the device once. crop_size defaults
     to the frame, out_size to the crop, c_out to Cs. `out`: an optional destination of that shape (any 4-byte alignment)."""
-    if not (torch.is_tensor(src) and src.is_cuda):
-        raise _lib.VpxError("frames_preprocess: src must be a GPU tensor; frames are converted by a HIP kernel, there is no CPU fallback")
-    if src.dtype not in FRAME_DTYPES:
-        raise ValueError(f"frames_preprocess: stored element type {src.dtype} is unknown (uint8, uint16 and float32 are)")
+    src = _stored_source("frames_preprocess", "src", src, FRAME_DTYPES, "frames are converted")
     if src.ndim not in (4, 5):
         raise ValueError(f"frames_preprocess: src must be [N, T', H, W] or [N, T', H, W, C] (got {tuple(src.shape)})")
-    src = src.contiguous()
     N, Tp, H, W = (int(s) for s in src.shape[:4])
     Cs = int(src.shape[4]) if src.ndim == 5 else 1
-    ch, cw = (H, W) if crop_size is None else (int(s) for s in crop_size)
-    oh, ow = (ch, cw) if out_size is None else (int(s) for s in out_size)
-    c_out = Cs if c_out is None else int(c_out)
-    if min(ch, cw, oh, ow, n_frames, seq_step) < 1:
-        raise ValueError(f"frames_preprocess: every size must be >= 1 (crop {ch}x{cw}, output {oh}x{ow}, {n_frames} frames, step {seq_step})")
+    ch, cw, oh, ow, c_out = _boxed_sizes("frames_preprocess", (H, W), Cs, crop_size, out_size, c_out, n_frames, seq_step)
     host = check_frames_table(table, N, (H, W), (ch, cw))
     B = host.shape[0]
     lo, hi = float(value_range[0]), float(value_range[1])
-    shape = (B, int(n_frames), c_out, oh, ow)
-    if out is None:
-        if min(shape) < 1:
-            raise ValueError(f"frames_preprocess: empty output {shape}")
-        out = torch.empty(shape, dtype=torch.float32, device=src.device)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
-        raise ValueError(f"frames_preprocess: out must be a contiguous float32 GPU tensor {shape}")
+    out = _gather_out("frames_preprocess", out, (B, int(n_frames), c_out, oh, ow), src.device)
     dev_table = torch.from_numpy(host).to(src.device)
     with torch.cuda.device(src.device):
         check(_lib.lib().vpx_frames_preprocess(ptr(src), FRAME_DTYPES[src.dtype], N, Tp, H, W, Cs, ptr(dev_table), B, int(n_frames), int(seq_step),
@@ -1424,31 +1502,14 @@ def check_clips_table(table, clip_first, n_frames, seq_step, frame_hw, crop_hw):
     bits, 0) with the index inside [0, n_clips), the window inside its clip (0 <= start, start + (n_frames - 1) * seq_step < the clip's
     length), the box inside the frame (there is no padding), flip bits in 0 ... 3 and a zero last column.
     Returns (int64 clip_first, int32 table), both contiguous."""
-    import numpy as np
-    first = clip_first.cpu().numpy() if torch.is_tensor(clip_first) else np.asarray(clip_first)
-    if first.ndim != 1 or first.shape[0] < 2 or not np.issubdtype(first.dtype, np.integer):
-        raise ValueError(f"clip_first must be an integer vector [n_clips + 1] (got {first.dtype} {first.shape})")
-    first = np.ascontiguousarray(first, dtype=np.int64)
-    if first[0] != 0 or np.diff(first).min() < 1:
-        raise ValueError("clip_first must start at 0 and increase strictly (every clip holds at least one frame)")
-    t = table.cpu().numpy() if torch.is_tensor(table) else np.asarray(table)
-    if t.ndim != 2 or t.shape[1] != 6 or t.shape[0] < 1 or not np.issubdtype(t.dtype, np.integer):
-        raise ValueError(f"table must be an integer table [B, 6] (got {t.dtype} {t.shape})")
-    t = t.astype(np.int64)
-    n_clips = first.shape[0] - 1
+    first = _host_clip_first(clip_first)
+    t = _host_table(table, 6)
     (H, W), (ch, cw) = frame_hw, crop_hw
-    if t[:, 0].min() < 0 or t[:, 0].max() >= n_clips:
-        raise ValueError(f"clip index outside [0, {n_clips})")
-    length = first[t[:, 0] + 1] - first[t[:, 0]]
-    if t[:, 1].min() < 0 or (t[:, 1] + (int(n_frames) - 1) * int(seq_step) >= length).any():
-        raise ValueError(f"a window of {n_frames} frames at step {seq_step} leaves its clip")
-    if t[:, 2].min() < 0 or t[:, 3].min() < 0 or t[:, 2].max() + ch > H or t[:, 3].max() + cw > W:
+    _check_windows(t, first[1:] - first[:-1], n_frames, seq_step)
+    if _boxes_leave(t[:, 2], t[:, 3], ch, cw, H, W):
         raise ValueError(f"a {ch}x{cw} crop box leaves the {H}x{W} frame (there is no padding)")
-    if t[:, 4].min() < 0 or t[:, 4].max() > 3:
-        raise ValueError("flip bits outside 0 ... 3 (bit 0 horizontal, bit 1 vertical)")
-    if (t[:, 5] != 0).any():
-        raise ValueError("the last column of a clips table is reserved: zeros")
-    return first, np.ascontiguousarray(t, dtype=np.int32)
+    _check_flips(t[:, 4], reserved=t[:, 5])
+    return first, _int32(t)
 
 
 def clips_preprocess(src, clip_first, table, n_frames, seq_step=1, crop_size=None, out_size=None, c_out=None, value_range=(0.0, 1.0), out=None):
@@ -1458,33 +1519,19 @@ def clips_preprocess(src, clip_first, table, n_frames, seq_step=1, crop_size=Non
     out[b, t] comes from frame clip_first[clip] + start + t * seq_step, through the pixel arithmetic of frames_preprocess (the same device
     function: scale, crop, bilinear resize, flips, gray repeat — see include/vpx.h). Both host arguments are checked here
     (check_clips_table) and copied to the device once. The defaults are those of frames_preprocess."""
-    if not (torch.is_tensor(src) and src.is_cuda):
-        raise _lib.VpxError("clips_preprocess: src must be a GPU tensor; frames are converted by a HIP kernel, there is no CPU fallback")
-    if src.dtype not in FRAME_DTYPES:
-        raise ValueError(f"clips_preprocess: stored element type {src.dtype} is unknown (uint8, uint16 and float32 are)")
+    src = _stored_source("clips_preprocess", "src", src, FRAME_DTYPES, "frames are converted")
     if src.ndim not in (3, 4):
         raise ValueError(f"clips_preprocess: src must be [frames, H, W] or [frames, H, W, C] (got {tuple(src.shape)})")
-    src = src.contiguous()
     total, H, W = (int(s) for s in src.shape[:3])
     Cs = int(src.shape[3]) if src.ndim == 4 else 1
-    ch, cw = (H, W) if crop_size is None else (int(s) for s in crop_size)
-    oh, ow = (ch, cw) if out_size is None else (int(s) for s in out_size)
-    c_out = Cs if c_out is None else int(c_out)
     n_frames, seq_step = int(n_frames), int(seq_step)
-    if min(ch, cw, oh, ow, n_frames, seq_step) < 1:
-        raise ValueError(f"clips_preprocess: every size must be >= 1 (crop {ch}x{cw}, output {oh}x{ow}, {n_frames} frames, step {seq_step})")
+    ch, cw, oh, ow, c_out = _boxed_sizes("clips_preprocess", (H, W), Cs, crop_size, out_size, c_out, n_frames, seq_step)
     first, host = check_clips_table(table, clip_first, n_frames, seq_step, (H, W), (ch, cw))
     if int(first[-1]) != total:
         raise ValueError(f"clips_preprocess: clip_first ends at {int(first[-1])} but src holds {total} frames")
     B = host.shape[0]
     lo, hi = float(value_range[0]), float(value_range[1])
-    shape = (B, n_frames, c_out, oh, ow)
-    if out is None:
-        if min(shape) < 1:
-            raise ValueError(f"clips_preprocess: empty output {shape}")
-        out = torch.empty(shape, dtype=torch.float32, device=src.device)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
-        raise ValueError(f"clips_preprocess: out must be a contiguous float32 GPU tensor {shape}")
+    out = _gather_out("clips_preprocess", out, (B, n_frames, c_out, oh, ow), src.device)
     dev_first = torch.from_numpy(first).to(src.device)
     dev_table = torch.from_numpy(host).to(src.device)
     with torch.cuda.device(src.device):
@@ -1501,13 +1548,9 @@ def actions_gather(raw_actions, table, n_frames, seq_step=1):
     out[b, t] = float32(raw_actions[table[b, 0], t * seq_step]) — see include/vpx.h. `table`: the host rows [B, 4] a preprocess launch
     takes, or a GPU int32 tensor [B, 4] whose sequence indices the caller has checked (a dataset hands over the table of its frames
     launch); only column 0 is read. float64 is rounded to nearest even, as numpy's astype(float32) does."""
-    if not (torch.is_tensor(raw_actions) and raw_actions.is_cuda):
-        raise _lib.VpxError("actions_gather: raw_actions must be a GPU tensor; the rows are gathered by a HIP kernel, there is no CPU fallback")
-    if raw_actions.dtype not in ACTION_DTYPES:
-        raise ValueError(f"actions_gather: stored element type {raw_actions.dtype} is unknown (float32 and float64 are)")
-    if raw_actions.ndim != 3 or min(raw_actions.shape) < 1:
-        raise ValueError(f"actions_gather: raw_actions must be [N, T', A], nothing empty (got {tuple(raw_actions.shape)})")
-    src = raw_actions.contiguous()
+    src = _stored_source("actions_gather", "raw_actions", raw_actions, ACTION_DTYPES, "the rows are gathered")
+    if src.ndim != 3 or min(src.shape) < 1:
+        raise ValueError(f"actions_gather: raw_actions must be [N, T', A], nothing empty (got {tuple(src.shape)})")
     N, Tp, A = (int(s) for s in src.shape)
     n_frames, seq_step = int(n_frames), int(seq_step)
     if min(n_frames, seq_step) < 1:
@@ -1519,13 +1562,9 @@ def actions_gather(raw_actions, table, n_frames, seq_step=1):
             raise ValueError(f"actions_gather: a device table must be a contiguous int32 [B, 4] on the actions' GPU (got {table.dtype} {tuple(table.shape)})")
         dev_table = table
     else:
-        import numpy as np
-        t = table.numpy() if torch.is_tensor(table) else np.asarray(table)
-        if t.ndim != 2 or t.shape[1] != 4 or t.shape[0] < 1 or not np.issubdtype(t.dtype, np.integer):
-            raise ValueError(f"table must be an integer table [B, 4] (got {t.dtype} {t.shape})")
-        if t[:, 0].min() < 0 or t[:, 0].max() >= N:
-            raise ValueError(f"sequence index outside [0, {N})")
-        dev_table = torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32)).to(src.device)
+        t = _host_table(table, 4)
+        _check_index(t[:, 0], N, "sequence")
+        dev_table = torch.from_numpy(_int32(t)).to(src.device)
     B = int(dev_table.shape[0])
     out = torch.empty((B, n_frames, A), dtype=torch.float32, device=src.device)
     with torch.cuda.device(src.device):
@@ -1542,31 +1581,17 @@ def check_clips_var_table(table, clip_geom, total_elems, channels, n_frames, seq
     its clip, a box of at least one pixel inside the clip's own H_i x W_i frame (there is no padding), flip bits in 0 ... 3 and a zero
     last column. Returns (int64 clip_geom, int32 table), both contiguous."""
     import numpy as np
-    geom = clip_geom.cpu().numpy() if torch.is_tensor(clip_geom) else np.asarray(clip_geom)
-    if geom.ndim != 2 or geom.shape[1] != 4 or geom.shape[0] < 1 or not np.issubdtype(geom.dtype, np.integer):
-        raise ValueError(f"clip_geom must be an integer table [n_clips, 4] (got {geom.dtype} {geom.shape})")
-    geom = np.ascontiguousarray(geom, dtype=np.int64)
+    geom = np.ascontiguousarray(_host_table(clip_geom, 4, "clip_geom", "[n_clips, 4]"))
     if geom[:, 0].min() < 0 or geom[:, 1:].min() < 1 or geom[:, 2:].max() > 32768:
         raise ValueError("clip_geom: an offset below 0, a frame count or a side below 1, or a side beyond 32768")
     if (geom[:, 0] + geom[:, 1] * geom[:, 2] * geom[:, 3] * int(channels) > int(total_elems)).any():
         raise ValueError(f"a clip leaves the {int(total_elems)} stored elements")
-    t = table.cpu().numpy() if torch.is_tensor(table) else np.asarray(table)
-    if t.ndim != 2 or t.shape[1] != 8 or t.shape[0] < 1 or not np.issubdtype(t.dtype, np.integer):
-        raise ValueError(f"table must be an integer table [B, 8] (got {t.dtype} {t.shape})")
-    t = t.astype(np.int64)
-    n_clips = geom.shape[0]
-    if t[:, 0].min() < 0 or t[:, 0].max() >= n_clips:
-        raise ValueError(f"clip index outside [0, {n_clips})")
-    count, H, W = (geom[t[:, 0], k] for k in (1, 2, 3))
-    if t[:, 1].min() < 0 or (t[:, 1] + (int(n_frames) - 1) * int(seq_step) >= count).any():
-        raise ValueError(f"a window of {n_frames} frames at step {seq_step} leaves its clip")
-    if t[:, 2:6].min() < 0 or t[:, 4:6].min() < 1 or (t[:, 2] + t[:, 4] > H).any() or (t[:, 3] + t[:, 5] > W).any():
+    t = _host_table(table, 8)
+    _check_windows(t, geom[:, 1], n_frames, seq_step)
+    if t[:, 4:6].min() < 1 or _boxes_leave(t[:, 2], t[:, 3], t[:, 4], t[:, 5], geom[t[:, 0], 2], geom[t[:, 0], 3]):
         raise ValueError("a crop box is empty or leaves its clip's frame (there is no padding)")
-    if t[:, 6].min() < 0 or t[:, 6].max() > 3:
-        raise ValueError("flip bits outside 0 ... 3 (bit 0 horizontal, bit 1 vertical)")
-    if (t[:, 7] != 0).any():
-        raise ValueError("the last column of a clips table is reserved: zeros")
-    return geom, np.ascontiguousarray(t, dtype=np.int32)
+    _check_flips(t[:, 6], reserved=t[:, 7])
+    return geom, _int32(t)
 
 
 def clips_preprocess_var(src, clip_geom, table, n_frames, seq_step=1, out_size=None, channels=1, c_out=None, value_range=(0.0, 1.0), out=None):
@@ -1578,11 +1603,7 @@ def clips_preprocess_var(src, clip_geom, table, n_frames, seq_step=1, out_size=N
     (bilinear, align_corners=False, no antialiasing); flips after the resize; c_out = 3 repeats one stored channel. Host tables are
     checked here (check_clips_var_table) and copied to the device once. Both may also be GPU tensors (int64 [n_clips, 4], int32 [B, 8])
     that the caller has checked: the launch reads nothing outside `src` for any row, and a row that was not valid yields zeros."""
-    if not (torch.is_tensor(src) and src.is_cuda):
-        raise _lib.VpxError("clips_preprocess_var: src must be a GPU tensor; frames are converted by a HIP kernel, there is no CPU fallback")
-    if src.dtype not in FRAME_DTYPES:
-        raise ValueError(f"clips_preprocess_var: stored element type {src.dtype} is unknown (uint8, uint16 and float32 are)")
-    src = src.contiguous()
+    src = _stored_source("clips_preprocess_var", "src", src, FRAME_DTYPES, "frames are converted")
     total, Cs = int(src.numel()), int(channels)
     n_frames, seq_step = int(n_frames), int(seq_step)
     if out_size is None:
@@ -1591,27 +1612,14 @@ def clips_preprocess_var(src, clip_geom, table, n_frames, seq_step=1, out_size=N
     c_out = Cs if c_out is None else int(c_out)
     if min(oh, ow, n_frames, seq_step, Cs, total) < 1:
         raise ValueError(f"clips_preprocess_var: every size must be >= 1 (output {oh}x{ow}, {n_frames} frames, step {seq_step}, {Cs} channels, {total} elements)")
-    on_device = [torch.is_tensor(t) and t.is_cuda for t in (clip_geom, table)]
-    if all(on_device):
-        if (clip_geom.dtype != torch.int64 or clip_geom.ndim != 2 or clip_geom.shape[1] != 4 or clip_geom.shape[0] < 1 or not clip_geom.is_contiguous()
-                or table.dtype != torch.int32 or table.ndim != 2 or table.shape[1] != 8 or table.shape[0] < 1 or not table.is_contiguous()
-                or clip_geom.device != src.device or table.device != src.device):
-            raise ValueError("clips_preprocess_var: device tables must be contiguous int64 [n_clips, 4] and int32 [B, 8] on the frames' GPU")
+    if _on_device("clips_preprocess_var", src, "frames'", clip_geom, "clip_geom", 4, table):
         dev_geom, dev_table = clip_geom, table
-    elif any(on_device):
-        raise ValueError("clips_preprocess_var: clip_geom and table must both be host tables or both be GPU tensors")
     else:
         geom, host = check_clips_var_table(table, clip_geom, total, Cs, n_frames, seq_step)
         dev_geom, dev_table = torch.from_numpy(geom).to(src.device), torch.from_numpy(host).to(src.device)
     B, n_clips = int(dev_table.shape[0]), int(dev_geom.shape[0])
     lo, hi = float(value_range[0]), float(value_range[1])
-    shape = (B, n_frames, c_out, oh, ow)
-    if out is None:
-        if min(shape) < 1:
-            raise ValueError(f"clips_preprocess_var: empty output {shape}")
-        out = torch.empty(shape, dtype=torch.float32, device=src.device)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
-        raise ValueError(f"clips_preprocess_var: out must be a contiguous float32 GPU tensor {shape}")
+    out = _gather_out("clips_preprocess_var", out, (B, n_frames, c_out, oh, ow), src.device)
     with torch.cuda.device(src.device):
         check(_lib.lib().vpx_clips_preprocess_var(ptr(src), FRAME_DTYPES[src.dtype], total, Cs, ptr(dev_geom), n_clips, ptr(dev_table), B, n_frames,
                                                   seq_step, oh, ow, c_out, lo, hi, ptr(out), stream()), "vpx_clips_preprocess_var")
@@ -1624,42 +1632,20 @@ def actions_diff_gather(positions, clip_first, table, n_frames, seq_step=1):
     the subtraction in the stored precision — see include/vpx.h. `clip_first`: host integers [n_clips + 1]; `table`: host rows [B, 8] of a
     mixed-shape clips launch (or any integer [B, >= 2] rows: only the clip index and the start frame are read), checked here; or both as
     GPU tensors (int64 [n_clips + 1], int32 [B, 8]) that the caller has checked."""
-    import numpy as np
-    if not (torch.is_tensor(positions) and positions.is_cuda):
-        raise _lib.VpxError("actions_diff_gather: positions must be a GPU tensor; the rows are gathered by a HIP kernel, there is no CPU fallback")
-    if positions.dtype not in ACTION_DTYPES:
-        raise ValueError(f"actions_diff_gather: stored element type {positions.dtype} is unknown (float32 and float64 are)")
-    if positions.ndim != 2 or min(positions.shape) < 1:
-        raise ValueError(f"actions_diff_gather: positions must be [frames, A], nothing empty (got {tuple(positions.shape)})")
-    src = positions.contiguous()
+    src = _stored_source("actions_diff_gather", "positions", positions, ACTION_DTYPES, "the rows are gathered")
+    if src.ndim != 2 or min(src.shape) < 1:
+        raise ValueError(f"actions_diff_gather: positions must be [frames, A], nothing empty (got {tuple(src.shape)})")
     total, A = (int(s) for s in src.shape)
     n_frames, seq_step = int(n_frames), int(seq_step)
     if n_frames < 2 or seq_step < 1:
         raise ValueError(f"actions_diff_gather: n_frames must be >= 2 (a difference needs two frames) and seq_step >= 1 (got {n_frames}, {seq_step})")
-    on_device = [torch.is_tensor(t) and t.is_cuda for t in (clip_first, table)]
-    if all(on_device):
-        if (clip_first.dtype != torch.int64 or clip_first.ndim != 1 or clip_first.shape[0] < 2 or not clip_first.is_contiguous()
-                or table.dtype != torch.int32 or table.ndim != 2 or table.shape[1] != 8 or table.shape[0] < 1 or not table.is_contiguous()
-                or clip_first.device != src.device or table.device != src.device):
-            raise ValueError("actions_diff_gather: device tables must be contiguous int64 [n_clips + 1] and int32 [B, 8] on the positions' GPU")
+    if _on_device("actions_diff_gather", src, "positions'", clip_first, "clip_first", None, table):
         dev_first, dev_table = clip_first, table
-    elif any(on_device):
-        raise ValueError("actions_diff_gather: clip_first and table must both be host tables or both be GPU tensors")
     else:
-        first = clip_first.numpy() if torch.is_tensor(clip_first) else np.asarray(clip_first)
-        if first.ndim != 1 or first.shape[0] < 2 or not np.issubdtype(first.dtype, np.integer):
-            raise ValueError(f"clip_first must be an integer vector [n_clips + 1] (got {first.dtype} {first.shape})")
-        first = np.ascontiguousarray(first, dtype=np.int64)
-        if first[0] != 0 or np.diff(first).min() < 1 or int(first[-1]) != total:
-            raise ValueError(f"clip_first must start at 0, increase strictly and end at the {total} stored rows")
-        t = table.numpy() if torch.is_tensor(table) else np.asarray(table)
-        if t.ndim != 2 or t.shape[1] < 2 or t.shape[1] > 8 or t.shape[0] < 1 or not np.issubdtype(t.dtype, np.integer):
-            raise ValueError(f"table must be an integer table [B, 8] (got {t.dtype} {t.shape})")
-        t = t.astype(np.int64)
-        if t[:, 0].min() < 0 or t[:, 0].max() >= first.shape[0] - 1:
-            raise ValueError(f"clip index outside [0, {first.shape[0] - 1})")
-        if t[:, 1].min() < 0 or (t[:, 1] + (n_frames - 1) * seq_step >= first[t[:, 0] + 1] - first[t[:, 0]]).any():
-            raise ValueError(f"a window of {n_frames} frames at step {seq_step} leaves its clip")
+        import numpy as np
+        first = _host_clip_first(clip_first, ends_at=total)
+        t = _host_table(table, 8, min_cols=2)
+        _check_windows(t, first[1:] - first[:-1], n_frames, seq_step)
         host = np.zeros((t.shape[0], 8), dtype=np.int32)
         host[:, :2] = t[:, :2]
         dev_first, dev_table = torch.from_numpy(first).to(src.device), torch.from_numpy(host).to(src.device)
