@@ -25,7 +25,8 @@
  * vpx_adam_step_clipped            clip_grad_norm_ / clip_grad_value_ + Adam step, optional skip of a non-finite step   (new)
  * vpx_pixel_measures_fwd / _bwd    MSE, L1, SmoothL1, PSNR per frame         vp_suite/measure/image_wise.py:19-71
  * vpx_ssim_fwd / _bwd              SSIM per frame (piqa defaults)           vp_suite/measure/image_wise.py:99-117
- * vpx_groupnorm_fwd / _bwd         GroupNorm + LeakyReLU (DCGAN layers)     vp_suite/model_blocks/conv.py, model_blocks/phydnet.py
+ * vpx_lpips_fwd (+ stem, maxpool, head)  LPIPS per frame on AlexNet weights the caller brings  vp_suite/measure/image_wise.py (LPIPS)
+ * vpx_groupnorm_fwd / _bwd         GroupNorm + LeakyReLU (DCGAN layers)    vp_suite/model_blocks/conv.py, model_blocks/phydnet.py
  * vpx_phycell_correct_fwd / _bwd   PhyCell_Cell prediction-correction       vp_suite/model_blocks/phydnet.py (PhyCell_Cell.forward)
  * vpx_moment_loss_fwd / _bwd       K2M + moment regularisation loss         vp_suite/models/phydnet.py (PhyDNet.forward)
  * vpx_sigmoid_head_fwd / _bwd      sigmoid output + stack of frames         vp_suite/models/phydnet.py (encoder_fwd, forward)
@@ -365,6 +366,38 @@ int vpx_ssim_fwd(const float* pred, const float* target, long long n_frames, int
                  void* workspace, size_t workspace_bytes, void* stream);
 int vpx_ssim_bwd(const float* pred, const float* target, const float* dssim, long long n_frames, int C, int H, int W,
                  int layout, float* dpred, void* stream);
+/* LPIPS on an AlexNet trunk (https://arxiv.org/abs/1801.03924; image_wise.py's LPIPS through piqa), forward only, fp32, no atomics
+ * (bit-reproducible in either determinism mode). The library ships no weights: the caller hands them in. Feature maps are
+ * channels-last, [N, h, w, C], the layout of the library's convolutions.
+ * vpx_lpips_fwd: pred / target: n_frames dense [3,H,W] frames in the model's range. Each is mapped by clamp((v+1)/2, 0, 1), then
+ *   (u - mean_c) / std_c with ImageNet's mean (0.485, 0.456, 0.406) and std (0.229, 0.224, 0.225); both go through the trunk as ONE
+ *   batch of 2 n_frames images: conv 3->64 k11 s4 p2 + ReLU (tap 1), max-pool 3/2, conv 64->192 k5 p2 + ReLU (tap 2), max-pool 3/2,
+ *   conv 192->384 k3 p1 + ReLU (tap 3), conv 384->256 k3 p1 + ReLU (tap 4), conv 256->256 k3 p1 + ReLU (tap 5); the pools in floor mode
+ *   without padding. table [n_frames] (doubles, OVERWRITTEN) = sum over the taps of the mean over a tap's pixels of
+ *   sum_c lin[c] (fx[c] / (|fx| + 1e-10) - fy[c] / (|fy| + 1e-10))^2, |f| the channel norm at the pixel.
+ *   params: 15 device pointers, conv1..conv5 weights [Co,Ci,k,k], conv1..conv5 biases [Co], lin1..lin5 [C] (the array itself on the host).
+ *   VPX_ERR_ARG: a NULL pointer, n_frames < 1, C != 3, H or W < 31 (below that the third tap has no pixel). VPX_ERR_UNSUPPORTED: more
+ *   work than one launch holds. VPX_ERR_WORKSPACE: workspace NULL or smaller than vpx_lpips_workspace_bytes(n_frames, H, W) (0 for
+ *   sizes the call refuses), which holds the feature maps of the 2 n_frames images (two slots, used in turn), the weight packs of
+ *   the four stride-1 convolutions, the transposed stem weights and the heads' partial sums.
+ * The pieces, as the trunk runs them:
+ * vpx_lpips_stem_fwd: y [n0 + n1, Ho, Wo, 64] = ReLU(conv(norm(x), w [64,3,11,11], stride 4, pad 2) + bias), Ho = (H + 4 - 11) / 4 + 1, over
+ *   the n0 images [3,H,W] at x0 followed by the n1 at x1 (n1 = 0: x1 may be NULL); `norm` as above, fused into the operand load; the
+ *   padding ring is zero in NORMALISED space, not the normalised value of 0. H, W >= 7. Workspace: vpx_lpips_stem_workspace_bytes().
+ * vpx_lpips_maxpool_fwd: y [N, (H-3)/2+1, (W-3)/2+1, C] = 3x3 stride-2 max-pool of x [N,H,W,C], floor mode, no padding; H, W >= 3.
+ * vpx_lpips_head_fwd: table[i] += mean over the HW pixels of the expression above for fx, fy [n, HW, C] and w [C]; C <= 512
+ *   (VPX_ERR_UNSUPPORTED beyond). Every feature element is read once, the arithmetic on them is double; an all-zero feature vector
+ *   contributes through the 1e-10, never as NaN. Workspace: vpx_lpips_head_workspace_bytes(n, HW). */
+size_t vpx_lpips_workspace_bytes(long long n_frames, int H, int W);
+int vpx_lpips_fwd(const float* pred, const float* target, long long n_frames, int C, int H, int W, const float* const* params,
+                  double* table, void* workspace, size_t workspace_bytes, void* stream);
+size_t vpx_lpips_stem_workspace_bytes(void);
+int vpx_lpips_stem_fwd(const float* x0, const float* x1, long long n0, long long n1, int H, int W, const float* w, const float* bias,
+                       float* y, void* workspace, size_t workspace_bytes, void* stream);
+int vpx_lpips_maxpool_fwd(const float* x, float* y, long long N, int H, int W, int C, void* stream);
+size_t vpx_lpips_head_workspace_bytes(long long n, long long HW);
+int vpx_lpips_head_fwd(const float* fx, const float* fy, const float* w, long long n, long long HW, int C, double* table,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- plain stride-1 "same" convolution, NHWC, optional bias; y [N,H,W,Co] = conv(x [N,H,W,Ci], w [Co,Ci,kh,kw]) --- */
 size_t vpx_conv2d_workspace_bytes(int Ci, int Co, int kh, int kw);

@@ -168,6 +168,13 @@ SIGNATURES = {
     "vpx_ssim_workspace_bytes": (sz, [ll, ci, ci]),
     "vpx_ssim_fwd": (ci, [vp, vp, ll] + [ci] * 4 + [vp] + _ws),
     "vpx_ssim_bwd": (ci, [vp, vp, vp, ll] + [ci] * 4 + [vp, vp]),
+    "vpx_lpips_workspace_bytes": (sz, [ll, ci, ci]),
+    "vpx_lpips_fwd": (ci, [vp, vp, ll] + [ci] * 3 + [vp, vp] + _ws),                                  # pred target n C H W | params table
+    "vpx_lpips_stem_workspace_bytes": (sz, []),
+    "vpx_lpips_stem_fwd": (ci, [vp, vp, ll, ll, ci, ci, vp, vp, vp] + _ws),                           # x0 x1 n0 n1 H W | w bias y
+    "vpx_lpips_maxpool_fwd": (ci, [vp, vp, ll] + [ci] * 3 + [vp]),
+    "vpx_lpips_head_workspace_bytes": (sz, [ll, ll]),
+    "vpx_lpips_head_fwd": (ci, [vp, vp, vp, ll, ll, ci, vp] + _ws),                                   # fx fy w n HW C | table
     # plain stride-1 "same" convolution
     "vpx_conv2d_workspace_bytes": (sz, [ci] * 4),
     "vpx_conv2d_nhwc_fwd": (ci, [vp] * 4 + [ci] * 8 + _ws),

@@ -8,7 +8,11 @@ by prefix means and transfers the results once. Host (CPU) tensors take the plai
 The MSE with the reference's reduction (sum over c,h,w -> mean over t -> mean over b; base_measure.py:57, image_wise.py:19-27) keeps
 its own kernel, which writes d/dpred in the same pass: `mse_measure`, and a provider configured with "mse" alone.
 
-LPIPS and FVD need pretrained networks this build does not ship: their registry entries raise NotImplementedError."""
+LPIPS runs on AlexNet weights the USER registers (register_lpips_weights: a dict, an .npz or a .pth file; nothing is ever downloaded):
+a third per-frame table, from csrc/lpips.hip on the GPU (forward only). Until weights are registered its registry entry raises
+NotImplementedError, as FVD's always does: this build ships no pretrained network."""
+import os
+
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -78,6 +82,135 @@ def frame_ssim(pred, target, name="Structural Similarity (SSIM)"):
     return _ssim_host(pred, target)
 
 
+# ---- LPIPS: weights a user brings, the host expression, the per-frame table ---------------------------------------------------------
+# Restated from the LPIPS paper (https://arxiv.org/abs/1801.03924) and the public descriptions of the `lpips` / `piqa` packages, neither
+# of which this project depends on: no upstream fixture pins these values (as with SSIM).
+LPIPS_NAME = "Learned Perceptual Image Patch Similarity (LPIPS)"
+LPIPS_MEAN, LPIPS_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)                  # ImageNet normalisation
+LPIPS_CONV_SHAPES = ((64, 3, 11, 11), (192, 64, 5, 5), (384, 192, 3, 3), (256, 384, 3, 3), (256, 256, 3, 3))   # torchvision's AlexNet.features
+LPIPS_MIN_SIDE = 31                                                                   # below it the third tap has no pixel
+_TORCHVISION_FEATURES = (0, 3, 6, 8, 10)                                              # features.{i}: the five convolutions
+_lpips_weights = None   # canonical {key: host tensor} once registered
+_lpips_on_device = {}   # (device, dtype) -> the same on a device
+
+
+def _lpips_canonical_key(key):
+    """The canonical name of a key of one of the accepted layouts, or None."""
+    parts = key.split(".")
+    if len(parts) == 2 and parts[1] in ("weight", "bias") and parts[0][:4] == "conv" and parts[0][4:] in tuple("12345"):
+        return key
+    if len(parts) == 2 and parts[1] == "weight" and parts[0][:3] == "lin" and parts[0][3:] in tuple("12345"):
+        return key
+    if len(parts) == 3 and parts[0] == "features" and parts[2] in ("weight", "bias") and parts[1].isdigit() and int(parts[1]) in _TORCHVISION_FEATURES:
+        return f"conv{_TORCHVISION_FEATURES.index(int(parts[1])) + 1}.{parts[2]}"
+    if len(parts) == 4 and parts[1:] == ["model", "1", "weight"] and parts[0][:3] == "lin" and parts[0][3:] in tuple("01234"):   # the `lpips` package
+        return f"lin{int(parts[0][3:]) + 1}.weight"
+    return None
+
+
+def _lpips_load(source):
+    if isinstance(source, dict):
+        return source
+    path = os.fspath(source)
+    if path.endswith(".npz"):
+        import numpy as np
+        with np.load(path) as z:
+            return {k: z[k] for k in z.files}
+    if path.endswith(".pth"):
+        return torch.load(path, map_location="cpu", weights_only=True)
+    raise ValueError(f"LPIPS weights: {path!r} is neither a dict, an .npz nor a .pth file")
+
+
+def register_lpips_weights(source, linear_source=None):
+    """Registers the AlexNet trunk and the five linear layers LPIPS runs on; from then on "lpips" works wherever a measure key is accepted.
+    source (and, where the linear layers live in a file of their own, as upstream keeps them, linear_source): a dict, an .npz file or a
+    .pth file (read with torch.load(weights_only=True)). Accepted keys: conv{1..5}.weight / .bias and lin{1..5}.weight ([C] or [1,C,1,1]);
+    torchvision's features.{0,3,6,8,10}.weight / .bias; the `lpips` package's lin{0..4}.model.1.weight. Other keys are ignored. Every shape
+    is checked before anything is stored (ValueError naming the key and both shapes). Nothing is ever downloaded."""
+    global _lpips_weights
+    found = {}
+    for src in (source, linear_source):
+        if src is None:
+            continue
+        for key, value in _lpips_load(src).items():
+            name = _lpips_canonical_key(key) if isinstance(key, str) else None
+            if name is None:
+                continue
+            t = torch.as_tensor(value).detach().cpu()
+            i = int(name[name.index(".") - 1]) - 1
+            want = LPIPS_CONV_SHAPES[i] if name.startswith("conv") and name.endswith("weight") else (LPIPS_CONV_SHAPES[i][0],)
+            if name.startswith("lin") and tuple(t.shape) == (1, want[0], 1, 1):
+                t = t.reshape(want)
+            if tuple(t.shape) != want:
+                raise ValueError(f"LPIPS weights: {key!r} has shape {tuple(t.shape)}, expected {want}" + (f" or {(1, want[0], 1, 1)}" if name.startswith("lin") else ""))
+            if not t.is_floating_point():
+                raise ValueError(f"LPIPS weights: {key!r} has dtype {t.dtype}, expected a floating-point tensor")
+            found[name] = t.clone().contiguous()
+    from .ops import LPIPS_KEYS
+    missing = [k for k in LPIPS_KEYS if k not in found]
+    if missing:
+        raise ValueError(f"LPIPS weights: no tensor for {missing} (accepted key layouts: see register_lpips_weights)")
+    _lpips_weights = {k: found[k] for k in LPIPS_KEYS}
+    _lpips_on_device.clear()
+
+
+def clear_lpips_weights():
+    """Forgets the registered weights: "lpips" raises NotImplementedError again."""
+    global _lpips_weights
+    _lpips_weights = None
+    _lpips_on_device.clear()
+
+
+def lpips_weights(device="cpu", dtype=torch.float32):
+    """The registered weights {canonical key: tensor} on `device` in `dtype` (moved once per device and dtype)."""
+    if _lpips_weights is None:
+        raise NotImplementedError(f"{LPIPS_NAME} needs pretrained weights that this build does not ship (register_lpips_weights)")
+    slot = (str(torch.device(device)), dtype)
+    if slot not in _lpips_on_device:
+        _lpips_on_device[slot] = {k: v.to(device=device, dtype=dtype) for k, v in _lpips_weights.items()}
+    return _lpips_on_device[slot]
+
+
+def _lpips_host(pred, target, weights):
+    """[B, T] on host tensors: the definition in plain torch, in the inputs' dtype."""
+    b, t = pred.shape[:2]
+    mean, std = pred.new_tensor(LPIPS_MEAN).view(1, 3, 1, 1), pred.new_tensor(LPIPS_STD).view(1, 3, 1, 1)
+    f = torch.cat([pred.reshape(-1, *pred.shape[2:]), target.reshape(-1, *target.shape[2:])])   # one batch of 2 B T images
+    f = (((f + 1) / 2).clamp(min=0.0, max=1.0) - mean) / std                                 # base_measure.py:71-74, then ImageNet
+    out = 0
+    for i in range(5):
+        k = LPIPS_CONV_SHAPES[i][2]
+        if i in (1, 2):
+            f = F.max_pool2d(f, 3, 2)
+        f = F.relu(F.conv2d(f, weights[f"conv{i + 1}.weight"], weights[f"conv{i + 1}.bias"], stride=4 if i == 0 else 1, padding=k // 2 if i else 2))
+        n = f / (f.square().sum(dim=1, keepdim=True).sqrt() + 1e-10)
+        d = (n[:b * t] - n[b * t:]).square() * weights[f"lin{i + 1}.weight"].view(1, -1, 1, 1)
+        out = out + d.sum(dim=1).mean(dim=(1, 2))
+    return out.view(b, t)
+
+
+def frame_lpips(pred, target, name=LPIPS_NAME):
+    """[B, T]: LPIPS of every frame on the registered weights (3-channel frames, channels at dim 2, at least 31x31). On the GPU forward
+    only: the backward is not implemented there (NotImplementedError for a prediction that requires grad under grad mode)."""
+    _check_5d(name, pred, target)
+    if pred.shape[2] != 3:
+        raise ValueError(f"{name} needs 3-channel images with the channels at dim 2")
+    if pred.shape[3] < LPIPS_MIN_SIDE or pred.shape[4] < LPIPS_MIN_SIDE:
+        raise ValueError(f"{name} needs images of at least {LPIPS_MIN_SIDE}x{LPIPS_MIN_SIDE} pixels (below that the third tap has no pixel)")
+    if pred.is_cuda:
+        from . import ops
+        return ops.lpips_frames(pred, target, lpips_weights(pred.device)).float()   # (the kernel's table is float64)
+    return _lpips_host(pred, target, lpips_weights("cpu", pred.dtype))
+
+
+def _frame_table(kind, pred, target, name):
+    if kind == "ssim":
+        return frame_ssim(pred, target, name)
+    if kind == "lpips":
+        return frame_lpips(pred, target, name)
+    return frame_sums(pred, target)
+
+
 # ---- measures --------------------------------------------------------------------------------------------------------------------
 class VPMeasure(nn.Module):
     """base_measure.py: a measure returns lower-is-better values; to_display() converts to the measure's usual representation.
@@ -86,7 +219,7 @@ class VPMeasure(nn.Module):
     REFERENCE: str = None
     BIGGER_IS_BETTER = False
     OPT_VALUE = 0.
-    TABLE = "sums"   # the per-frame table the measure is derived from: "sums" (frame_sums) or "ssim" (frame_ssim)
+    TABLE = "sums"   # the per-frame table the measure is derived from: "sums" (frame_sums), "ssim" (frame_ssim) or "lpips" (frame_lpips)
     ROW = 0          # row of the sums table
 
     def __init__(self, device):
@@ -99,7 +232,7 @@ class VPMeasure(nn.Module):
 
     def forward(self, pred, target):
         _check_5d(self.NAME, pred, target)
-        table = frame_ssim(pred, target, self.NAME) if self.TABLE == "ssim" else frame_sums(pred, target)
+        table = _frame_table(self.TABLE, pred, target, self.NAME)
         return self.frame_values(table, pred[0, 0].numel()).mean(dim=1).mean(dim=0)
 
     @classmethod
@@ -160,9 +293,19 @@ class _Unavailable(VPMeasure):
         raise NotImplementedError(f"{self.NAME} needs pretrained weights that this build does not ship")
 
 
-class LPIPS(_Unavailable):
-    NAME = "Learned Perceptual Image Patch Similarity (LPIPS)"
+class LPIPS(VPMeasure):
+    """image_wise.py's LPIPS: the mean over all frames of the AlexNet LPIPS value, on weights the user registered (register_lpips_weights);
+    without them the constructor raises NotImplementedError, as it always did."""
+    NAME = LPIPS_NAME
     REFERENCE = "https://arxiv.org/abs/1801.03924"
+    TABLE = "lpips"
+
+    def __init__(self, device):
+        lpips_weights()   # NotImplementedError until weights are registered
+        super().__init__(device)
+
+    def frame_values(self, table, frame_elems):
+        return table
 
 
 class FrechetVideoDistance(_Unavailable):
@@ -183,14 +326,15 @@ def _frame_values(measures, pred, target):
     out = {}
     for key, m in measures.items():
         if m.TABLE not in tables:
-            tables[m.TABLE] = frame_ssim(pred, target, m.NAME) if m.TABLE == "ssim" else frame_sums(pred, target)
+            tables[m.TABLE] = _frame_table(m.TABLE, pred, target, m.NAME)
         out[key] = m.frame_values(tables[m.TABLE], pred[0, 0].numel())
     return out
 
 
 class PredictionLossProvider:
     """config: {"device": ..., "losses_and_scales": {key: scale}} over any mix of "mse", "l1", "smooth_l1", "psnr" and "ssim"
-    (loss_provider.py). All pixel-wise terms together cost one sums pass and one gradient pass, SSIM one of each."""
+    (loss_provider.py). All pixel-wise terms together cost one sums pass and one gradient pass, SSIM one of each. "lpips" joins them once
+    weights are registered: on the GPU as a value only (its backward is not implemented: a prediction that requires grad raises)."""
 
     def __init__(self, config: dict):
         self.device = config["device"]

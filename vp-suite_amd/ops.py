@@ -892,6 +892,96 @@ def ssim_frames(pred, target):
     return _SSIMFramesFn.apply(pred, target)
 
 
+# ---- LPIPS on an AlexNet trunk (csrc/lpips.hip): forward only; feature maps are channels-last [N, h, w, C] ---------------------------
+LPIPS_MIN_SIDE = 31   # below it the third tap has no pixel
+LPIPS_CONV_SHAPES = ((64, 3, 11, 11), (192, 64, 5, 5), (384, 192, 3, 3), (256, 384, 3, 3), (256, 256, 3, 3))   # torchvision's AlexNet.features
+LPIPS_KEYS = tuple(f"conv{i}.weight" for i in range(1, 6)) + tuple(f"conv{i}.bias" for i in range(1, 6)) + tuple(f"lin{i}.weight" for i in range(1, 6))
+LPIPS_SHAPES = dict(zip(LPIPS_KEYS, LPIPS_CONV_SHAPES + tuple((s[0],) for s in LPIPS_CONV_SHAPES) * 2))
+
+
+def _lpips_operand(t, what, name, shape=None):
+    require_gpu(t, what)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t.contiguous()
+
+
+def lpips_stem(x, w, bias, x1=None):
+    """[N, Ho, Wo, 64] channels-last: ReLU(conv(norm(x), w, stride 4, padding 2) + bias) of x [N,3,H,W] in the model's range (and of the
+    images of x1 behind them), norm = ImageNet normalisation of clamp((x+1)/2, 0, 1); the padding ring is zero in normalised space."""
+    what = "lpips_stem"
+    if x.ndim != 4 or x.shape[1] != 3 or (x1 is not None and x1.shape[1:] != x.shape[1:]):
+        raise ValueError(f"{what}: expected [N,3,H,W] images of one size")
+    x = _lpips_operand(x, what, "x")
+    x1 = None if x1 is None else _lpips_operand(x1, what, "x1")
+    w, bias = _lpips_operand(w, what, "w", LPIPS_CONV_SHAPES[0]), _lpips_operand(bias, what, "bias", (64,))
+    n0, n1, (H, W) = x.shape[0], 0 if x1 is None else x1.shape[0], x.shape[2:]
+    L = _lib.lib()
+    ws, ws_bytes = workspace(x.device, L.vpx_lpips_stem_workspace_bytes)
+    y = torch.empty(n0 + n1, max((H + 4 - 11) // 4 + 1, 0), max((W + 4 - 11) // 4 + 1, 0), 64, device=x.device)
+    check(L.vpx_lpips_stem_fwd(ptr(x), ptr(x1), n0, n1, H, W, ptr(w), ptr(bias), ptr(y), ptr(ws), ws_bytes, stream()), "vpx_lpips_stem_fwd")
+    return y
+
+
+def lpips_maxpool(x):
+    """[N, (h-3)//2+1, (w-3)//2+1, C]: 3x3 stride-2 max-pool (floor mode, no padding) of a channels-last map [N, h, w, C]."""
+    if x.ndim != 4:
+        raise ValueError("lpips_maxpool: expected a channels-last map [N, h, w, C]")
+    x = _lpips_operand(x, "lpips_maxpool", "x")
+    N, h, w, C = x.shape
+    y = torch.empty(N, max((h - 3) // 2 + 1, 0), max((w - 3) // 2 + 1, 0), C, device=x.device)
+    check(_lib.lib().vpx_lpips_maxpool_fwd(ptr(x), ptr(y), N, h, w, C, stream()), "vpx_lpips_maxpool_fwd")
+    return y
+
+
+def lpips_head(fx, fy, w, table=None):
+    """table [N] (float64; zeros when not given) += mean over the pixels of sum_c w[c] (fx / (|fx| + 1e-10) - fy / (|fy| + 1e-10))^2 for
+    channels-last feature maps fx, fy [N, h, w, C], |f| the channel norm at a pixel."""
+    what = "lpips_head"
+    if fx.ndim != 4 or fx.shape != fy.shape:
+        raise ValueError(f"{what}: expected two channels-last maps [N, h, w, C] of one shape")
+    fx, fy = _lpips_operand(fx, what, "fx"), _lpips_operand(fy, what, "fy")
+    N, h, wd, C = fx.shape
+    w = _lpips_operand(w, what, "w", (C,))
+    if table is None:
+        table = torch.zeros(N, device=fx.device, dtype=torch.float64)
+    elif table.dtype != torch.float64 or tuple(table.shape) != (N,) or not table.is_contiguous() or table.device != fx.device:
+        raise ValueError(f"{what}: table must be a contiguous float64 tensor of shape ({N},) on the maps' device")
+    L = _lib.lib()
+    ws, ws_bytes = workspace(fx.device, L.vpx_lpips_head_workspace_bytes, N, h * wd)
+    check(L.vpx_lpips_head_fwd(ptr(fx), ptr(fy), ptr(w), N, h * wd, C, ptr(table), ptr(ws), ws_bytes, stream()), "vpx_lpips_head_fwd")
+    return table
+
+
+def lpips_frames(pred, target, weights):
+    """[B, T] float64: LPIPS of each predicted frame against its target frame on an AlexNet trunk. pred, target: [B, T, 3, H, W] in the
+    model's range, H, W >= 31. weights: {key: device tensor} over LPIPS_KEYS (measure.register_lpips_weights builds it). Prediction and
+    target run through the trunk as one batch. FORWARD ONLY: the backward is not implemented, a prediction that requires grad under grad
+    mode raises NotImplementedError (use torch.no_grad() or detach)."""
+    what = "lpips_frames"
+    if pred.ndim != 5 or target.ndim != 5:
+        raise ValueError(f"{what} expects 5-D inputs!")
+    if pred.shape != target.shape:
+        raise ValueError("Output images and target images are of different shape!")
+    B, T, C, H, W = pred.shape
+    if C != 3:
+        raise ValueError(f"{what} needs 3-channel images with the channels at dim 2")
+    if H < LPIPS_MIN_SIDE or W < LPIPS_MIN_SIDE:
+        raise ValueError(f"{what} needs images of at least {LPIPS_MIN_SIDE}x{LPIPS_MIN_SIDE} pixels (below that the third tap has no pixel)")
+    if needs_grad(pred, target):
+        raise NotImplementedError(f"{what}: the backward of LPIPS is not implemented in this build (forward only): evaluate it under "
+                                  f"torch.no_grad() or on detached tensors")
+    p, tg = _lpips_operand(pred, what, "pred"), _lpips_operand(target, what, "target")
+    params = [_lpips_operand(weights[k], what, k, LPIPS_SHAPES[k]) for k in LPIPS_KEYS]
+    if any(t.device != p.device for t in params + [tg]):
+        raise ValueError(f"{what}: prediction, target and weights must live on one device")
+    L = _lib.lib()
+    ws, ws_bytes = workspace(p.device, L.vpx_lpips_workspace_bytes, B * T, H, W)
+    table = torch.empty(B, T, device=p.device, dtype=torch.float64)
+    check(L.vpx_lpips_fwd(ptr(p), ptr(tg), B * T, C, H, W, ptr_array(params), ptr(table), ptr(ws), ws_bytes, stream()), "vpx_lpips_fwd")
+    return table
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
     """One torch.optim.Adam update of flat fp32 buckets, in place (vpsuite.py:353; torch/optim/adam.py semantics)."""
     require_gpu(param, "adam_step")

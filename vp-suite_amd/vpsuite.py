@@ -17,7 +17,9 @@ DEFAULT_RUN_CONFIG is the reference's DefaultRunConfig (defaults.py:37-64) key f
     ground truth / prediction GIF per datapoint and model, a comparison PNG per datapoint, vis_info.txt. Each output is one canvas
     composed by one HIP launch (ops.vis_compose, csrc/vis.hip). GIFs carry no matplotlib titles, one-channel frames are shown as grey
     RGB, and there is no mp4 (visualization.py lists the departures).
-  * metrics = ["mse", "psnr", "ssim"]: "lpips" needs pretrained weights this build does not ship.
+  * metrics = ["mse", "psnr", "ssim"]: "lpips" needs pretrained weights this build does not ship, so it is not a default. After
+    measure.register_lpips_weights(...) (AlexNet weights the user brings; nothing is downloaded) the reference's own list,
+    metrics=["mse", "lpips", "psnr", "ssim"], runs in train() and test(); on one-channel data it fails with the measure's ValueError.
   * One added key, test_batch_size = 1: test() may evaluate several datapoints per launch. Per-horizon means stay means over
     DATAPOINTS (batch means weighted by batch size), so a ragged last batch changes nothing.
   * One added key, flat_adam = False: True trains with train.FlatAdam (one HIP kernel over flat buckets) instead of torch.optim.Adam.
