@@ -199,6 +199,28 @@ int vpx_convlstm_seq_bwd(const vpx_convlstm_desc* d, const float* x, const float
                          const float* dcT, float* dx, float* dh0, float* dc0, float* dW, float* db, float* dWci,
                          float* dWcf, float* dWco, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The plan of a sequence call: which kernels vpx_convlstm_seq_fwd / _bwd with this descriptor take under the current
+ * vpx_set_deterministic / vpx_set_option state, filled by the functions that decide it for the calls themselves. No launch, no
+ * allocation. x_present: 0 = the call's `x` is NULL; want_dx / want_dW: the backward is asked for dx / dW (non-NULL pointers).
+ *   forward   route (VPX_CL_ROUTE_*); qform: the 16x16x32 MFMA form on CELL2 / C3; c3nt: C3's column tiles per N tile (4 | 2, else 0);
+ *             mw: FUSED's workgroup form (1: four waves, 2: eight waves; 0 off FUSED); ksplit: K ranges of the step's convolution on
+ *             KSPLIT (else 0); hh_split: K ranges of HOIST's recurrent convolution, the only split of that route (else 0); hoist_convq: the hoisted projection of HOIST / CELL3 on the
+ *             schedule-driven kernel; cell2x: CELL2's q form on the eight-wave half tile
+ *   backward  (all zero without VPX_FLAG_SAVE_FOR_BWD) dgrad: the data gradient on 0 the first-generation kernel, 1 conv2;
+ *             dgrad_qform: conv2's MFMA form; d_mw: the first-generation data gradient's workgroup form (0 on conv2); dgrad_cols: the
+ *             columns of [x | h] it writes (Cin + Ch, or Ch without dx); wgrad (0 without want_dW): 0 launch_wgrad, 1 wgrad2 on the
+ *             operands of the reserve, 2 wgrad2 on operands the backward converts itself; n_slices: K slices of the weight-gradient
+ *             kernel that takes the launch; dG_f32: the gate backward writes dG in fp32; gate_slices: its batch slices (peephole
+ *             gradients are reduced over them when > 1)
+ * Returns what vpx_convlstm_workspace_bytes' checks refuse with (VPX_ERR_ARG, VPX_ERR_UNSUPPORTED), VPX_ERR_ARG for a NULL `out`. */
+enum { VPX_CL_ROUTE_FUSED = 0, VPX_CL_ROUTE_KSPLIT = 1, VPX_CL_ROUTE_HOIST = 2, VPX_CL_ROUTE_CELL3 = 3, VPX_CL_ROUTE_CELL2 = 4,
+       VPX_CL_ROUTE_C3 = 5 };
+typedef struct vpx_convlstm_plan_info {
+    int32_t route, qform, c3nt, mw, ksplit, hh_split, hoist_convq, cell2x;
+    int32_t dgrad, dgrad_qform, d_mw, dgrad_cols, wgrad, n_slices, dG_f32, gate_slices;
+} vpx_convlstm_plan_info;
+int vpx_convlstm_plan(const vpx_convlstm_desc* d, int x_present, int want_dx, int want_dW, vpx_convlstm_plan_info* out);
+
 /* ---- ST-LSTM cell step (PredRNN-V2) -------------------------------------------------------------------------- */
 size_t vpx_stlstm_workspace_bytes(const vpx_stlstm_desc* d);
 size_t vpx_stlstm_reserve_bytes(const vpx_stlstm_desc* d);

@@ -104,6 +104,15 @@ class STLSTMPlanInfo(ctypes.Structure):
 ST_ROUTE_LN, ST_ROUTE_GEN1, ST_ROUTE_C5, ST_ROUTE_C5K = 0, 1, 2, 3
 
 
+class ConvLSTMPlanInfo(ctypes.Structure):
+    """vpx_convlstm_plan_info: the kernels a sequence call with a descriptor takes (include/vpx.h), every field an int32."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("route", "qform", "c3nt", "mw", "ksplit", "hh_split", "hoist_convq", "cell2x", "dgrad", "dgrad_qform",
+                                              "d_mw", "dgrad_cols", "wgrad", "n_slices", "dG_f32", "gate_slices")]
+
+
+CL_ROUTE_FUSED, CL_ROUTE_KSPLIT, CL_ROUTE_HOIST, CL_ROUTE_CELL3, CL_ROUTE_CELL2, CL_ROUTE_C3 = range(6)
+
+
 class DensePlanInfo(ctypes.Structure):
     """vpx_dense_plan_info: the launch a dense layer of (M, N, K) takes (include/vpx.h), every field an int32."""
     _fields_ = [(n, ctypes.c_int32) for n in ("split", "chunks", "chunk_len", "form", "tile_m", "tile_n", "m_tiles", "n_tiles")]
@@ -138,6 +147,7 @@ SIGNATURES = {
     "vpx_convlstm_reserve_bytes": (sz, [_clstm]),
     "vpx_convlstm_seq_fwd": (ci, [_clstm] + [vp] * 8 + [vp] * 3 + _rs_ws),                     # x h0 c0 W bias Wci Wcf Wco | out hT cT
     "vpx_convlstm_seq_bwd": (ci, [_clstm] + [vp] * 8 + [vp, sz] + [vp] * 3 + [vp] * 8 + _ws),  # x h0 c0 W Wci Wcf Wco out | reserve | dout dhT dcT | 8 gradients
+    "vpx_convlstm_plan": (ci, [_clstm, ci, ci, ci, vp]),
     # ST-LSTM cell step
     "vpx_stlstm_workspace_bytes": (sz, [_stlstm]),
     "vpx_stlstm_reserve_bytes": (sz, [_stlstm]),
@@ -320,6 +330,13 @@ def exp_bits(text: str) -> int:
     for t in text.split("|"):
         bits |= Exp[t.strip()] if t.strip() in Exp.__members__ else int(t, 0)
     return int(bits)
+
+
+def convlstm_plan(d: ConvLSTMDesc, x_present=True, want_dx=True, want_dW=True) -> dict:
+    """vpx_convlstm_plan as a dict (field -> int) under the current options; raises as check() does where the query refuses."""
+    info = ConvLSTMPlanInfo()
+    check(lib().vpx_convlstm_plan(ctypes.byref(d), int(bool(x_present)), int(bool(want_dx)), int(bool(want_dW)), ctypes.byref(info)), "vpx_convlstm_plan")
+    return {n: getattr(info, n) for n, _ in ConvLSTMPlanInfo._fields_}
 
 
 def check(rc: int, what: str):

@@ -963,7 +963,7 @@ static hipError_t launch_cell2_t(const Cell2Plan& plan, const Epi& epi, hipStrea
 }
 
 hipError_t launch_cell2(const Cell2Plan& plan, const ConvLSTMStepArgs& ea, void* h_sp, long long h_sp_bstride, hipStream_t s) {
-    if (plan.qform && cell2x_selected()) {   // the eight-wave half tile (cell2x.hip): four waves per SIMD
+    if (cell2_step_on_x(plan.qform)) {   // the eight-wave half tile (cell2x.hip): four waves per SIMD
         Cell2Plan p = plan;
         p.tiles_y = (p.H + 15) / 16;
         p.grid_m = p.B * p.tiles_x * p.tiles_y;

@@ -49,6 +49,45 @@ size_t vpx::convlstm_bwd_workspace_bytes(const vpx_convlstm_desc* d, const ConvL
     return m.off;
 }
 
+// ---- the form of a call, decided once from the layout, the present operands and the requested gradients ----
+// c2d: the data gradient on conv2 (dG in the split operand format) instead of the first-generation kernel; wsp: the forward ran on
+// another kernel, the weight gradient on wgrad2 all the same, on operands this call converts; wgrad: 0 launch_wgrad, 1 wgrad2 on the
+// reserve's operands, 2 wgrad2 behind wsp (0 without dW); need_dG_f32: a consumer still reads dG in fp32
+struct BwdChoice {
+    bool c2d, wsp, need_dx, need_dG_f32;
+    int qform, col_start, n_out, wgrad, wgrad_slices, gb_slices;
+};
+static BwdChoice convlstm_bwd_choice(const vpx_convlstm_desc* d, const ConvLSTMLayout& L, bool x_present, bool want_dx, bool want_dW) {
+    BwdChoice r{};
+    const int N4 = 4 * d->Ch;
+    r.gb_slices = gate_bwd_slices(d->H * d->W, d->Ch, d->B, false);
+    r.c2d = L.v2;
+    r.wsp = wgrad2_wsp(d, L) && want_dW;
+    // data-gradient weights: contraction over the 4Ch gate rows, outputs over [x | h] (or only h) columns
+    r.need_dx = want_dx && x_present;
+    r.col_start = r.need_dx ? 0 : d->Cin;
+    r.n_out = r.need_dx ? d->Cin + d->Ch : d->Ch;
+    r.qform = g_mfma_shape == 1 ? 1 : 0;   // conv2's epilogue handles ragged tiles in both forms
+    // the weight gradient: wgrad2 where its operands are in the split format (the reserve's after a cell2 forward, or this call's own)
+    WgradArgs probe{};
+    probe.T = d->T; probe.B = d->B; probe.H = d->H; probe.W = d->W; probe.kh = d->kh; probe.kw = d->kw; probe.N4 = N4; probe.Cin = d->Cin; probe.Ch = d->Ch;
+    probe.prec = d->precision;
+    probe.a_split = ((L.v2 && d->layout == VPX_LAYOUT_NHWC) || r.wsp) ? 1 : 0;
+    probe.g_sp = (r.c2d || r.wsp) ? reinterpret_cast<const char*>(&L) : nullptr;   // (any non-NULL address: the probe asks whether dG comes split, no more)
+    probe.n_ctiles = wgrad_make_ctiles(probe.ct, WG_MAX_CTILES, x_present ? d->Cin : 0, d->Ch, d->Cin);
+    const bool w2 = want_dW && L.n_slices2 > 0 && wgrad2_applicable(probe);
+    r.wgrad = !w2 ? 0 : (r.wsp ? 2 : 1);
+    r.wgrad_slices = !want_dW ? 0 : (w2 ? wgrad2_used_slices(probe, L.n_slices2) : L.n_slices);
+    // fp32 dG is only written for consumers that still read it (first-generation data- / weight-gradient kernels)
+    r.need_dG_f32 = !r.c2d || (want_dW && r.wgrad != 1);
+    return r;
+}
+void vpx::convlstm_bwd_plan(const vpx_convlstm_desc* d, const ConvLSTMLayout& L, bool x_present, bool want_dx, bool want_dW, vpx_convlstm_plan_info* out) {
+    const BwdChoice r = convlstm_bwd_choice(d, L, x_present, want_dx, want_dW);
+    out->dgrad = r.c2d ? 1 : 0; out->dgrad_qform = r.c2d ? r.qform : 0; out->d_mw = r.c2d ? 0 : L.d_mw; out->dgrad_cols = r.n_out;
+    out->wgrad = r.wgrad; out->n_slices = r.wgrad_slices; out->dG_f32 = r.need_dG_f32 ? 1 : 0; out->gate_slices = r.gb_slices;
+}
+
 extern "C" int vpx_convlstm_seq_bwd(const vpx_convlstm_desc* d, const float* x, const float* h0, const float* c0,
                                     const float* W, const float* Wci, const float* Wcf, const float* Wco,
                                     const float* out, const void* reserve, size_t reserve_bytes, const float* dout,
@@ -80,10 +119,10 @@ extern "C" int vpx_convlstm_seq_bwd(const vpx_convlstm_desc* d, const float* x, 
     VPX_CHECK_CARVE(ws, "vpx_convlstm_seq_bwd");
     // peephole gradients: a sum over the batch. With several batch slices every slice accumulates (over the time steps, single
     // owner per element) into its own partial tensor; launch_peep_reduce adds them in a fixed order after the loop
-    const int gb_slices = gate_bwd_slices((int)HW, Ch, B, false);
+    const BwdChoice ch = convlstm_bwd_choice(d, L, x != nullptr, dx != nullptr, dW != nullptr);
+    const int gb_slices = ch.gb_slices;
     const int gb_blocks = gate_bwd_blocks((int)HW, Ch) * gb_slices;  // partial rows per step
-    const bool c2d = L.v2;
-    const bool wsp = wgrad2_wsp(d, L) && dW != nullptr;   // forward on another kernel, weight gradient on wgrad2 all the same
+    const bool c2d = ch.c2d, wsp = ch.wsp;
 
     // ---- layout adaptation ----
     const float *xn = x, *h0n = h0, *c0n = c0, *outn = out, *doutn = dout, *dhTn = dhT, *dcTn = dcT;
@@ -124,11 +163,9 @@ extern "C" int vpx_convlstm_seq_bwd(const vpx_convlstm_desc* d, const float* x, 
     }
 
     // ---- data-gradient weights: contraction over the 4Ch gate rows, outputs over [x | h] (or only h) columns ----
-    const bool need_dx = dxn && xn;
-    const int col_start = need_dx ? 0 : Cin;
-    const int n_out = need_dx ? Ct : Ch;
+    const bool need_dx = ch.need_dx;
+    const int col_start = ch.col_start, n_out = ch.n_out, qform = ch.qform;
     const int d_tiles = plain_tiles(n_out);
-    const int qform = g_mfma_shape == 1 ? 1 : 0;   // conv2's epilogue handles ragged tiles in both forms
     if (c2d) {
         Conv2Pack pk{W, (long long)L.taps, (long long)Ct * L.taps, n_out, col_start, conv2_tiles(n_out), conv2_gpt(n_out),
                      qform ? cell2_qchunks(N4 / 16) : 3 * (N4 / 16), 1, qform, 0};
@@ -143,15 +180,7 @@ extern "C" int vpx_convlstm_seq_bwd(const vpx_convlstm_desc* d, const float* x, 
         VPX_CHECK_HIP(launch_pack_weights(pd, s.wpk, stream));
     }
 
-    // fp32 dG is only written for consumers that still read it (first-generation data- / weight-gradient kernels)
-    bool wgrad_takes_sp = false;
-    if (c2d && d->layout == VPX_LAYOUT_NHWC) {
-        WgradArgs probe{};
-        probe.T = T; probe.B = B; probe.H = H; probe.W = Wd; probe.kh = d->kh; probe.kw = d->kw; probe.N4 = N4; probe.Cin = Cin; probe.Ch = Ch;
-        probe.prec = d->precision; probe.a_split = 1; probe.g_sp = s.dG_sp_all;
-        wgrad_takes_sp = wgrad2_applicable(probe);
-    }
-    const bool need_dG_f32 = !c2d || (dW && !wgrad_takes_sp);
+    const bool need_dG_f32 = ch.need_dG_f32;
     for (int t = T - 1; t >= 0; --t) {
         GateBwdArgs ga{};
         ga.B = B; ga.HW = (int)HW; ga.Ch = Ch;
@@ -238,7 +267,7 @@ extern "C" int vpx_convlstm_seq_bwd(const vpx_convlstm_desc* d, const float* x, 
         if (!xn) VPX_CHECK_HIP(vpx_memset_async(s.slabs, 0, L.slab_floats * sizeof(float), stream));
         wa.g_sp = (c2d || wsp) ? s.dG_sp_all : nullptr;
         int ns_used = L.n_slices, tail_col0 = Ct, tail_slices = L.n_slices;
-        if (L.n_slices2 > 0 && wgrad2_applicable(wa)) VPX_CHECK_HIP(launch_wgrad2(wa, L.n_slices2, &ns_used, &tail_col0, &tail_slices, stream));
+        if (ch.wgrad) VPX_CHECK_HIP(launch_wgrad2(wa, L.n_slices2, &ns_used, &tail_col0, &tail_slices, stream));
         else VPX_CHECK_HIP(launch_wgrad(wa, L.n_slices, stream));
         VPX_CHECK_HIP(launch_wgrad_reduce_tail(s.slabs, dW, ns_used, L.taps, N4, Ct, tail_col0, tail_slices, stream));
     }

@@ -518,3 +518,23 @@ extern "C" int vpx_convlstm_seq_fwd(const vpx_convlstm_desc* d, const float* x, 
     }
     return VPX_OK;
 }
+
+// The plan of a call (include/vpx.h): the layout, the route and the backward's choice as the calls compute them, nothing launched or carved
+extern "C" int vpx_convlstm_plan(const vpx_convlstm_desc* d, int x_present, int want_dx, int want_dW, vpx_convlstm_plan_info* out) {
+    int rc = check_convlstm_desc(d);
+    if (rc != VPX_OK) return rc;
+    if (!out) { set_error("vpx_convlstm_plan: out is NULL"); return VPX_ERR_ARG; }
+    ConvLSTMLayout L;
+    if ((rc = convlstm_layout(d, L)) != VPX_OK) return rc;
+    const RouteChoice r = convlstm_route(d, L, x_present != 0);
+    ConvQProblem hq;
+    *out = vpx_convlstm_plan_info{};
+    out->route = (int)r.route; out->qform = r.qform; out->c3nt = r.c3nt;
+    out->mw = r.route == Route::FUSED ? L.mw : 0;
+    out->ksplit = r.route == Route::KSPLIT ? L.split : 0;   // (HOIST launches nothing with L.split: its steps split by hh_split)
+    out->hh_split = r.route == Route::HOIST ? L.hh_split : 0;
+    out->hoist_convq = x_present && route_hoists_on_convq(d, r, hq) ? 1 : 0;   // (without x the entry point runs no projection)
+    out->cell2x = r.route == Route::CELL2 && cell2_step_on_x(r.qform) ? 1 : 0;
+    if (d->flags & VPX_FLAG_SAVE_FOR_BWD) convlstm_bwd_plan(d, L, x_present != 0, want_dx != 0, want_dW != 0, out);
+    return VPX_OK;
+}

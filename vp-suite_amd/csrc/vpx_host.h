@@ -251,6 +251,8 @@ static inline int convlstm_layout(const vpx_convlstm_desc* d, ConvLSTMLayout& L)
 // It registers nowhere, records no slot, touches no pending pack or violation text and hands out no address.
 struct CarveMeasure { size_t off = 0; float* take(size_t nfloat) { off += align256(nfloat * sizeof(float)); return nullptr; } };
 size_t convlstm_bwd_workspace_bytes(const vpx_convlstm_desc* d, const ConvLSTMLayout& L);   // vpx_convlstm_seq_bwd's own carve, measured
+// vpx_convlstm_plan's backward fields (convlstm_bwd_api.hip): the choice as a call with these operands and requested gradients makes it
+void convlstm_bwd_plan(const vpx_convlstm_desc* d, const ConvLSTMLayout& L, bool x_present, bool want_dx, bool want_dW, vpx_convlstm_plan_info* out);
 
 // The reserve a saving forward fills and the backward reads: gates [T][B,H,W,4Ch], cell states [T][B,H,W,Ch] and, where the forward runs
 // on the second-generation cell, the operands in split format for the weight gradient (x all frames, h_0, h_1 .. h_T).

@@ -224,6 +224,7 @@ hipError_t launch_cell2(const Cell2Plan& plan, const ConvLSTMStepArgs& ea, void*
 // (development state: the four-wave half tile stays the default until the A/B says otherwise)
 hipError_t launch_cell2x(const Cell2Plan& plan, const ConvLSTMStepArgs& ea, void* h_sp, long long h_sp_bstride, hipStream_t s);
 static inline bool cell2x_selected() { return exp_on(VPX_EXP_CELL2X); }
+static inline bool cell2_step_on_x(int qform) { return qform && cell2x_selected(); }   // launch_cell2's choice (and vpx_convlstm_plan's answer)
 // c16 (conv16.hip): 3x3 stride-1 'same' (transposed or not) layers with 16 output channels on split input, weights resident in registers
 bool c16_applicable(const ::vpx_conv_desc* d);
 size_t c16_wpk_bytes(const ::vpx_conv_desc* d);
@@ -485,6 +486,7 @@ static inline int wgrad2_slices(int target, int rows128, int n_ctiles, bool half
 }
 // columns >= *tail_col0 (the half-empty last column tile, if any) were written to the first *tail_slices slabs only
 hipError_t launch_wgrad2(const WgradArgs& a, int max_slices, int* used_slices, int* tail_col0, int* tail_slices, hipStream_t s);
+int wgrad2_used_slices(const WgradArgs& a, int max_slices);   // the K slices that launch takes (a.n_ctiles / a.ct set)
 hipError_t launch_wgrad_reduce_tail(const float* slabs, float* dW, int n_slices, int taps, int N4, int Ct, int tail_col0, int tail_slices,
                                     hipStream_t s);
 // wgrad2.hip, glue form: one stride residue of a stage-glue layer's weight gradient with BOTH operands in the split format (g_sp: the

@@ -437,6 +437,19 @@ bool wgrad2_applicable(const WgradArgs& a) {
 }
 
 // slices: whole rounds of 256 one-per-CU workgroups (two rounds: WGRAD2_TARGET_WGS), at most max_slices
+int wgrad2_used_slices(const WgradArgs& a, int max_slices) {
+    const int rows = (a.N4 + 127) / 128;
+    const bool half_tail = a.ct[a.n_ctiles - 1].h[1].cn == 0;
+    // Full tiles take ns slices, the half-empty tail tiles 5/8 ns: an item of a tail tile costs 0.62 of a full one (measured: the
+    // MFMA work halves, the copy and the barrier do not), so with 8/5 of the items its workgroups run as long as the others —
+    // ns * nf + 5/8 ns * nh workgroups of equal length, at most WGRAD2_TARGET_WGS.
+    int ns = wgrad2_slices(WGRAD2_TARGET_WGS, rows, a.n_ctiles, half_tail);
+    if (ns > max_slices) ns = max_slices;
+    const long long items = (long long)a.T * a.B * ((a.W + 15) / 16) * ((a.H + W2_TH - 1) / W2_TH);
+    if (ns > items) ns = (int)items;
+    if (half_tail && ns >= 8) ns &= ~7;
+    return ns < 1 ? 1 : ns;
+}
 hipError_t launch_wgrad2(const WgradArgs& a_in, int max_slices, int* used_slices, int* tail_col0, int* tail_slices, hipStream_t s) {
     static bool attr_set = false;
     if (!attr_set) {
@@ -446,22 +459,13 @@ hipError_t launch_wgrad2(const WgradArgs& a_in, int max_slices, int* used_slices
         if (e != hipSuccess) return e;
         attr_set = !g_dry_run;
     }
-    const int target = WGRAD2_TARGET_WGS;
     WgradArgs a = a_in;
     const int rows = (a.N4 + 127) / 128;
     a.grid_x = rows * a.n_ctiles;
     const bool half_tail = a.ct[a.n_ctiles - 1].h[1].cn == 0;
     a.w2_nh = half_tail ? rows : 0;
     const int nf = a.grid_x - a.w2_nh;
-    // Full tiles take ns slices, the half-empty tail tiles 5/8 ns: an item of a tail tile costs 0.62 of a full one (measured: the
-    // MFMA work halves, the copy and the barrier do not), so with 8/5 of the items its workgroups run as long as the others —
-    // ns * nf + 5/8 ns * nh workgroups of equal length, at most `target`.
-    int ns = wgrad2_slices(target, rows, a.n_ctiles, half_tail);
-    if (ns > max_slices) ns = max_slices;
-    const long long items = (long long)a.T * a.B * ((a.W + 15) / 16) * ((a.H + W2_TH - 1) / W2_TH);
-    if (ns > items) ns = (int)items;
-    if (half_tail && ns >= 8) ns &= ~7;
-    if (ns < 1) ns = 1;
+    const int ns = wgrad2_used_slices(a, max_slices);
     a.grid_slices = ns;
     a.w2_ns_half = half_tail ? (ns >= 8 ? ns / 8 * 5 : ns) : 0;
     *used_slices = ns;
