@@ -331,10 +331,10 @@ def predrnn_v2_action_forward(sd, frames, actions, pred_frames, *, patch_size, n
     return pred, decoupling_loss_scale * torch.mean(torch.stack(dec, dim=0))
 
 
-def trajgru_seq(inputs, states, seq_len, p, L, slope=0.2):
+def trajgru_seq(inputs, states, seq_len, p, L, slope=0.2, i2h_pad=1):
     """Functional restatement of TrajGRU.forward (vp_suite/model_blocks/traj_gru.py:164-214; zoneout 0): i2h over all
     frames, per step flow generation (:134-146), L bilinear warps of h (:148-162, default grid_sample alignment), 1x1 ret
-    conv and the GRU gate arithmetic (:190-203)."""
+    conv and the GRU gate arithmetic (:190-203). `i2h_pad`: padding of the input projection (k // 2 for a k x k 'same' i2h)."""
     import torch
     import torch.nn.functional as F
     nf = p["ret.weight"].shape[0] // 3
@@ -347,7 +347,7 @@ def trajgru_seq(inputs, states, seq_len, p, L, slope=0.2):
     H, W = states.shape[-2:]
     if inputs is not None:
         b, _, c, h, w = inputs.shape
-        i2h = conv("i2h", inputs[:, :seq_len].reshape(-1, c, h, w), 1).reshape(b, seq_len, 3 * nf, H, W)
+        i2h = conv("i2h", inputs[:, :seq_len].reshape(-1, c, h, w), i2h_pad).reshape(b, seq_len, 3 * nf, H, W)
         i2h = torch.split(i2h, nf, dim=2)
     else:
         i2h = None
