@@ -5,7 +5,8 @@ Bounds. Per kernel: max|got - ref| / max|ref| <= 1e-5, the project's bar for fp3
 head's identical-input and repeat results are exact). End to end: per case, 4 x the max-normalised error of the plain float32 torch
 chain against the float64 restatement at the same inputs and weights, measured on the CPU (lpips_ref.e2e_case) — 4 for an equally
 valid fp32 summation order in each of five chained layers. Every end-to-end case prints its figures and records them through parity_log;
-with VPX_LPIPS_PARITY_OUT=FILE in the environment they are also written there (how profiles/lpips_parity.json was made)."""
+with VPX_LPIPS_PARITY_OUT=FILE in the environment they are also written there (how profiles/lpips_parity.json was made). Every tap on
+its own, the trunk layers alone and the edges of the three kernels: tests/test_gpu_lpips_taps.py (its per-tap figures go into the same file)."""
 import functools
 import json
 import os
@@ -19,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 KERNEL_TOL = 1e-5
 PARITY_OUT = os.environ.get("VPX_LPIPS_PARITY_OUT")
-_PARITY = {}
+_PARITY, _PER_TAP = {}, {}
 
 
 @pytest.fixture
@@ -113,14 +114,22 @@ def test_head_vs_fp64(vpx, parity_log, N, C, h, w):
 
 
 # ---- end to end --------------------------------------------------------------------------------------------------------------------
-def _record(case, **figures):
-    _PARITY[str(case)] = figures
+def _record(case, tap=None, **figures):
+    """End to end (tap None) or one tap of a geometry case (tests/test_gpu_lpips_taps.py); the file is rewritten with everything so far."""
+    if tap is None:
+        _PARITY[str(case)] = figures
+    else:
+        _PER_TAP.setdefault(str(case), {})[f"tap {tap}"] = figures
     if not PARITY_OUT:
         return
     with open(PARITY_OUT, "w") as fh:
         json.dump({"what": "ops.lpips_frames on the GPU against the float64 restatement (tests/lpips_ref.py), max|got-ref| / max|ref| over the [B,T] table; "
                            "reference_error: the plain float32 torch chain on the CPU against the same restatement; bound = margin x reference_error",
-                   "margin": lpips_ref.E2E_MARGIN, "cases (B, T, H, W)": _PARITY}, fh, indent=1)
+                   "margin": lpips_ref.E2E_MARGIN, "cases (B, T, H, W)": _PARITY,
+                   "per_tap": {"what": "the same three figures for one tap's share of the table alone (every lin{k}.weight zeroed but the tap's), over lpips_ref.GEOMETRY_CASES; "
+                                       "bound = max(margin x reference_error, floor), a bound above the ceiling fails its case",
+                               "floor": lpips_ref.TAP_FLOOR, "ceiling": lpips_ref.TAP_CEILING, "tap map sizes (h, w)": {str(c): [list(m) for m in t] for c, t in lpips_ref.GEOMETRY_TAPS.items()},
+                               "cases (B, T, H, W)": _PER_TAP}}, fh, indent=1)
 
 
 @pytest.mark.parametrize("case", lpips_ref.E2E_CASES)

@@ -279,3 +279,138 @@ def test_entry_points_refuse_bad_arguments(L):
     bad[5] = 513
     assert L.vpx_lpips_head_fwd(*bad, ws, nb, None) == E_UNSUPPORTED and b"512" in L.vpx_last_error()
     assert L.vpx_lpips_head_fwd(*good, None, nb, None) == E_WS
+
+
+# ---- the per-tap geometry table and the edge cases of tests/test_gpu_lpips_taps.py: conditions on the inputs ------------------------------
+def test_geometry_table_reaches_the_seams():
+    assert set(lpips_ref.GEOMETRY_TAPS) == set(lpips_ref.GEOMETRY_CASES)
+    assert {(31, 31), (39, 71), (67, 38), (128, 96)} <= {c[2:] for c in lpips_ref.GEOMETRY_CASES}
+    sides = set()
+    for case in lpips_ref.GEOMETRY_CASES:
+        B, T, H, W = case
+        assert B * T <= 4 and (B * T == 2 or H * W < 128 * 96), case
+        stated = lpips_ref.GEOMETRY_TAPS[case]
+        assert stated == lpips_ref.tap_sizes(H, W), case
+        x, _ = lpips_ref.frames((1, 1, 3, H, W), seed=1)
+        assert stated == tuple(tuple(f.shape[2:]) for f in lpips_ref.taps(x[0], lpips_ref.weights())), case
+        sides |= set(stated[0])
+    assert lpips_ref.GEOMETRY_TAPS[(2, 2, 39, 71)] == ((9, 17), (4, 8), (1, 3), (1, 3), (1, 3))
+    assert lpips_ref.GEOMETRY_TAPS[(2, 2, 67, 38)] == ((16, 8), (7, 3), (3, 1), (3, 1), (3, 1))
+    assert lpips_ref.GEOMETRY_TAPS[(1, 2, 128, 96)][2:] == ((7, 5),) * 3
+    # around the stem's 8x8 tile: on the seam, one before, one past, two tiles + 1, and four tiles per side
+    assert sides >= {7, 8, 9, 16, 17} and max(sides) > 24, sides
+    assert any(h > w for (h, w), *_ in lpips_ref.GEOMETRY_TAPS.values()) and any(h < w for (h, w), *_ in lpips_ref.GEOMETRY_TAPS.values())
+
+
+@pytest.mark.parametrize("case", lpips_ref.GEOMETRY_CASES)
+def test_geometry_case_conditions(case):
+    pred, target, ref, errs, bounds = lpips_ref.geometry_case(case)
+    w = lpips_ref.weights()
+    assert len(ref) == len(errs) == len(bounds) == 5
+    total = 0
+    for l in range(1, 6):
+        table, err, bound = ref[l - 1], errs[l - 1], bounds[l - 1]
+        print(f"geometry {case} tap {l}: values {float(table.min()):.3e} .. {float(table.max()):.3e}, reference-side {err:.3e}, bound {bound:.3e}")
+        assert table.shape == case[:2] and table.dtype == torch.float64
+        assert bool((table > 0).all()), (case, l)                       # no degenerate tap, at 1x1 maps either
+        assert float(table.min()) > 1e-3 * float(table.max()), (case, l)   # every frame carries weight in the max-normalised figure
+        assert 0 < err and bound == max(lpips_ref.E2E_MARGIN * err, lpips_ref.TAP_FLOOR)
+        assert bound <= lpips_ref.TAP_CEILING, (case, l, bound)         # (a miss: next seed revision, lpips_ref.REJECTED_SEEDS)
+        # the isolating weights give exactly this tap's table in the restatement, and nothing of another tap
+        iso = lpips_ref.isolated(w, l)
+        assert all(torch.equal(iso[k], w[k]) for k in w if not k.startswith("lin") or k == f"lin{l}.weight")
+        assert all(not bool(iso[f"lin{k}.weight"].any()) for k in range(1, 6) if k != l)
+        assert torch.equal(lpips_ref.lpips_frames(pred, target, iso), table)
+        total = total + table
+    assert lpips_ref.relmax(total, lpips_ref.lpips_frames(pred, target, w)) < 1e-14
+    f32 = lpips_ref.tap_tables_f32(pred, target, w)
+    assert torch.equal(sum(f32[1:], f32[0]), lpips_ref.lpips_frames_f32(pred, target, w))
+    rev = 1 + max(lpips_ref.REJECTED_SEEDS.get(case, {-1: ""}))
+    assert all(r < rev for r in lpips_ref.REJECTED_SEEDS.get(case, {}))
+
+
+def test_split_float32_chain_keeps_the_end_to_end_figures():
+    """profiles/lpips_parity.json's reference-side errors were measured with the unsplit chain: the split one gives the same numbers."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "lpips_parity.json")) as fh:
+        rec = json.load(fh)["cases (B, T, H, W)"]
+    for case in lpips_ref.E2E_CASES:
+        assert lpips_ref.e2e_case(case)[3] == pytest.approx(rec[str(case)]["reference_error"], rel=1e-9), case
+
+
+def test_trunk_layer_cases():
+    """The 20 (layer, map) cases: the ReLU is at work, some outputs are clearly off, and none of them is a case of tests/glue_ref.py."""
+    import glue_ref
+    ours = set()
+    for layer, (Ci, Co, k, pad) in enumerate(lpips_ref.TRUNK_LAYERS):
+        assert lpips_ref.CONV_SHAPES[layer + 1] == (Co, Ci, k, k) and lpips_ref.STRIDE_PAD[layer + 1] == (1, pad)
+        for h, w in lpips_ref.TRUNK_MAPS:
+            x, wt, b, pre = lpips_ref.trunk_case(layer, h, w)
+            assert x.shape == (lpips_ref.TRUNK_N, Ci, h, w) and float(x.min()) >= 0 and pre.shape == (lpips_ref.TRUNK_N, Co, h, w)
+            scale = float(pre.clamp_min(0).max())
+            off = float((pre < -lpips_ref.TRUNK_TOL * scale).double().mean())
+            assert scale > 0 and 0.2 < off < 0.8, (layer, h, w, off)
+            ours.add((0, lpips_ref.TRUNK_N, Ci, Co, k, k, 1, pad, 0, 0, h, w))
+    assert {m for c in lpips_ref.GEOMETRY_TAPS.values() for m in c[2:]} <= set(lpips_ref.TRUNK_MAPS)
+    theirs = {tuple(c) for t in glue_ref.TABLES.values() for c in t}
+    assert not {c[2:8] for c in ours} & {c[2:8] for c in theirs}     # no (Ci, Co, kh, kw, s, p) of the trunk is in the glue tables at any map
+
+
+def test_edge_case_conditions():
+    for H, W in lpips_ref.STEM_EDGE_SIZES:
+        for kind in lpips_ref.STEM_EDGE_KINDS:
+            x, ref = lpips_ref.stem_edge_case(2, H, W, kind)
+            assert ref.shape[2:] == lpips_ref.tap_sizes(H, W)[0] and float(ref.max()) > 0
+            if kind == "noise":
+                assert float(x.min()) < -1.05 and float(x.max()) > 1.05
+                assert all(bool((x[:, :, y, xx] == v).all()) for y, xx, v in lpips_ref.STEM_PINNED)
+            elif kind == "bounds":
+                assert set(x.unique().tolist()) == {-1.0, 1.0}
+            else:
+                assert set(x.unique().tolist()) == {-1.0}
+    for C in lpips_ref.HEAD_EDGE_C:
+        for h, w in lpips_ref.HEAD_EDGE_MAPS:
+            fx, fy, lin, ref = lpips_ref.head_edge_case(C, h, w)
+            assert ref.shape == (lpips_ref.HEAD_EDGE_N,) and float(ref.max()) > 0, (C, h, w)
+            assert bool((fx.pow(2).sum(dim=1) == 0).any()) and bool((fy.pow(2).sum(dim=1) == 0).any()) or C == 1, (C, h, w)
+    assert sorted(h * w for h, w in lpips_ref.HEAD_EDGE_MAPS) == [1, 63, 64, 65, 129]
+    for scale, C, h, w in lpips_ref.HEAD_SCALED:
+        fx, fy, lin, ref = lpips_ref.head_edge_case(C, h, w, scale)
+        assert bool(torch.isfinite(fx).all()) and bool(torch.isfinite(ref).all()) and float(ref.min()) > 0
+        norms = fx.double().pow(2).sum(dim=1).sqrt()
+        if scale < 1:   # the 1e-10 of the norm dominates: the value is far below the unscaled one
+            assert float(norms.max()) < 1e-10 and float(ref.max()) < 0.1 * float(lpips_ref.head_edge_case(C, h, w)[3].max())
+        else:           # the squares leave the fp32 range
+            assert float(fx.max()) ** 2 > 3.5e38 and not bool(torch.isfinite(fx.pow(2).sum(dim=1)).all())
+            assert lpips_ref.relmax(ref, lpips_ref.head_edge_case(C, h, w)[3]) < 1e-6   # (and in float64 the value is the unscaled one)
+
+
+def test_new_shapes_dry_run(L):
+    params = (ctypes.c_void_p * 15)(*[0x200000000000 + i * (1 << 30) for i in range(15)])
+    for B, T, H, W in lpips_ref.GEOMETRY_CASES:
+        nb = L.vpx_lpips_workspace_bytes(B * T, H, W)
+        assert nb > 0
+        for base in (WS_BASE, WS_BASE_ODD):
+            _ok(L, L.vpx_lpips_fwd(_fake(1), _fake(2), B * T, 3, H, W, params, _fake(3), ctypes.c_void_p(base), nb, None), f"lpips fwd {(B, T, H, W)}", False)
+        assert L.vpx_lpips_fwd(_fake(1), _fake(2), B * T, 3, H, W, params, _fake(3), ctypes.c_void_p(WS_BASE), nb - 1, None) == E_WS
+    nb = L.vpx_lpips_stem_workspace_bytes()
+    for H, W in lpips_ref.STEM_EDGE_SIZES:
+        for n0, n1 in ((2, 0), (1, 0), (1, 4), (4, 1)):
+            _ok(L, L.vpx_lpips_stem_fwd(_fake(1), _fake(2) if n1 else None, n0, n1, H, W, _fake(3), _fake(4), _fake(5), ctypes.c_void_p(WS_BASE_ODD), nb, None), f"stem {(n0, n1, H, W)}", False)
+    assert L.vpx_lpips_stem_fwd(_fake(1), None, 1, 0, 6, 7, _fake(3), _fake(4), _fake(5), ctypes.c_void_p(WS_BASE), nb, None) == E_ARG
+    assert L.vpx_lpips_stem_fwd(_fake(1), None, 1, 0, 7, 6, _fake(3), _fake(4), _fake(5), ctypes.c_void_p(WS_BASE), nb, None) == E_ARG
+    for h, w in lpips_ref.POOL_EDGE_MAPS:
+        for C in lpips_ref.POOL_EDGE_C:
+            _ok(L, L.vpx_lpips_maxpool_fwd(_fake(1), _fake(2), 2, h, w, C, None), f"maxpool {(h, w, C)}", False)
+    for C in lpips_ref.HEAD_EDGE_C:
+        for h, w in lpips_ref.HEAD_EDGE_MAPS:
+            nb = L.vpx_lpips_head_workspace_bytes(lpips_ref.HEAD_EDGE_N, h * w)
+            _ok(L, L.vpx_lpips_head_fwd(_fake(1), _fake(2), _fake(3), lpips_ref.HEAD_EDGE_N, h * w, C, _fake(4), ctypes.c_void_p(WS_BASE_ODD), nb, None), f"head {(h * w, C)}", False)
+    from vp_suite_amd._lib import ACT_RELU, PREC_F32, ConvDesc
+    for Ci, Co, k, pad in lpips_ref.TRUNK_LAYERS:
+        for h, w in lpips_ref.TRUNK_MAPS:
+            d = ConvDesc(lpips_ref.TRUNK_N, h, w, Ci, Co, k, k, 1, pad, 0, 0.0, PREC_F32, 0, 0)
+            nb = L.vpx_conv2d_act_workspace_bytes(ctypes.byref(d), ACT_RELU)
+            assert nb > 0, L.vpx_last_error()
+            _ok(L, L.vpx_conv2d_act_fwd(ctypes.byref(d), ACT_RELU, _fake(1), _fake(2), _fake(3), _fake(4), ctypes.c_void_p(WS_BASE_ODD), nb, None), f"trunk {(Ci, Co, k, h, w)}", False)
