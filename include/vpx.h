@@ -26,6 +26,7 @@
  * vpx_pixel_measures_fwd / _bwd    MSE, L1, SmoothL1, PSNR per frame         vp_suite/measure/image_wise.py:19-71
  * vpx_ssim_fwd / _bwd              SSIM per frame (piqa defaults)           vp_suite/measure/image_wise.py:99-117
  * vpx_lpips_fwd (+ stem, maxpool, head)  LPIPS per frame on AlexNet weights the caller brings  vp_suite/measure/image_wise.py (LPIPS)
+ * vpx_lpips_fwd_train / _bwd (+ stem, maxpool, head _bwd)  the same as a training loss: gradient to the prediction
  * vpx_groupnorm_fwd / _bwd         GroupNorm + LeakyReLU (DCGAN layers)    vp_suite/model_blocks/conv.py, model_blocks/phydnet.py
  * vpx_phycell_correct_fwd / _bwd   PhyCell_Cell prediction-correction       vp_suite/model_blocks/phydnet.py (PhyCell_Cell.forward)
  * vpx_moment_loss_fwd / _bwd       K2M + moment regularisation loss         vp_suite/models/phydnet.py (PhyDNet.forward)
@@ -388,8 +389,8 @@ int vpx_ssim_fwd(const float* pred, const float* target, long long n_frames, int
                  void* workspace, size_t workspace_bytes, void* stream);
 int vpx_ssim_bwd(const float* pred, const float* target, const float* dssim, long long n_frames, int C, int H, int W,
                  int layout, float* dpred, void* stream);
-/* LPIPS on an AlexNet trunk (https://arxiv.org/abs/1801.03924; image_wise.py's LPIPS through piqa), forward only, fp32, no atomics
- * (bit-reproducible in either determinism mode). The library ships no weights: the caller hands them in. Feature maps are
+/* LPIPS on an AlexNet trunk (https://arxiv.org/abs/1801.03924; image_wise.py's LPIPS through piqa), fp32, no atomics
+ * (bit-reproducible in either determinism mode); the training entry points and the backward follow below. The library ships no weights: the caller hands them in. Feature maps are
  * channels-last, [N, h, w, C], the layout of the library's convolutions.
  * vpx_lpips_fwd: pred / target: n_frames dense [3,H,W] frames in the model's range. Each is mapped by clamp((v+1)/2, 0, 1), then
  *   (u - mean_c) / std_c with ImageNet's mean (0.485, 0.456, 0.406) and std (0.229, 0.224, 0.225); both go through the trunk as ONE
@@ -420,6 +421,43 @@ int vpx_lpips_maxpool_fwd(const float* x, float* y, long long N, int H, int W, i
 size_t vpx_lpips_head_workspace_bytes(long long n, long long HW);
 int vpx_lpips_head_fwd(const float* fx, const float* fy, const float* w, long long n, long long HW, int C, double* table,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* LPIPS as a training loss: the gradient with respect to the PREDICTION (target and weights get none: the trunk is frozen). fp32 storage,
+ * no atomics, bit-reproducible in either determinism mode.
+ * vpx_lpips_fwd_train: vpx_lpips_fwd's launches in its order, so `table` is bit-equal to vpx_lpips_fwd's; the five taps of the 2 n_frames
+ *   images (prediction first) are written into `reserve` instead of the two slots used in turn. Workspace: vpx_lpips_workspace_bytes.
+ *   vpx_lpips_reserve_bytes(n_frames, H, W) = sum over the taps k of align256(2 n_frames h_k w_k C_k 4) + 256 bytes, (h_k, w_k) the map of
+ *   tap k ((H-7)/4+1 at tap 1, (h-3)/2+1 per pool), C_k = 64, 192, 384, 256, 256; 0 for sizes the call refuses. The pooled maps are not
+ *   kept. VPX_ERR_WORKSPACE also for a reserve that is NULL or smaller than that.
+ * vpx_lpips_bwd: dpred [n_frames,3,H,W] (dense, every element OVERWRITTEN) = sum_i dtable[i] d table[i] / d pred, from the reserve that
+ *   vpx_lpips_fwd_train filled for the same pred, params and sizes. dtable: n_frames doubles ON THE DEVICE (no host sync). Runs over the
+ *   n_frames prediction images only, the target half of each tap serves as fy: head of tap 5; conv5 data gradient, head of tap 4 with it
+ *   as `incoming`; conv4, head 3; conv3, pool, head 2; conv2, pool, head 1; stem. The four stride-1 data gradients are
+ *   vpx_conv2d_ex_bwd calls (exact fp32 operands, dw and db not requested) on a slot of vpx_conv2d_ex_bwd_workspace_bytes, which counts
+ *   weight-gradient slabs this call never touches. Workspace: vpx_lpips_bwd_workspace_bytes(n_frames, H, W). Errors as vpx_lpips_fwd.
+ * The pieces:
+ * vpx_lpips_head_bwd: dz [n, HW, C] (float32) = the gradient with respect to the tap's PRE-activation. With s = |fx|, r = 1 / (s + 1e-10),
+ *   u_c = 2 w_c (fx_c r - fy_c / (|fy| + 1e-10)):  dz_c = [fx_c > 0] (incoming_c + (dtable[i] / HW) (r u_c - fx_c r^2 (sum_k u_k fx_k) / s)),
+ *   in double. incoming [n, HW, C]: the gradient arriving from the next layer, or NULL; dz may be `incoming` itself. An all-zero feature
+ *   vector gives exactly 0, never NaN. C <= 512 (VPX_ERR_UNSUPPORTED beyond). No workspace.
+ * vpx_lpips_maxpool_bwd: dx [N,H,W,C] (every element written) from dy [N,(H-3)/2+1,(W-3)/2+1,C] and the pool's input x. Tie rule: a
+ *   window hands its gradient to the FIRST of its maximal elements in row-major order (rows, then columns), the element torch's CPU
+ *   max_pool2d picks; a NaN takes the window, the last one if there are several. Rows and columns that floor mode drops get exactly 0.
+ * vpx_lpips_stem_bwd: dx [n,3,H,W] (dense, every element written) from dz [n,Ho,Wo,64] (the gradient of tap 1's pre-activation), the
+ *   images x and w [64,3,11,11]: the data gradient of the stride-4 convolution times 0.5 / std_c times the clamp's mask. Clamp rule: the
+ *   mask is evaluated on the forward's own fp32 u = (x + 1) / 2 and passes the gradient where 0 <= u <= 1, bounds INCLUDED (torch's
+ *   clamp). Pixels no window covers (trailing rows / columns when (H + 4 - 11) % 4 != 0) get exactly 0. Workspace:
+ *   vpx_lpips_stem_workspace_bytes(). */
+size_t vpx_lpips_reserve_bytes(long long n_frames, int H, int W);
+int vpx_lpips_fwd_train(const float* pred, const float* target, long long n_frames, int C, int H, int W, const float* const* params,
+                        double* table, void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes, void* stream);
+size_t vpx_lpips_bwd_workspace_bytes(long long n_frames, int H, int W);
+int vpx_lpips_bwd(const float* pred, const float* const* params, const void* reserve, const double* dtable, long long n_frames, int C,
+                  int H, int W, float* dpred, void* workspace, size_t workspace_bytes, void* stream);
+int vpx_lpips_head_bwd(const float* fx, const float* fy, const float* w, const double* dtable, const float* incoming, long long n,
+                       long long HW, int C, float* dz, void* stream);
+int vpx_lpips_maxpool_bwd(const float* x, const float* dy, float* dx, long long N, int H, int W, int C, void* stream);
+int vpx_lpips_stem_bwd(const float* x, const float* w, const float* dz, long long n, int H, int W, float* dx, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* ---- plain stride-1 "same" convolution, NHWC, optional bias; y [N,H,W,Co] = conv(x [N,H,W,Ci], w [Co,Ci,kh,kw]) --- */
 size_t vpx_conv2d_workspace_bytes(int Ci, int Co, int kh, int kw);

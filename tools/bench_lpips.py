@@ -1,8 +1,9 @@
 """LPIPS (csrc/lpips.hip through ops.lpips_frames) against the plain-torch float32 chain of tests/lpips_ref.py on the same GPU, on the
 seeded weights of that module; prints ONE JSON line and writes it to profiles/lpips_bench.json. Not part of bench.py.
 
-For B*T = 160 frames of 3x64x64 and of 3x128x128 (T = 10), forward only (the library has no backward): the whole measure, and the
-stem, the first max-pool and the first head on their own against the matching torch expressions.
+For B*T = 160 frames of 3x64x64 and of 3x128x128 (T = 10): the whole measure forward, the stem, the first max-pool and the first head on
+their own against the matching torch expressions, and forward + backward (ops.lpips_frames_diff and its gradient with respect to the
+prediction against the torch chain under autograd, cotangent of ones).
 Library and torch calls are timed interleaved in one process (one step of each in turn), HIP events around each step after `--warmup`
 steps of both, the median of `--steps` reported; ratio = torch ms / library ms. Every step reads the next of a ring of input pairs
 that together exceed the last-level cache (256 MiB), so no step finds its inputs cached by the one before.
@@ -78,7 +79,7 @@ def main():
     assert torch.cuda.is_available(), "needs a GPU"
     w = {k: v.cuda() for k, v in lpips_ref.weights().items()}
     mean, std = torch.tensor(lpips_ref.MEAN, device="cuda").view(1, 3, 1, 1), torch.tensor(lpips_ref.STD, device="cuda").view(1, 3, 1, 1)
-    out = {"what": "csrc/lpips.hip vs the plain-torch float32 chain (same GPU, same weights), forward, interleaved, inputs rotated through a ring larger "
+    out = {"what": "csrc/lpips.hip vs the plain-torch float32 chain (same GPU, same weights), forward (and forward + backward to the prediction), interleaved, inputs rotated through a ring larger "
                    "than the last-level cache; ratio = torch ms / library ms", "steps": args.steps, "warmup": args.warmup, "cases": {}}
 
     def torch_norm(x):
@@ -101,6 +102,13 @@ def main():
         nx, ny = fx / (fx.pow(2).sum(dim=3, keepdim=True).sqrt() + 1e-10), fy / (fy.pow(2).sum(dim=3, keepdim=True).sqrt() + 1e-10)
         return ((nx - ny).pow(2) * w["lin1.weight"]).sum(dim=3).flatten(1).mean(dim=1)
 
+    def train_step(fn):
+        def run(pred, target):
+            p = pred.detach().requires_grad_()
+            fn(p, target).sum().backward()
+            return p.grad
+        return run
+
     with torch.no_grad():
         for name, shape in CASES.items():
             frames = _Ring(lambda: (torch.rand(shape, device="cuda") * 2.6 - 1.3, torch.rand(shape, device="cuda") * 2.6 - 1.3), 2 * 4 * torch.Size(shape).numel())
@@ -112,6 +120,9 @@ def main():
             maps = _Ring(lambda: (torch.rand(n2 // 2, h1, h1, 64, device="cuda"), torch.rand(n2 // 2, h1, h1, 64, device="cuda")), 4 * n2 * h1 * h1 * 64)
             res["maxpool1"] = _entry(*_time_pair(lambda a, b: ops.lpips_maxpool(a), lambda a, b: F.max_pool2d(a.permute(0, 3, 1, 2), 3, 2), maps, args.steps, args.warmup))
             res["head1"] = _entry(*_time_pair(lambda a, b: ops.lpips_head(a, b, w["lin1.weight"]), torch_head, maps, args.steps, args.warmup))
+            with torch.enable_grad():
+                res["lpips_frames_diff fwd+bwd"] = _entry(*_time_pair(train_step(lambda p, t: ops.lpips_frames_diff(p, t, w)), train_step(torch_chain),
+                                                                      frames, args.steps, args.warmup))
             out["cases"][name] = res
     out["lib_sha16"] = _lib_sha16()
     out["device"] = torch.cuda.get_device_name(0)

@@ -185,6 +185,13 @@ SIGNATURES = {
     "vpx_lpips_maxpool_fwd": (ci, [vp, vp, ll] + [ci] * 3 + [vp]),
     "vpx_lpips_head_workspace_bytes": (sz, [ll, ll]),
     "vpx_lpips_head_fwd": (ci, [vp, vp, vp, ll, ll, ci, vp] + _ws),                                   # fx fy w n HW C | table
+    "vpx_lpips_reserve_bytes": (sz, [ll, ci, ci]),
+    "vpx_lpips_fwd_train": (ci, [vp, vp, ll] + [ci] * 3 + [vp, vp, vp, sz] + _ws),                    # pred target n C H W | params table reserve
+    "vpx_lpips_bwd_workspace_bytes": (sz, [ll, ci, ci]),
+    "vpx_lpips_bwd": (ci, [vp, vp, vp, vp, ll] + [ci] * 3 + [vp] + _ws),                              # pred params reserve dtable n C H W | dpred
+    "vpx_lpips_head_bwd": (ci, [vp, vp, vp, vp, vp, ll, ll, ci, vp, vp]),                             # fx fy w dtable incoming n HW C | dz
+    "vpx_lpips_maxpool_bwd": (ci, [vp, vp, vp, ll] + [ci] * 3 + [vp]),
+    "vpx_lpips_stem_bwd": (ci, [vp, vp, vp, ll, ci, ci, vp] + _ws),                                   # x w dz n H W | dx
     # plain stride-1 "same" convolution
     "vpx_conv2d_workspace_bytes": (sz, [ci] * 4),
     "vpx_conv2d_nhwc_fwd": (ci, [vp] * 4 + [ci] * 8 + _ws),

@@ -9,8 +9,8 @@ The MSE with the reference's reduction (sum over c,h,w -> mean over t -> mean ov
 its own kernel, which writes d/dpred in the same pass: `mse_measure`, and a provider configured with "mse" alone.
 
 LPIPS runs on AlexNet weights the USER registers (register_lpips_weights: a dict, an .npz or a .pth file; nothing is ever downloaded):
-a third per-frame table, from csrc/lpips.hip on the GPU (forward only). Until weights are registered its registry entry raises
-NotImplementedError, as FVD's always does: this build ships no pretrained network."""
+a third per-frame table, from csrc/lpips.hip on the GPU (a training loss too once registered with differentiable=True). Until weights
+are registered its registry entry raises NotImplementedError, as FVD's always does: this build ships no pretrained network."""
 import os
 
 import torch
@@ -92,6 +92,7 @@ LPIPS_MIN_SIDE = 31                                                             
 _TORCHVISION_FEATURES = (0, 3, 6, 8, 10)                                              # features.{i}: the five convolutions
 _lpips_weights = None   # canonical {key: host tensor} once registered
 _lpips_on_device = {}   # (device, dtype) -> the same on a device
+_lpips_differentiable = False   # register_lpips_weights(differentiable=True): a GPU prediction that requires grad runs the training call
 
 
 def _lpips_canonical_key(key):
@@ -121,13 +122,17 @@ def _lpips_load(source):
     raise ValueError(f"LPIPS weights: {path!r} is neither a dict, an .npz nor a .pth file")
 
 
-def register_lpips_weights(source, linear_source=None):
+def register_lpips_weights(source, linear_source=None, differentiable=False):
     """Registers the AlexNet trunk and the five linear layers LPIPS runs on; from then on "lpips" works wherever a measure key is accepted.
     source (and, where the linear layers live in a file of their own, as upstream keeps them, linear_source): a dict, an .npz file or a
     .pth file (read with torch.load(weights_only=True)). Accepted keys: conv{1..5}.weight / .bias and lin{1..5}.weight ([C] or [1,C,1,1]);
     torchvision's features.{0,3,6,8,10}.weight / .bias; the `lpips` package's lin{0..4}.model.1.weight. Other keys are ignored. Every shape
-    is checked before anything is stored (ValueError naming the key and both shapes). Nothing is ever downloaded."""
-    global _lpips_weights
+    is checked before anything is stored (ValueError naming the key and both shapes). Nothing is ever downloaded.
+    differentiable=True makes LPIPS a training loss on the GPU: a prediction that requires grad under grad mode then runs
+    ops.lpips_frames_diff, which keeps the five taps of prediction and target until its backward has run (memory an evaluation call does
+    not hold) and hands the gradient to the prediction alone. With the default, and for every prediction without grad, the call and its
+    bits are the evaluation's, and a prediction that requires grad is refused."""
+    global _lpips_weights, _lpips_differentiable
     found = {}
     for src in (source, linear_source):
         if src is None:
@@ -151,13 +156,15 @@ def register_lpips_weights(source, linear_source=None):
     if missing:
         raise ValueError(f"LPIPS weights: no tensor for {missing} (accepted key layouts: see register_lpips_weights)")
     _lpips_weights = {k: found[k] for k in LPIPS_KEYS}
+    _lpips_differentiable = bool(differentiable)
     _lpips_on_device.clear()
 
 
 def clear_lpips_weights():
-    """Forgets the registered weights: "lpips" raises NotImplementedError again."""
-    global _lpips_weights
+    """Forgets the registered weights and the differentiable flag: "lpips" raises NotImplementedError again."""
+    global _lpips_weights, _lpips_differentiable
     _lpips_weights = None
+    _lpips_differentiable = False
     _lpips_on_device.clear()
 
 
@@ -190,8 +197,9 @@ def _lpips_host(pred, target, weights):
 
 
 def frame_lpips(pred, target, name=LPIPS_NAME):
-    """[B, T]: LPIPS of every frame on the registered weights (3-channel frames, channels at dim 2, at least 31x31). On the GPU forward
-    only: the backward is not implemented there (NotImplementedError for a prediction that requires grad under grad mode)."""
+    """[B, T]: LPIPS of every frame on the registered weights (3-channel frames, channels at dim 2, at least 31x31). On the GPU a
+    prediction that requires grad under grad mode is refused (NotImplementedError) unless the weights were registered with
+    differentiable=True: then it runs ops.lpips_frames_diff, same values, gradient to the prediction."""
     _check_5d(name, pred, target)
     if pred.shape[2] != 3:
         raise ValueError(f"{name} needs 3-channel images with the channels at dim 2")
@@ -199,6 +207,8 @@ def frame_lpips(pred, target, name=LPIPS_NAME):
         raise ValueError(f"{name} needs images of at least {LPIPS_MIN_SIDE}x{LPIPS_MIN_SIDE} pixels (below that the third tap has no pixel)")
     if pred.is_cuda:
         from . import ops
+        if _lpips_differentiable and ops.needs_grad(pred):
+            return ops.lpips_frames_diff(pred, target, lpips_weights(pred.device)).float()
         return ops.lpips_frames(pred, target, lpips_weights(pred.device)).float()   # (the kernel's table is float64)
     return _lpips_host(pred, target, lpips_weights("cpu", pred.dtype))
 
@@ -334,7 +344,8 @@ def _frame_values(measures, pred, target):
 class PredictionLossProvider:
     """config: {"device": ..., "losses_and_scales": {key: scale}} over any mix of "mse", "l1", "smooth_l1", "psnr" and "ssim"
     (loss_provider.py). All pixel-wise terms together cost one sums pass and one gradient pass, SSIM one of each. "lpips" joins them once
-    weights are registered: on the GPU as a value only (its backward is not implemented: a prediction that requires grad raises)."""
+    weights are registered: on the GPU as a value only (a prediction that requires grad raises) unless they were registered with
+    differentiable=True, which makes it a loss term with a HIP backward."""
 
     def __init__(self, config: dict):
         self.device = config["device"]

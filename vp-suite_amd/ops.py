@@ -892,7 +892,8 @@ def ssim_frames(pred, target):
     return _SSIMFramesFn.apply(pred, target)
 
 
-# ---- LPIPS on an AlexNet trunk (csrc/lpips.hip): forward only; feature maps are channels-last [N, h, w, C] ---------------------------
+# ---- LPIPS on an AlexNet trunk (csrc/lpips.hip); feature maps are channels-last [N, h, w, C]. lpips_frames is the evaluation call (forward
+# only), lpips_frames_diff the training call (gradient to the prediction) ---------------------------------------------------------------
 LPIPS_MIN_SIDE = 31   # below it the third tap has no pixel
 LPIPS_CONV_SHAPES = ((64, 3, 11, 11), (192, 64, 5, 5), (384, 192, 3, 3), (256, 384, 3, 3), (256, 256, 3, 3))   # torchvision's AlexNet.features
 LPIPS_KEYS = tuple(f"conv{i}.weight" for i in range(1, 6)) + tuple(f"conv{i}.bias" for i in range(1, 6)) + tuple(f"lin{i}.weight" for i in range(1, 6))
@@ -959,6 +960,19 @@ def lpips_frames(pred, target, weights):
     target run through the trunk as one batch. FORWARD ONLY: the backward is not implemented, a prediction that requires grad under grad
     mode raises NotImplementedError (use torch.no_grad() or detach)."""
     what = "lpips_frames"
+    B, T, C, H, W = _lpips_frames_shape(what, pred, target)
+    if needs_grad(pred, target):
+        raise NotImplementedError(f"{what}: the backward of LPIPS is not implemented in this build (forward only): evaluate it under "
+                                  f"torch.no_grad() or on detached tensors")
+    p, tg, params = _lpips_frames_operands(what, pred, target, weights)
+    L = _lib.lib()
+    ws, ws_bytes = workspace(p.device, L.vpx_lpips_workspace_bytes, B * T, H, W)
+    table = torch.empty(B, T, device=p.device, dtype=torch.float64)
+    check(L.vpx_lpips_fwd(ptr(p), ptr(tg), B * T, C, H, W, ptr_array(params), ptr(table), ptr(ws), ws_bytes, stream()), "vpx_lpips_fwd")
+    return table
+
+
+def _lpips_frames_shape(what, pred, target):
     if pred.ndim != 5 or target.ndim != 5:
         raise ValueError(f"{what} expects 5-D inputs!")
     if pred.shape != target.shape:
@@ -968,18 +982,109 @@ def lpips_frames(pred, target, weights):
         raise ValueError(f"{what} needs 3-channel images with the channels at dim 2")
     if H < LPIPS_MIN_SIDE or W < LPIPS_MIN_SIDE:
         raise ValueError(f"{what} needs images of at least {LPIPS_MIN_SIDE}x{LPIPS_MIN_SIDE} pixels (below that the third tap has no pixel)")
-    if needs_grad(pred, target):
-        raise NotImplementedError(f"{what}: the backward of LPIPS is not implemented in this build (forward only): evaluate it under "
-                                  f"torch.no_grad() or on detached tensors")
+    return B, T, C, H, W
+
+
+def _lpips_frames_operands(what, pred, target, weights):
     p, tg = _lpips_operand(pred, what, "pred"), _lpips_operand(target, what, "target")
     params = [_lpips_operand(weights[k], what, k, LPIPS_SHAPES[k]) for k in LPIPS_KEYS]
     if any(t.device != p.device for t in params + [tg]):
         raise ValueError(f"{what}: prediction, target and weights must live on one device")
+    return p, tg, params
+
+
+class _LPIPSFramesFn(torch.autograd.Function):
+    """lpips_frames_diff: the forward keeps the five taps of both halves of the batch in a reserve, the backward runs from them. The
+    gradient goes to the prediction alone."""
+
+    @staticmethod
+    def forward(ctx, pred, target, weights):
+        what = "lpips_frames_diff"
+        p, tg, params = _lpips_frames_operands(what, pred, target, weights)
+        B, T, C, H, W = p.shape
+        L = _lib.lib()
+        ws, ws_bytes = workspace(p.device, L.vpx_lpips_workspace_bytes, B * T, H, W)
+        reserve, reserve_bytes = workspace(p.device, L.vpx_lpips_reserve_bytes, B * T, H, W)
+        table = torch.empty(B, T, device=p.device, dtype=torch.float64)
+        check(L.vpx_lpips_fwd_train(ptr(p), ptr(tg), B * T, C, H, W, ptr_array(params), ptr(table), ptr(reserve), reserve_bytes, ptr(ws), ws_bytes,
+                                    stream()), "vpx_lpips_fwd_train")
+        ctx.save_for_backward(p, reserve, *params)
+        return table
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dtable):
+        p, reserve, *params = ctx.saved_tensors
+        B, T, C, H, W = p.shape
+        L = _lib.lib()
+        ws, ws_bytes = workspace(p.device, L.vpx_lpips_bwd_workspace_bytes, B * T, H, W)
+        g = torch.empty_like(p)   # out of place: a second backward through the same node (retain_graph) stays correct
+        dtable = dtable.to(torch.float64).contiguous()
+        check(L.vpx_lpips_bwd(ptr(p), ptr_array(params), ptr(reserve), ptr(dtable), B * T, C, H, W, ptr(g), ptr(ws), ws_bytes, stream()),
+              "vpx_lpips_bwd")
+        return g, None, None
+
+
+def lpips_frames_diff(pred, target, weights):
+    """lpips_frames as a training loss: the same [B, T] float64 table, bit for bit, differentiable ONCE with respect to `pred`. The
+    weights never receive a gradient (the trunk is frozen) and a target that requires grad raises NotImplementedError. A call whose
+    prediction requires grad keeps the five taps of the 2 B T images until its backward has run; without grad it is lpips_frames."""
+    what = "lpips_frames_diff"
+    B, T, C, H, W = _lpips_frames_shape(what, pred, target)
+    if needs_grad(target):
+        raise NotImplementedError(f"{what}: the gradient with respect to the target is not implemented (the gradient goes to the prediction)")
+    if not needs_grad(pred):
+        return lpips_frames(pred, target, weights)
+    return _LPIPSFramesFn.apply(pred, target, weights)
+
+
+def lpips_head_bwd(fx, fy, w, dtable, incoming=None):
+    """[N, h, w, C] float32: the gradient with respect to the PRE-activation of the tap fx (channels-last, as lpips_head takes it) of
+    sum_i dtable[i] * lpips_head(fx, fy, w)[i], plus `incoming` (the gradient arriving from the next layer), times the mask fx > 0.
+    dtable: [N] float64 on the maps' device."""
+    what = "lpips_head_bwd"
+    if fx.ndim != 4 or fx.shape != fy.shape or (incoming is not None and incoming.shape != fx.shape):
+        raise ValueError(f"{what}: expected channels-last maps [N, h, w, C] of one shape")
+    fx, fy = _lpips_operand(fx, what, "fx"), _lpips_operand(fy, what, "fy")
+    incoming = None if incoming is None else _lpips_operand(incoming, what, "incoming")
+    N, h, wd, C = fx.shape
+    w = _lpips_operand(w, what, "w", (C,))
+    if dtable.dtype != torch.float64 or tuple(dtable.shape) != (N,) or not dtable.is_contiguous() or dtable.device != fx.device:
+        raise ValueError(f"{what}: dtable must be a contiguous float64 tensor of shape ({N},) on the maps' device")
+    dz = torch.empty_like(fx)
+    check(_lib.lib().vpx_lpips_head_bwd(ptr(fx), ptr(fy), ptr(w), ptr(dtable), ptr(incoming), N, h * wd, C, ptr(dz), stream()), "vpx_lpips_head_bwd")
+    return dz
+
+
+def lpips_maxpool_bwd(x, dy):
+    """[N, h, w, C]: the gradient of lpips_maxpool at its input x from dy [N, (h-3)//2+1, (w-3)//2+1, C]. Among tied maxima of a window the
+    first in row-major order takes the gradient (torch's CPU rule)."""
+    what = "lpips_maxpool_bwd"
+    if x.ndim != 4:
+        raise ValueError(f"{what}: expected a channels-last map [N, h, w, C]")
+    x = _lpips_operand(x, what, "x")
+    N, h, w, C = x.shape
+    dy = _lpips_operand(dy, what, "dy", (N, max((h - 3) // 2 + 1, 0), max((w - 3) // 2 + 1, 0), C))
+    dx = torch.empty_like(x)
+    check(_lib.lib().vpx_lpips_maxpool_bwd(ptr(x), ptr(dy), ptr(dx), N, h, w, C, stream()), "vpx_lpips_maxpool_bwd")
+    return dx
+
+
+def lpips_stem_bwd(x, w, dz):
+    """[N, 3, H, W]: the gradient of lpips_stem at the images x from dz [N, Ho, Wo, 64], the gradient of tap 1's pre-activation; the clamp
+    passes the gradient where 0 <= (x + 1) / 2 <= 1 in float32, bounds included."""
+    what = "lpips_stem_bwd"
+    if x.ndim != 4 or x.shape[1] != 3:
+        raise ValueError(f"{what}: expected [N,3,H,W] images of one size")
+    x = _lpips_operand(x, what, "x")
+    w = _lpips_operand(w, what, "w", LPIPS_CONV_SHAPES[0])
+    N, (H, W) = x.shape[0], x.shape[2:]
+    dz = _lpips_operand(dz, what, "dz", (N, max((H + 4 - 11) // 4 + 1, 0), max((W + 4 - 11) // 4 + 1, 0), 64))
     L = _lib.lib()
-    ws, ws_bytes = workspace(p.device, L.vpx_lpips_workspace_bytes, B * T, H, W)
-    table = torch.empty(B, T, device=p.device, dtype=torch.float64)
-    check(L.vpx_lpips_fwd(ptr(p), ptr(tg), B * T, C, H, W, ptr_array(params), ptr(table), ptr(ws), ws_bytes, stream()), "vpx_lpips_fwd")
-    return table
+    ws, ws_bytes = workspace(x.device, L.vpx_lpips_stem_workspace_bytes)
+    dx = torch.empty_like(x)
+    check(L.vpx_lpips_stem_bwd(ptr(x), ptr(w), ptr(dz), N, H, W, ptr(dx), ptr(ws), ws_bytes, stream()), "vpx_lpips_stem_bwd")
+    return dx
 
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
