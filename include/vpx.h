@@ -27,6 +27,7 @@
  * vpx_ssim_fwd / _bwd              SSIM per frame (piqa defaults)           vp_suite/measure/image_wise.py:99-117
  * vpx_lpips_fwd (+ stem, maxpool, head)  LPIPS per frame on AlexNet weights the caller brings  vp_suite/measure/image_wise.py (LPIPS)
  * vpx_lpips_fwd_train / _bwd (+ stem, maxpool, head _bwd)  the same as a training loss: gradient to the prediction
+ * vpx_fvd_features (+ conv3d_same, maxpool3d_same, fvd_head) / vpx_frechet_distance  FVD on I3D weights the caller brings  vp_suite/measure/fvd/fvd.py
  * vpx_groupnorm_fwd / _bwd         GroupNorm + LeakyReLU (DCGAN layers)    vp_suite/model_blocks/conv.py, model_blocks/phydnet.py
  * vpx_phycell_correct_fwd / _bwd   PhyCell_Cell prediction-correction       vp_suite/model_blocks/phydnet.py (PhyCell_Cell.forward)
  * vpx_moment_loss_fwd / _bwd       K2M + moment regularisation loss         vp_suite/models/phydnet.py (PhyDNet.forward)
@@ -458,6 +459,53 @@ int vpx_lpips_head_bwd(const float* fx, const float* fy, const float* w, const d
 int vpx_lpips_maxpool_bwd(const float* x, const float* dy, float* dx, long long N, int H, int W, int C, void* stream);
 int vpx_lpips_stem_bwd(const float* x, const float* w, const float* dz, long long n, int H, int W, float* dx, void* workspace,
                        size_t workspace_bytes, void* stream);
+
+/* ---- Frechet Video Distance on an Inception-I3D trunk (csrc/fvd.hip; vp_suite/measure/fvd), forward only. Activations are channels-last
+ * [N, T, H, W, C] float32. "SAME" padding, per axis (the reference's Unit3D / MaxPool3dSamePadding rule): pad = max(k - s, 0) if
+ * size % s == 0, else max(k - size % s, 0); front = pad / 2, the rest behind; output size ceil(size / s). vpx_same_padding answers it
+ * (host only): *front and *out for one axis.
+ *
+ * vpx_conv3d_same: y[.., coff + o] = act(sum x * w + bias[o]) over the ZERO-padded map. x [N,T,H,W,Ci] dense; wp the weights PACKED as
+ *   [kt][kh][kw][Ci][Co] (a permutation of the reference's [Co,Ci,kt,kh,kw]; BatchNorm, where a layer has one, folded in by the caller);
+ *   bias [Co]; y [N,To,Ho,Wo,ldy], of which only channels coff .. coff + Co - 1 are written (the branches of an Inception block share one
+ *   tensor). relu: 0 / 1. Operands are exact fp32 on the fp32 MFMA; every output sums K in one fixed order, whatever the batch size.
+ *   Kernel and stride sides up to 15. No workspace (the query answers 0).
+ * vpx_maxpool3d_same: the max over windows of the ZERO-padded map, as the reference pads before it pools: a window that touches the border
+ *   never returns less than 0. NaN wins, as in torch. No workspace.
+ * vpx_fvd_head: out [N, n_features] = bias + w [n_features, C] * (mean over the positions of x [N,2,7,7,C]); double arithmetic, rounded
+ *   once. A map that is not 2x7x7 is VPX_ERR_ARG; C <= 4096. No workspace.
+ * vpx_fvd_features: out [n0 + n1, n_features] of the clips x0 [n0,T,C,h,w] and, behind them, x1 [n1,T,C,h,w] (NULL with n1 = 0): planar
+ *   frames, values as they are. They are resized to 224x224 (bilinear, align_corners = False, no antialiasing, the arithmetic of
+ *   vpx_frames_adapt bit for bit; 224x224 frames are copied) straight into the channels-last stem input, then the rows of `table` run.
+ *   A row has VPX_FVD_ROW ints: op, src, dst, Ci, Co, kt, kh, kw, st, sh, sw, relu, coff, ld, param, 0. src and dst are two different ones of
+ *   four buffers, buffer 0 the staged clips. VPX_FVD_CONV writes channels coff .. coff + Co - 1 of a map of channel stride ld into dst from
+ *   params[param] (packed weights, as above) and params[param + 1] (bias); VPX_FVD_POOL pools src into dst; VPX_FVD_HEAD, the last row,
+ *   reads params[param] ([Co, Ci]) and params[param + 1] and writes `out`. `table` lives on the HOST, `params` is a host array of
+ *   device pointers. VPX_ERR_ARG: a row whose Ci is not its source's channel count, a buffer read before it is written, a final map
+ *   that is not 2x7x7 (clips of 9 .. 16 frames give it). Workspace: vpx_fvd_features_workspace_bytes(n0 + n1, ...), 0 for a refusal.
+ * vpx_frechet_distance: *out (ONE double on the device) = fact sum Ep^2 + fact sum Et^2 - 2 sum_i sqrt(sigma_i^2 + 1e-15) + |mu_p - mu_t|^2
+ *   for pred, target [b, n] float32, E the centred tables, fact = 1 / (b - 1) (1 for b = 1), sigma_i the singular values of the b x b
+ *   matrix fact Ep Et^T: the reference's calculate_2_wasserstein_dist restated, in float64, every sum in one fixed order. The singular
+ *   values come from a one-sided Jacobi iteration of at most 40 sweeps; input on which a 40th sweep still rotates gives NaN, never an
+ *   unconverged number. b <= 256 (VPX_ERR_UNSUPPORTED beyond). */
+#define VPX_FVD_ROW 16
+enum { VPX_FVD_CONV = 0, VPX_FVD_POOL = 1, VPX_FVD_HEAD = 2 };
+int vpx_same_padding(int size, int k, int s, int* front, int* out);
+size_t vpx_conv3d_same_workspace_bytes(void);
+int vpx_conv3d_same(const float* x, const float* wp, const float* bias, float* y, long long N, int T, int H, int W, int Ci, int Co,
+                    int kt, int kh, int kw, int st, int sh, int sw, int relu, int ldy, int coff, void* stream);
+size_t vpx_maxpool3d_same_workspace_bytes(void);
+int vpx_maxpool3d_same(const float* x, float* y, long long N, int T, int H, int W, int C, int kt, int kh, int kw, int st, int sh, int sw,
+                       void* stream);
+size_t vpx_fvd_head_workspace_bytes(void);
+int vpx_fvd_head(const float* x, const float* w, const float* bias, float* out, long long N, int T, int H, int W, int C, int n_features,
+                 void* stream);
+size_t vpx_fvd_features_workspace_bytes(long long n_clips, int T, int C, int h, int w, const int* table, int n_rows);
+int vpx_fvd_features(const float* x0, const float* x1, long long n0, long long n1, int T, int C, int h, int w, const int* table, int n_rows,
+                     const float* const* params, int n_params, float* out, void* workspace, size_t workspace_bytes, void* stream);
+size_t vpx_frechet_distance_workspace_bytes(int b, int n);
+int vpx_frechet_distance(const float* pred, const float* target, int b, int n, double* out, void* workspace, size_t workspace_bytes,
+                         void* stream);
 
 /* ---- plain stride-1 "same" convolution, NHWC, optional bias; y [N,H,W,Co] = conv(x [N,H,W,Ci], w [Co,Ci,kh,kw]) --- */
 size_t vpx_conv2d_workspace_bytes(int Ci, int Co, int kh, int kw);

@@ -192,6 +192,18 @@ SIGNATURES = {
     "vpx_lpips_head_bwd": (ci, [vp, vp, vp, vp, vp, ll, ll, ci, vp, vp]),                             # fx fy w dtable incoming n HW C | dz
     "vpx_lpips_maxpool_bwd": (ci, [vp, vp, vp, ll] + [ci] * 3 + [vp]),
     "vpx_lpips_stem_bwd": (ci, [vp, vp, vp, ll, ci, ci, vp] + _ws),                                   # x w dz n H W | dx
+    # Frechet Video Distance on an I3D trunk
+    "vpx_same_padding": (ci, [ci, ci, ci, _int_p, _int_p]),
+    "vpx_conv3d_same_workspace_bytes": (sz, []),
+    "vpx_conv3d_same": (ci, [vp] * 4 + [ll] + [ci] * 14 + [vp]),                                      # x wp bias y | N T H W Ci Co | kernel stride | relu ldy coff
+    "vpx_maxpool3d_same_workspace_bytes": (sz, []),
+    "vpx_maxpool3d_same": (ci, [vp, vp, ll] + [ci] * 10 + [vp]),                                      # x y | N T H W C | kernel stride
+    "vpx_fvd_head_workspace_bytes": (sz, []),
+    "vpx_fvd_head": (ci, [vp] * 4 + [ll] + [ci] * 5 + [vp]),                                          # x w bias out | N T H W C n_features
+    "vpx_fvd_features_workspace_bytes": (sz, [ll] + [ci] * 4 + [_int_p, ci]),                         # n_clips T C h w | table n_rows
+    "vpx_fvd_features": (ci, [vp, vp, ll, ll] + [ci] * 4 + [_int_p, ci, vp, ci, vp] + _ws),           # x0 x1 n0 n1 T C h w | table n_rows params n_params | out
+    "vpx_frechet_distance_workspace_bytes": (sz, [ci, ci]),
+    "vpx_frechet_distance": (ci, [vp, vp, ci, ci, vp] + _ws),                                         # pred target b n | out
     # plain stride-1 "same" convolution
     "vpx_conv2d_workspace_bytes": (sz, [ci] * 4),
     "vpx_conv2d_nhwc_fwd": (ci, [vp] * 4 + [ci] * 8 + _ws),

@@ -10,8 +10,13 @@ its own kernel, which writes d/dpred in the same pass: `mse_measure`, and a prov
 
 LPIPS runs on AlexNet weights the USER registers (register_lpips_weights: a dict, an .npz or a .pth file; nothing is ever downloaded):
 a third per-frame table, from csrc/lpips.hip on the GPU (a training loss too once registered with differentiable=True). Until weights
-are registered its registry entry raises NotImplementedError, as FVD's always does: this build ships no pretrained network."""
+are registered its registry entry raises NotImplementedError: this build ships no pretrained network.
+
+FVD likewise runs on Inception-I3D weights the USER registers (register_fvd_weights; channel widths read from the tensors, BatchNorm folded
+at registration): not a per-frame table but one distance per clip chunk, from csrc/fvd.hip on the GPU (forward only), computed by the
+providers beside the tables. Until weights are registered "fvd" raises NotImplementedError everywhere."""
 import os
+import warnings
 
 import torch
 import torch.nn.functional as F
@@ -298,11 +303,6 @@ class SSIM(VPMeasure):
         return 1.0 - x
 
 
-class _Unavailable(VPMeasure):
-    def __init__(self, device):
-        raise NotImplementedError(f"{self.NAME} needs pretrained weights that this build does not ship")
-
-
 class LPIPS(VPMeasure):
     """image_wise.py's LPIPS: the mean over all frames of the AlexNet LPIPS value, on weights the user registered (register_lpips_weights);
     without them the constructor raises NotImplementedError, as it always did."""
@@ -318,9 +318,284 @@ class LPIPS(VPMeasure):
         return table
 
 
-class FrechetVideoDistance(_Unavailable):
-    NAME = "Frechet Video Distance (FVD)"
+# ---- FVD: I3D weights a user brings, the host expression, the chunk rule ------------------------------------------------------------------
+FVD_NAME = "Frechet Video Distance (FVD)"
+FVD_MIN_T, FVD_MAX_T, FVD_SIDE, FVD_BN_EPS = 9, 16, 224, 1e-3
+FVD_BLOCKS = ("Mixed_3b", "Mixed_3c", "Mixed_4b", "Mixed_4c", "Mixed_4d", "Mixed_4e", "Mixed_4f", "Mixed_5b", "Mixed_5c")
+FVD_BRANCHES = (("b0", 1), ("b1a", 1), ("b1b", 3), ("b2a", 1), ("b2b", 3), ("b3b", 1))   # the units of an Inception block and their kernel side
+# InceptionI3d up to its logits: ("unit", name, kernel, stride) | ("pool", kernel, stride) | ("block", name). The topology is fixed, the
+# channel widths are read from the registered tensors.
+FVD_SEQUENCE = ((("unit", "Conv3d_1a_7x7", (7, 7, 7), (2, 2, 2)), ("pool", (1, 3, 3), (1, 2, 2)), ("unit", "Conv3d_2b_1x1", (1, 1, 1), (1, 1, 1)),
+                 ("unit", "Conv3d_2c_3x3", (3, 3, 3), (1, 1, 1)), ("pool", (1, 3, 3), (1, 2, 2)))
+                + tuple(("block", n) for n in FVD_BLOCKS[:2]) + (("pool", (3, 3, 3), (2, 2, 2)),)
+                + tuple(("block", n) for n in FVD_BLOCKS[2:7]) + (("pool", (2, 2, 2), (2, 2, 2)),) + tuple(("block", n) for n in FVD_BLOCKS[7:]))
+FVD_UNITS = tuple(u for step in FVD_SEQUENCE if step[0] != "pool" for u in ((step[1],) if step[0] == "unit" else tuple(f"{step[1]}.{b}" for b, _ in FVD_BRANCHES)))
+_fvd_weights = None    # {unit: (folded weight, bias) float64 on the host, "logits": (weight [F, C], bias)} once registered
+_fvd_on_device = {}    # device -> what the trunk reads there
+
+
+def _fvd_unit_kernel(unit):
+    for step in FVD_SEQUENCE:
+        if step[0] == "unit" and step[1] == unit:
+            return step[2]
+    return (dict(FVD_BRANCHES)[unit.split(".")[1]],) * 3
+
+
+def fvd_fold(w, gamma, beta, mean, var):
+    """(weight, bias) of a Unit3D with its eval-mode BatchNorm (eps 1e-3) folded in, in float64: scale = gamma / sqrt(var + eps) goes into
+    the weights, beta - mean * scale becomes the bias."""
+    w, gamma, beta, mean, var = (t.double() for t in (w, gamma, beta, mean, var))
+    scale = gamma / torch.sqrt(var + FVD_BN_EPS)
+    return (w * scale.view(-1, 1, 1, 1, 1)).contiguous(), (beta - mean * scale).contiguous()
+
+
+def register_fvd_weights(source):
+    """Registers the Inception-I3D network FVD runs on; from then on "fvd" works wherever a measure key is accepted. source: a dict, an
+    .npz file or a .pth file (read with torch.load(weights_only=True)) keyed as InceptionI3d.state_dict(): {unit}.conv3d.weight and
+    {unit}.bn.weight / .bias / .running_mean / .running_var for Conv3d_1a_7x7, Conv3d_2b_1x1, Conv3d_2c_3x3 and Mixed_3b.b0 ... Mixed_5c.b3b,
+    logits.conv3d.weight / .bias; num_batches_tracked and other keys are ignored. The topology is I3D's; the channel WIDTHS are read from the
+    tensors (a thin network registers like the real one; the stem takes 2 or 3 channels) and checked for consistency before anything is
+    stored: every layer's input channels against its producer's outputs, a block's four branches against the next layer's inputs (ValueError
+    naming the key and both shapes). BatchNorm (eps 1e-3, running statistics) is folded here, in float64: scale = gamma / sqrt(var + eps)
+    goes into the weights, beta - mean * scale becomes a bias. Nothing is ever downloaded."""
+    global _fvd_weights
+    raw = {k: torch.as_tensor(v).detach().cpu() for k, v in _lpips_load(source).items() if isinstance(k, str)}
+
+    def need(key, shape=None):
+        if key not in raw:
+            raise ValueError(f"FVD weights: no tensor for {key!r} (expected the keys of InceptionI3d.state_dict())")
+        t = raw[key]
+        if not t.is_floating_point():
+            raise ValueError(f"FVD weights: {key!r} has dtype {t.dtype}, expected a floating-point tensor")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"FVD weights: {key!r} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t.double()
+
+    def unit(name, c_in, producer):
+        key = f"{name}.conv3d.weight"
+        w = need(key)
+        k = _fvd_unit_kernel(name)
+        if w.ndim != 5 or tuple(w.shape[2:]) != k:
+            raise ValueError(f"FVD weights: {key!r} has shape {tuple(w.shape)}, expected (Co, Ci, {k[0]}, {k[1]}, {k[2]})")
+        if c_in is None:
+            if w.shape[1] not in (2, 3):
+                raise ValueError(f"FVD weights: {key!r} has shape {tuple(w.shape)}, expected (Co, 2 or 3, 7, 7, 7): the stem takes 2 or 3 channels")
+        elif w.shape[1] != c_in:
+            raise ValueError(f"FVD weights: {key!r} has shape {tuple(w.shape)}, expected ({w.shape[0]}, {c_in}, {k[0]}, {k[1]}, {k[2]}): its producer {producer}")
+        co = w.shape[0]
+        return fvd_fold(w, *(need(f"{name}.bn.{p}", (co,)) for p in ("weight", "bias", "running_mean", "running_var")))
+
+    found, c, producer = {}, None, None
+    for step in FVD_SEQUENCE:
+        if step[0] == "unit":
+            found[step[1]] = unit(step[1], c, producer)
+            c, producer = found[step[1]][0].shape[0], f"{step[1] + '.conv3d.weight'!r} has shape {tuple(found[step[1]][0].shape)}"
+        elif step[0] == "block":
+            name, widths = step[1], {}
+            for b, _ in FVD_BRANCHES:
+                c_b, prod_b = (c, producer) if b in ("b0", "b1a", "b2a", "b3b") else (widths[b[:2] + "a"], f"{name + '.' + b[:2] + 'a.conv3d.weight'!r} has {widths[b[:2] + 'a']} output channels")
+                found[f"{name}.{b}"] = unit(f"{name}.{b}", c_b, prod_b)
+                widths[b] = found[f"{name}.{b}"][0].shape[0]
+            outs = tuple(widths[b] for b in ("b0", "b1b", "b2b", "b3b"))
+            c, producer = sum(outs), f"{name} ends in {outs[0]} + {outs[1]} + {outs[2]} + {outs[3]} = {sum(outs)} channels"
+    w = need("logits.conv3d.weight")
+    if w.ndim != 5 or tuple(w.shape[1:]) != (c, 1, 1, 1):
+        raise ValueError(f"FVD weights: 'logits.conv3d.weight' has shape {tuple(w.shape)}, expected (n_features, {c}, 1, 1, 1): its producer {producer}")
+    found["logits"] = (w.reshape(w.shape[0], c).contiguous(), need("logits.conv3d.bias", (w.shape[0],)).contiguous())
+    _fvd_weights = found
+    _fvd_on_device.clear()
+
+
+def clear_fvd_weights():
+    """Forgets the registered network: "fvd" raises NotImplementedError again."""
+    global _fvd_weights
+    _fvd_weights = None
+    _fvd_on_device.clear()
+
+
+def _fvd_trunk(device):
+    """What ops.fvd_features reads on a GPU: the folded weights packed [kt, kh, kw, Ci, Co] and the biases as float32 tensors, and the layer
+    table over four buffers (0: the staged clips; two that the maps alternate between; one for what a block's 1x1x1 units and its pool
+    hand to the next unit). A block's branches write their channel ranges of ONE map: no cat."""
+    from . import ops
+    params, rows = [], []
+
+    def conv(name, src, dst, k, s, coff, ld):
+        w, b = _fvd_weights[name]
+        rows.append((ops.FVD_CONV, src, dst, w.shape[1], w.shape[0], k, s, True, coff, w.shape[0] if ld is None else ld, len(params)))
+        params.extend([ops.conv3d_pack(w.float()).to(device), b.float().to(device)])
+
+    cur, c = 0, _fvd_weights["Conv3d_1a_7x7"][0].shape[1]
+    for step in FVD_SEQUENCE:
+        dst = 2 if cur == 1 else 1
+        if step[0] == "unit":
+            conv(step[1], cur, dst, step[2], step[3], 0, None)
+            c = _fvd_weights[step[1]][0].shape[0]
+        elif step[0] == "pool":
+            rows.append((ops.FVD_POOL, cur, dst, c, c, step[1], step[2], False, 0, c, 0))
+        else:
+            name = step[1]
+            co = {b: _fvd_weights[f"{name}.{b}"][0].shape[0] for b, _ in FVD_BRANCHES}
+            ld, one, three = co["b0"] + co["b1b"] + co["b2b"] + co["b3b"], (1, 1, 1), (3, 3, 3)
+            conv(f"{name}.b0", cur, dst, one, one, 0, ld)
+            conv(f"{name}.b1a", cur, 3, one, one, 0, None)
+            conv(f"{name}.b1b", 3, dst, three, one, co["b0"], ld)
+            conv(f"{name}.b2a", cur, 3, one, one, 0, None)
+            conv(f"{name}.b2b", 3, dst, three, one, co["b0"] + co["b1b"], ld)
+            rows.append((ops.FVD_POOL, cur, 3, c, c, three, one, False, 0, c, 0))
+            conv(f"{name}.b3b", 3, dst, one, one, co["b0"] + co["b1b"] + co["b2b"], ld)
+            c = ld
+        cur = dst
+    w, b = _fvd_weights["logits"]
+    rows.append((ops.FVD_HEAD, cur, cur, c, w.shape[0], (1, 1, 1), (1, 1, 1), False, 0, w.shape[0], len(params)))
+    params.extend([w.float().to(device), b.float().to(device)])
+    table, n_rows = ops.fvd_table(rows)
+    return {"table": table, "n_rows": n_rows, "params": params, "rows": rows, "ci": _fvd_weights["Conv3d_1a_7x7"][0].shape[1], "n_features": w.shape[0]}
+
+
+def fvd_weights(device="cpu", dtype=torch.float32):
+    """The registered network on `device`, built once per device: on a GPU what ops.fvd_features takes (float32, weights packed for the
+    kernel, the layer table); on the host {unit: (folded weight, bias), "logits": (weight [F, C], bias)} in `dtype`."""
+    if _fvd_weights is None:
+        raise NotImplementedError(f"{FVD_NAME} needs pretrained weights that this build does not ship (register_fvd_weights)")
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:   # "cuda" and "cuda:0" are one device: one pack
+        dev = torch.device("cuda", torch.cuda.current_device())
+    slot = (str(dev), dtype if dev.type == "cpu" else torch.float32)
+    if slot not in _fvd_on_device:
+        _fvd_on_device[slot] = {k: (w.to(dtype), b.to(dtype)) for k, (w, b) in _fvd_weights.items()} if dev.type == "cpu" else _fvd_trunk(dev)
+    return _fvd_on_device[slot]
+
+
+def fvd_in_channels():
+    """The channel count the registered stem takes (2 or 3)."""
+    fvd_weights()
+    return _fvd_weights["Conv3d_1a_7x7"][0].shape[1]
+
+
+def same_pad(size, k, s):
+    """(front, back, out) of one axis: the reference's "SAME" rule (Unit3D.compute_pad, MaxPool3dSamePadding.compute_pad)."""
+    pad = max(k - s, 0) if size % s == 0 else max(k - size % s, 0)
+    return pad // 2, pad - pad // 2, -(-size // s)
+
+
+def _fvd_pad(x, k, s):
+    pads = [same_pad(n, kk, ss) for n, kk, ss in zip(x.shape[2:], k, s)]
+    return F.pad(x, (pads[2][0], pads[2][1], pads[1][0], pads[1][1], pads[0][0], pads[0][1]))
+
+
+def _fvd_unit_host(x, wb, k, s=(1, 1, 1)):
+    return F.relu(F.conv3d(_fvd_pad(x, k, s), wb[0], wb[1], stride=s))
+
+
+def _fvd_pool_host(x, k, s):
+    return F.max_pool3d(_fvd_pad(x, k, s), k, s)   # the padding is ZERO, and part of the pooled map
+
+
+def _fvd_block_host(x, weights, name):
+    one, three = (1, 1, 1), (3, 3, 3)
+    u = lambda b, z: _fvd_unit_host(z, weights[f"{name}.{b}"], dict(FVD_BRANCHES)[b] == 1 and one or three)
+    return torch.cat([u("b0", x), u("b1b", u("b1a", x)), u("b2b", u("b2a", x)), u("b3b", _fvd_pool_host(x, three, one))], dim=1)
+
+
+def _fvd_features_host(clips, weights):
+    """[N, n_features] on host tensors: the trunk in plain torch on the folded weights, in the clips' dtype. clips: [N, T, C, h, w]."""
+    n, t, c, h, w = clips.shape
+    x = clips.reshape(n * t, c, h, w)
+    if (h, w) != (FVD_SIDE, FVD_SIDE):
+        x = F.interpolate(x, size=(FVD_SIDE, FVD_SIDE), mode="bilinear", align_corners=False, antialias=False)
+    x = x.reshape(n, t, c, FVD_SIDE, FVD_SIDE).permute(0, 2, 1, 3, 4)
+    for step in FVD_SEQUENCE:
+        if step[0] == "unit":
+            x = _fvd_unit_host(x, weights[step[1]], step[2], step[3])
+        elif step[0] == "pool":
+            x = _fvd_pool_host(x, step[1], step[2])
+        else:
+            x = _fvd_block_host(x, weights, step[1])
+    if tuple(x.shape[2:]) != (2, 7, 7):
+        raise ValueError(f"{FVD_NAME}: the final map must be 2x7x7 (got {tuple(x.shape[2:])}): clips of {FVD_MIN_T} .. {FVD_MAX_T} frames give it")
+    return x.mean(dim=(2, 3, 4)) @ weights["logits"][0].t() + weights["logits"][1]
+
+
+def frechet_distance_host(pred, target):
+    """A float64 scalar: the reference's calculate_2_wasserstein_dist on two [b, n] tables, restated. With E the centred tables and
+    fact = 1 / (b - 1) (1 for b = 1): fact sum Ep^2 + fact sum Et^2 - 2 sum_i sqrt(sigma_i^2 + 1e-15) + |mu_p - mu_t|^2, sigma_i the singular
+    values of the b x b matrix fact Ep Et^T (the reference's M = M_l M_l^T is symmetric positive semidefinite with eigenvalues sigma_i^2).
+    The n x n covariances are never formed."""
+    if pred.ndim != 2 or pred.shape != target.shape:
+        raise ValueError("Expecting equal shapes for pred and target!")
+    p, t = pred.double(), target.double()
+    b = p.shape[0]
+    fact = 1.0 if b < 2 else 1.0 / (b - 1)
+    mp, mt = p.mean(dim=0), t.mean(dim=0)
+    ep, et = p - mp, t - mt
+    sigma = torch.linalg.svdvals(fact * (ep @ et.t()))
+    return fact * ep.square().sum() + fact * et.square().sum() - 2.0 * torch.sqrt(sigma.square() + 1e-15).sum() + (mp - mt).square().sum()
+
+
+def fvd_chunks(num_frames):
+    """The chunks FVD runs on for a clip length, [(first frame, length), ...], or None below 9 frames (fvd.py: calculate_n_chunks, then
+    torch.chunk's sizes). Up to 16 frames: one chunk. Beyond: the number of chunks of the LAST chunk length L in 16 .. 9 whose remainder
+    num_frames % L is at least 9 (num_frames // L + 1 chunks, none dropped). Where no length leaves such a remainder (17, 18 and 112 frames up
+    to 128) the reference divides by a tuple and raises TypeError; this restates its evident intent: the chunk length with the largest
+    remainder (the last of them among equals, as its sort orders them), num_frames // L + 1 chunks, the last one dropped."""
+    if num_frames < FVD_MIN_T:
+        return None
+    n_chunks, drop_last = 1, False
+    if num_frames > FVD_MAX_T:
+        lengths = range(FVD_MAX_T, FVD_MIN_T - 1, -1)
+        fitting = [l for l in lengths if num_frames % l >= FVD_MIN_T]
+        if fitting:
+            n_chunks = num_frames // fitting[-1] + 1
+        else:
+            best = sorted(((l, num_frames % l) for l in lengths), key=lambda lm: lm[1])[-1][0]
+            n_chunks, drop_last = num_frames // best + 1, True
+    size = -(-num_frames // n_chunks)                                   # torch.chunk: pieces of ceil(T / n), the last one shorter
+    pieces = [(s, min(size, num_frames - s)) for s in range(0, num_frames, size)]
+    return pieces[:n_chunks - 1 if drop_last else n_chunks]
+
+
+class FrechetVideoDistance(VPMeasure):
+    """fvd.py's measure on an I3D network the user registered (register_fvd_weights); without one the constructor raises NotImplementedError,
+    as it always did. Not a mean over frames: prediction and target clips go through the trunk as ONE batch of 2B, the distance is taken
+    between the two sets of B feature vectors, per chunk of 9 .. 16 frames (fvd_chunks), and the chunks' distances are averaged. Clips below
+    9 frames give None. Forward only: a prediction that requires grad under grad mode raises NotImplementedError, on either device."""
+    NAME = FVD_NAME
     REFERENCE = "https://arxiv.org/abs/1812.01717"
+    TABLE = None   # no per-frame table: the providers compute it beside the tables
+
+    def __init__(self, device):
+        fvd_weights()   # NotImplementedError until weights are registered
+        super().__init__(device)
+
+    def forward(self, pred, target):
+        if pred.shape != target.shape:
+            raise ValueError("FrechetVideoDistance: vid shapes not equal!")
+        if pred.ndim != 5:
+            raise ValueError(f"{self.NAME} expects 5-D inputs!")
+        chunks = fvd_chunks(pred.shape[1])
+        if chunks is None:
+            return None
+        if pred.shape[2] != fvd_in_channels():
+            raise ValueError(f"{self.NAME}: the frames have {pred.shape[2]} channels, the registered network takes {fvd_in_channels()}")
+        b = pred.shape[0]
+        values = []
+        if torch.is_grad_enabled() and pred.requires_grad:   # on either device: a term without a gradient must not pass for a loss
+            raise NotImplementedError(f"{self.NAME}: the backward is not implemented in this build (forward only): evaluate it under "
+                                      f"torch.no_grad() or on detached tensors")
+        if pred.is_cuda:
+            from . import ops
+            trunk = fvd_weights(pred.device)
+            for first, length in chunks:
+                feats = ops.fvd_features(pred[:, first:first + length].detach(), trunk, target[:, first:first + length].detach())
+                values.append(ops.frechet_distance(feats[:b], feats[b:]))
+        else:
+            weights = fvd_weights("cpu", pred.dtype)
+            with torch.no_grad():
+                for first, length in chunks:
+                    feats = _fvd_features_host(torch.cat([pred[:, first:first + length], target[:, first:first + length]]), weights)
+                    values.append(frechet_distance_host(feats[:b], feats[b:]))
+        return (sum(values) / len(values)).float()
 
 
 LOSS_CLASSES = {"mse": MSE, "l1": L1, "smooth_l1": SmoothL1, "lpips": LPIPS, "ssim": SSIM, "psnr": PSNR, "fvd": FrechetVideoDistance}
@@ -345,7 +620,8 @@ class PredictionLossProvider:
     """config: {"device": ..., "losses_and_scales": {key: scale}} over any mix of "mse", "l1", "smooth_l1", "psnr" and "ssim"
     (loss_provider.py). All pixel-wise terms together cost one sums pass and one gradient pass, SSIM one of each. "lpips" joins them once
     weights are registered: on the GPU as a value only (a prediction that requires grad raises) unless they were registered with
-    differentiable=True, which makes it a loss term with a HIP backward."""
+    differentiable=True, which makes it a loss term with a HIP backward. "fvd" joins them once its weights are registered, as a value for
+    inputs without grad (forward only); clips below 9 frames have none and add no term."""
 
     def __init__(self, config: dict):
         self.device = config["device"]
@@ -362,9 +638,12 @@ class PredictionLossProvider:
         if list(self.losses) == ["mse"]:   # the fused value + gradient kernel
             values = {"mse": self.losses["mse"][0](pred, target)}
         else:
-            frames = _frame_values({k: m for k, (m, _) in self.losses.items()}, pred, target)
+            frames = _frame_values({k: m for k, (m, _) in self.losses.items() if m.TABLE is not None}, pred, target)
             values = {k: v.mean(dim=1).mean(dim=0) for k, v in frames.items()}
+            values.update({k: m(pred, target) for k, (m, _) in self.losses.items() if m.TABLE is None})   # FVD: not a per-frame table
         for key, (m, scale) in self.losses.items():
+            if values[key] is None:   # FVD below 9 frames: no value, no term
+                continue
             total = total + scale * values[key]
             display[key] = m.to_display(values[key])
         return display, total
@@ -391,15 +670,30 @@ class PredictionMetricProvider:
         if pred.shape != target.shape:
             raise ValueError("Output images and target images are of different shape!")
         frames = frames or pred.shape[1]
-        if not self.metrics:
-            return [{} for _ in range(frames if all_frame_cnts else 1)]
-        values = _frame_values(self.metrics, pred[:, :frames], target[:, :frames])
-        table = torch.stack([values[k] for k in self.metrics])                       # [K, B, frames]
-        if all_frame_cnts:   # horizon n = mean over b of the mean over the first n frames
-            counts = torch.arange(1, frames + 1, device=table.device, dtype=table.dtype)
-            table = (table.cumsum(dim=2) / counts).mean(dim=1)                       # [K, frames]
-        else:
-            table = table.mean(dim=2).mean(dim=1, keepdim=True)                      # [K, 1]
-        host = table.cpu().tolist()                                                  # the one transfer
-        return [{f"{k} ({'↑' if m.BIGGER_IS_BETTER else '↓'})": m.to_display(host[i][n]) for i, (k, m) in enumerate(self.metrics.items())}
-                for n in range(len(host[0]))]
+        horizons = list(range(1, frames + 1)) if all_frame_cnts else [frames]
+        framewise = {k: m for k, m in self.metrics.items() if m.TABLE is not None}
+        out = [{} for _ in horizons]
+        if framewise:
+            values = _frame_values(framewise, pred[:, :frames], target[:, :frames])
+            table = torch.stack([values[k] for k in framewise])                      # [K, B, frames]
+            if all_frame_cnts:   # horizon n = mean over b of the mean over the first n frames
+                counts = torch.arange(1, frames + 1, device=table.device, dtype=table.dtype)
+                table = (table.cumsum(dim=2) / counts).mean(dim=1)                   # [K, frames]
+            else:
+                table = table.mean(dim=2).mean(dim=1, keepdim=True)                  # [K, 1]
+            host = table.cpu().tolist()                                              # the one transfer
+            out = [{f"{k} ({'↑' if m.BIGGER_IS_BETTER else '↓'})": m.to_display(host[i][n]) for i, (k, m) in enumerate(framewise.items())}
+                   for n in range(len(host[0]))]
+        # FVD is no per-frame table: one value per requested horizon, present in that horizon's dict only from 9 frames on
+        for k, m in self.metrics.items():
+            if m.TABLE is not None:
+                continue
+            if pred.shape[2] != fvd_in_channels():   # (the reference drops it for frames its network cannot take)
+                warnings.warn(f"metric {k!r} dropped: the frames have {pred.shape[2]} channels, the registered network takes {fvd_in_channels()}")
+                continue
+            computed = [(i, m(pred[:, :n], target[:, :n])) for i, n in enumerate(horizons) if n >= FVD_MIN_T]
+            if computed:
+                host = torch.stack([v.double() for _, v in computed]).cpu().tolist()
+                for (i, _), v in zip(computed, host):
+                    out[i][f"{k} ({'↑' if m.BIGGER_IS_BETTER else '↓'})"] = m.to_display(v)
+        return out

@@ -2026,3 +2026,159 @@ def vis_compose(src, tiles, canvas_shape, lo=0.0, hi=1.0, background=255, *, max
         check(_lib.lib().vpx_vis_compose(ptr(xc), S, T, C, h, w, float(lo), float(hi), ptr(dev), int(dev.shape[0]), bmax, ptr(canvas), F, Hc, Wc,
                                          fill, stream()), "vpx_vis_compose")
     return canvas
+
+
+# ---- Frechet Video Distance on an Inception-I3D trunk (csrc/fvd.hip); maps are channels-last [N, T, H, W, C]; forward only ----------------
+FVD_SIDE = 224       # the I3D input: frames are resized to it
+FVD_MAX_B = 256      # the cap on feature vectors per set in frechet_distance
+FVD_ROW, FVD_CONV, FVD_POOL, FVD_HEAD = 16, 0, 1, 2   # include/vpx.h: VPX_FVD_ROW, VPX_FVD_CONV / _POOL / _HEAD
+
+
+def same_padding(size, k, s):
+    """(front, back, out) of one axis under the reference's "SAME" rule: pad = max(k - s, 0) if size % s == 0 else max(k - size % s, 0),
+    front = pad // 2, output size ceil(size / s). Answered by the library (host only), so that Python and the kernels share one rule."""
+    front, out = ctypes.c_int(), ctypes.c_int()
+    check(_lib.lib().vpx_same_padding(int(size), int(k), int(s), ctypes.byref(front), ctypes.byref(out)), "vpx_same_padding")
+    back = max((out.value - 1) * s + k - size, 0) - front.value   # what the library's front and output size leave behind the map
+    return front.value, back, out.value
+
+
+def _fvd_operand(t, what, name, shape=None):
+    require_gpu(t, what)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t.contiguous()
+
+
+def _triple(v, what, name):
+    v = tuple(int(i) for i in ((v,) * 3 if isinstance(v, int) else v))
+    if len(v) != 3 or min(v) < 1:
+        raise ValueError(f"{what}: {name} must be three sizes >= 1 (got {v})")
+    return v
+
+
+def conv3d_pack(w):
+    """[kt, kh, kw, Ci, Co] contiguous: the layout vpx_conv3d_same reads, from the reference's [Co, Ci, kt, kh, kw]."""
+    return w.permute(2, 3, 4, 1, 0).contiguous()
+
+
+def conv3d_same(x, w, bias, stride=(1, 1, 1), relu=False, out=None, channel_offset=0, packed=False):
+    """Unit3D without its BatchNorm (fold it into w and bias): ReLU?(conv3d(zero-pad "SAME"(x), w) + bias) of a channels-last map
+    x [N, T, H, W, Ci]. w: [Co, Ci, kt, kh, kw], packed here per call, or with packed=True the result of conv3d_pack (the trunk packs
+    once, at registration). Returns [N, To, Ho, Wo, Co]; with `out` [N, To, Ho, Wo, ld] only its channels channel_offset ..
+    channel_offset + Co - 1 are written. Exact fp32 operands."""
+    what = "conv3d_same"
+    if x.ndim != 5 or w.ndim != 5:
+        raise ValueError(f"{what}: expected a channels-last map [N, T, H, W, Ci] and weights with five axes")
+    x = _fvd_operand(x, what, "x")
+    N, T, H, W, Ci = x.shape
+    wp = _fvd_operand(w, what, "w") if packed else conv3d_pack(_fvd_operand(w, what, "w"))
+    kt, kh, kw, wci, Co = wp.shape
+    if wci != Ci:
+        raise ValueError(f"{what}: w has {wci} input channels, x has {Ci}")
+    bias = _fvd_operand(bias, what, "bias", (Co,))
+    st, sh, sw = _triple(stride, what, "stride")
+    To, Ho, Wo = same_padding(T, kt, st)[2], same_padding(H, kh, sh)[2], same_padding(W, kw, sw)[2]
+    if out is None:
+        out = torch.empty(N, To, Ho, Wo, Co, device=x.device)
+        channel_offset = 0
+    else:
+        require_gpu(out, what)
+        if out.ndim != 5 or tuple(out.shape[:4]) != (N, To, Ho, Wo) or not out.is_contiguous() or out.device != x.device:
+            raise ValueError(f"{what}: out must be a contiguous [N, To, Ho, Wo, ld] = [{N}, {To}, {Ho}, {Wo}, ld] map on x's device (got {tuple(out.shape)})")
+        if channel_offset < 0 or channel_offset + Co > out.shape[4]:
+            raise ValueError(f"{what}: channels {channel_offset} .. {channel_offset + Co - 1} do not fit out's {out.shape[4]}")
+    with torch.cuda.device(x.device):
+        check(_lib.lib().vpx_conv3d_same(ptr(x), ptr(wp), ptr(bias), ptr(out), N, T, H, W, Ci, Co, kt, kh, kw, st, sh, sw, int(bool(relu)), out.shape[4],
+                                         int(channel_offset), stream()), "vpx_conv3d_same")
+    return out
+
+
+def maxpool3d_same(x, kernel, stride):
+    """[N, To, Ho, Wo, C]: max-pool of a channels-last map [N, T, H, W, C] over its ZERO-padded extension ("SAME" padding: the reference
+    pads with zeros before it pools, so a window on the border never returns less than 0)."""
+    what = "maxpool3d_same"
+    if x.ndim != 5:
+        raise ValueError(f"{what}: expected a channels-last map [N, T, H, W, C]")
+    x = _fvd_operand(x, what, "x")
+    N, T, H, W, C = x.shape
+    (kt, kh, kw), (st, sh, sw) = _triple(kernel, what, "kernel"), _triple(stride, what, "stride")
+    y = torch.empty(N, same_padding(T, kt, st)[2], same_padding(H, kh, sh)[2], same_padding(W, kw, sw)[2], C, device=x.device)
+    with torch.cuda.device(x.device):
+        check(_lib.lib().vpx_maxpool3d_same(ptr(x), ptr(y), N, T, H, W, C, kt, kh, kw, st, sh, sw, stream()), "vpx_maxpool3d_same")
+    return y
+
+
+def fvd_head(x, w, bias):
+    """[N, n_features] float32: the mean over the 2x7x7 positions of a channels-last map [N, 2, 7, 7, C], then the logits layer
+    w [n_features, C] (or [n_features, C, 1, 1, 1]) with bias. Any other map is refused."""
+    what = "fvd_head"
+    if x.ndim != 5:
+        raise ValueError(f"{what}: expected a channels-last map [N, 2, 7, 7, C]")
+    x = _fvd_operand(x, what, "x")
+    N, T, H, W, C = x.shape
+    if w.ndim == 5 and tuple(w.shape[2:]) == (1, 1, 1):
+        w = w.reshape(w.shape[0], w.shape[1])
+    w = _fvd_operand(w, what, "w", (w.shape[0], C))
+    bias = _fvd_operand(bias, what, "bias", (w.shape[0],))
+    out = torch.empty(N, w.shape[0], device=x.device)
+    with torch.cuda.device(x.device):
+        check(_lib.lib().vpx_fvd_head(ptr(x), ptr(w), ptr(bias), ptr(out), N, T, H, W, C, w.shape[0], stream()), "vpx_fvd_head")
+    return out
+
+
+def fvd_table(rows):
+    """(C int array, n_rows) of layer-table rows (op, src, dst, Ci, Co, kernel, stride, relu, coff, ld, param): what vpx_fvd_features walks."""
+    flat = []
+    for op, src, dst, Ci, Co, k, s, relu, coff, ld, param in rows:
+        flat += [op, src, dst, Ci, Co, *k, *s, int(relu), coff, ld, param, 0]
+    assert len(flat) == FVD_ROW * len(rows)
+    return (ctypes.c_int * len(flat))(*flat), len(rows)
+
+
+def fvd_features(x, trunk, x1=None):
+    """[N (+ N1), n_features] float32: the I3D logits of the clips x [N, T, C, h, w] (and of x1 behind them, as one batch), values as they
+    are. The frames are resized to 224x224 (ops.frames_adapt's resize, bit for bit) inside the call. trunk: what
+    measure.fvd_weights(device) returns: {"table", "n_rows", "params", "ci", "n_features"}. T must lead to a final 2x7x7 map: 9 .. 16."""
+    what = "fvd_features"
+    if x.ndim != 5 or (x1 is not None and x1.shape[1:] != x.shape[1:]):
+        raise ValueError(f"{what}: expected clips [N, T, C, h, w] of one shape")
+    if needs_grad(x, x1):
+        raise NotImplementedError(f"{what}: the backward of FVD is not implemented in this build (forward only): evaluate it under torch.no_grad() "
+                                  f"or on detached tensors")
+    x = _fvd_operand(x, what, "x")
+    x1 = None if x1 is None else _fvd_operand(x1, what, "x1")
+    n0, T, C, h, w = x.shape
+    n1 = 0 if x1 is None else x1.shape[0]
+    if C != trunk["ci"]:
+        raise ValueError(f"{what}: the frames have {C} channels, the registered stem takes {trunk['ci']}")
+    if any(p.device != x.device for p in trunk["params"]) or (x1 is not None and x1.device != x.device):
+        raise ValueError(f"{what}: clips and weights must live on one device")
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        ws, ws_bytes = workspace(x.device, L.vpx_fvd_features_workspace_bytes, n0 + n1, T, C, h, w, trunk["table"], trunk["n_rows"], unsupported=b"beyond")
+        out = torch.empty(n0 + n1, trunk["n_features"], device=x.device)
+        check(L.vpx_fvd_features(ptr(x), ptr(x1), n0, n1, T, C, h, w, trunk["table"], trunk["n_rows"], ptr_array(trunk["params"]), len(trunk["params"]),
+                                 ptr(out), ptr(ws), ws_bytes, stream()), "vpx_fvd_features")
+    return out
+
+
+def frechet_distance(pred, target):
+    """A float64 scalar on the device: fact sum Ep^2 + fact sum Et^2 - 2 sum_i sqrt(sigma_i^2 + 1e-15) + |mu_p - mu_t|^2 of two feature
+    tables [b, n] float32 (the reference's calculate_2_wasserstein_dist restated: sigma_i the singular values of the b x b matrix
+    fact Ep Et^T, by a Jacobi iteration of a fixed maximum of sweeps). b <= FVD_MAX_B: more raises VpxError."""
+    what = "frechet_distance"
+    if pred.ndim != 2 or pred.shape != target.shape:
+        raise ValueError(f"{what}: expected two feature tables [b, n] of one shape")
+    pred, target = _fvd_operand(pred, what, "pred"), _fvd_operand(target, what, "target")
+    b, n = pred.shape
+    if b > FVD_MAX_B:
+        raise VpxError(f"{what}: {b} feature vectors per set, this build supports at most {FVD_MAX_B}")
+    if target.device != pred.device:
+        raise ValueError(f"{what}: both tables must live on one device")
+    L = _lib.lib()
+    with torch.cuda.device(pred.device):
+        ws, ws_bytes = workspace(pred.device, L.vpx_frechet_distance_workspace_bytes, b, n)
+        out = torch.empty((), device=pred.device, dtype=torch.float64)
+        check(L.vpx_frechet_distance(ptr(pred), ptr(target), b, n, ptr(out), ptr(ws), ws_bytes, stream()), "vpx_frechet_distance")
+    return out

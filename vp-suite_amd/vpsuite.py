@@ -20,6 +20,8 @@ DEFAULT_RUN_CONFIG is the reference's DefaultRunConfig (defaults.py:37-64) key f
   * metrics = ["mse", "psnr", "ssim"]: "lpips" needs pretrained weights this build does not ship, so it is not a default. After
     measure.register_lpips_weights(...) (AlexNet weights the user brings; nothing is downloaded) the reference's own list,
     metrics=["mse", "lpips", "psnr", "ssim"], runs in train() and test(); on one-channel data it fails with the measure's ValueError.
+    "fvd" likewise joins a metrics list after measure.register_fvd_weights(...) (an I3D network the user brings); it has a value from 9
+    predicted frames on and is dropped with a warning for frames whose channel count the registered stem does not take.
   * One added key, test_batch_size = 1: test() may evaluate several datapoints per launch. Per-horizon means stay means over
     DATAPOINTS (batch means weighted by batch size), so a ragged last batch changes nothing.
   * One added key, flat_adam = False: True trains with train.FlatAdam (one HIP kernel over flat buckets) instead of torch.optim.Adam.
@@ -457,9 +459,9 @@ class VPSuite:
             # -> means over all datapoints, the metrics and prediction horizons kept apart
             total = sum(n for n, _ in model_metrics_per_batch)
             frame_range = range(len(model_metrics_per_batch[0][1]))
-            metric_keys = model_metrics_per_batch[0][1][0].keys()
-            mean_metric_dicts = [{key: float(sum(n * dicts[frame][key] for n, dicts in model_metrics_per_batch) / total) for key in metric_keys}
-                                 for frame in frame_range]
+            # (the keys of each horizon's own dict: "fvd" has a value from 9 frames on only)
+            mean_metric_dicts = [{key: float(sum(n * dicts[frame][key] for n, dicts in model_metrics_per_batch) / total)
+                                  for key in model_metrics_per_batch[0][1][frame].keys()} for frame in frame_range]
             name = model.NAME if model.NAME not in results else f"{model.NAME} #{i}"
             results[name] = mean_metric_dicts
             print(f"\n{model.NAME} (path: {model.model_dir}, {test_mode} test): ")
