@@ -454,6 +454,82 @@ def test_trajgru_sequence(L):
     assert L.vpx_trajgru_workspace_bytes(ctypes.byref(d)) == 0
 
 
+def test_trajgru_refuses_short_buffers_and_accepts_exact_ones(L):
+    """vpx_trajgru_seq_fwd / _bwd, every i2h kernel size, operand mode and operand form, with and without the fixed-point scatter's slot in
+    use: the sizes the queries return (each direction's own carve, measured) are accepted at an aligned and at an odd base; a workspace 256
+    bytes short, and (saving descriptor) a reserve one byte short, are refused with VPX_ERR_WORKSPACE. Only a saving descriptor has a reserve."""
+    from vp_suite_amd._lib import TrajGRUDesc
+    descs = [(3, 8, 1, 1, 3), (6, 12, 9, 11, 5), (16, 64, 64, 64, 13)]
+    params = (ctypes.c_void_p * 10)(*[0x200000000000 + i * (1 << 32) for i in range(10)])
+    dparams = (ctypes.c_void_p * 10)(*[0x300000000000 + i * (1 << 32) for i in range(10)])
+    for det in (0, 1):
+        L.vpx_set_deterministic(det)
+        for (Cin, C, H, W, nl), k, B, T, prec, save in itertools.product(descs, (1, 3, 5, 7), (1, 2), (1, 4), (0, 1, 2), (0, 1)):
+            d = TrajGRUDesc(B, T, Cin, C, H, W, nl, k, prec, _lib.FLAG_SAVE_FOR_BWD if save else 0, 0.2)
+            nb, rs = L.vpx_trajgru_workspace_bytes(ctypes.byref(d)), L.vpx_trajgru_reserve_bytes(ctypes.byref(d))
+            assert nb > 256 and (rs > 0) == bool(save)
+            for (x, h0) in ((_fake(1), _fake(2)), (None, _fake(2)), (_fake(1), None)):
+                def fwd(rs_, base, nb_):
+                    return L.vpx_trajgru_seq_fwd(ctypes.byref(d), x, h0, params, _fake(3), _fake(4), rs_, ctypes.c_void_p(base), nb_, None)
+
+                def bwd(rs_, base, nb_):
+                    return L.vpx_trajgru_seq_bwd(ctypes.byref(d), x, h0, params, _fake(3), _fake(4), rs_, _fake(5), _fake(6), None if x is None else _fake(7),
+                                                 None if h0 is None else _fake(8), dparams, ctypes.c_void_p(base), nb_, None)
+                tag = f"trajgru {(Cin, C, H, W, nl)} k={k} B={B} T={T} prec={prec} save={save} det={det} x={x is not None} h0={h0 is not None}"
+                for call in ((fwd, bwd) if save else (fwd,)):
+                    assert call(rs, WS_BASE, nb - 256) == E_WS, (tag, call.__name__)
+                    if save:
+                        assert call(rs - 1, WS_BASE, nb) == E_WS, (tag, call.__name__, "reserve")
+                    for base in (WS_BASE, WS_BASE_ODD):
+                        _ok(L, call(rs, base, nb), f"{tag} {call.__name__} base={base:#x}", allow_unsupported=False)
+
+
+def test_acstlstm_refuses_short_buffers_and_accepts_exact_ones(L):
+    """vpx_acstlstm_step_fwd / _bwd, with and without LayerNorm, every operand mode, all gradients wanted and the frozen pattern of
+    `test_acstlstm_step`: the sizes the queries return (each direction's own carve, measured) are accepted at an aligned and at an odd base; a
+    workspace 256 bytes short, and (saving descriptor) a reserve one byte short, are refused with VPX_ERR_WORKSPACE. Only a saving
+    descriptor has a reserve. Each call is handed its own descriptor's sizes: no order between the saving and the non-saving query is
+    assumed. They do differ where there is no LayerNorm — the non-saving forward takes conv_h / conv_a / mem from its workspace and pays for
+    no backward, the saving one takes them from the reserve and is sized for the backward's carve; a formula that ignores the flag (as the
+    hand count did) returns one number for both."""
+    from vp_suite_amd._lib import ACSTLSTMDesc
+    descs = [(1, 4, 7, 5, 1), (3, 6, 9, 11, 3), (12, 20, 33, 17, 7)]
+    params = (ctypes.c_void_p * 12)(*[0x200000000000 + i * (1 << 32) for i in range(12)])
+    L.vpx_set_deterministic(0)
+    for (Cin, Ch, H, W, k), B, ln, prec in itertools.product(descs, (1, 8), (0, 1), (0, 1, 2)):
+        lnp = (ctypes.c_void_p * 10)(*[0x280000000000 + i * (1 << 32) for i in range(10)]) if ln else None
+        sizes = {}
+        for save in (0, 1):
+            d = ACSTLSTMDesc(B, Cin, Ch, H, W, k, ln, prec, _lib.FLAG_SAVE_FOR_BWD if save else 0, 1.0)
+            nb, rs = L.vpx_acstlstm_workspace_bytes(ctypes.byref(d)), L.vpx_acstlstm_reserve_bytes(ctypes.byref(d))
+            assert nb > 256 and (rs > 0) == bool(save)
+            sizes[save] = nb
+
+            def fwd(rs_, base, nb_):
+                return L.vpx_acstlstm_step_fwd(ctypes.byref(d), *[_fake(i) for i in range(1, 6)], params, lnp, *[_fake(i) for i in range(6, 11)], _fake(11), rs_,
+                                               ctypes.c_void_p(base), nb_, None)
+
+            def bwd(frozen):
+                dparams = (ctypes.c_void_p * 12)(*[None if (frozen and i % 3 == 0) else 0x300000000000 + i * (1 << 32) for i in range(12)])
+                dln = (ctypes.c_void_p * 10)(*[None if (frozen and i % 4 == 1) else 0x380000000000 + i * (1 << 32) for i in range(10)]) if ln else None
+                douts = [_fake(12)] + [None if frozen else _fake(13 + i) for i in range(4)]
+                dins = [None if (frozen and i in (0, 3)) else _fake(20 + i) for i in range(5)]
+
+                def call(rs_, base, nb_):
+                    return L.vpx_acstlstm_step_bwd(ctypes.byref(d), *[_fake(i) for i in range(1, 6)], params, lnp, _fake(11), rs_, *douts, *dins, dparams, dln,
+                                                   ctypes.c_void_p(base), nb_, None)
+                return call
+            tag = f"acstlstm {(Cin, Ch, H, W, k)} B={B} ln={ln} prec={prec} save={save}"
+            for name, call in ((("fwd", fwd), ("bwd", bwd(False)), ("bwd frozen", bwd(True))) if save else (("fwd", fwd),)):
+                assert call(rs, WS_BASE, nb - 256) == E_WS, (tag, name)
+                if save:
+                    assert call(rs - 1, WS_BASE, nb) == E_WS, (tag, name, "reserve")
+                for base in (WS_BASE, WS_BASE_ODD):
+                    _ok(L, call(rs, base, nb), f"{tag} {name} base={base:#x}", allow_unsupported=False)
+        if not ln:
+            assert sizes[0] != sizes[1], (Cin, Ch, H, W, k, B, prec, sizes)
+
+
 def test_acstlstm_step(L):
     """vpx_acstlstm_step_fwd / _bwd (action-conditional ST-LSTM cell, predrnn.py:86-169): with / without LayerNorm, every operand mode, odd
     map sizes, frozen parameters and unwanted data gradients."""

@@ -131,20 +131,44 @@ static const char* acs_check(const vpx_acstlstm_desc* d) {
     return nullptr;
 }
 constexpr int ACS_LN_MULT[5] = {7, 4, 4, 3, 1};   // channels / Ch of conv_x, conv_h, conv_a, conv_m, conv_o
-constexpr int ACS_LN_PLANES = 19;
+// The reserve a saving forward fills and the backward reads: the conv_h / conv_a outputs, the gates, mem = (c_new | m_new), the output gate
+// and tanh(conv_last); LayerNorm: the five normalised outputs and 5 x stats[B][2] (st). A descriptor that does not save has none.
+struct ACSReserve { float *hc, *ac, *save, *mem, *o, *tl, *xhat[5], *st; };
+template <class WS>
+static void acs_carve_reserve(WS& rs, const vpx_acstlstm_desc* d, const ACS& s, ACSReserve& R) {
+    if (!(d->flags & VPX_FLAG_SAVE_FOR_BWD)) return;
+    R.hc = rs.take(4 * s.n_state); R.ac = rs.take(4 * s.n_state); R.save = rs.take(6 * s.n_state); R.mem = rs.take(2 * s.n_state);
+    R.o = rs.take(s.n_state); R.tl = rs.take(s.n_state);
+    if (!d->layer_norm) return;
+    for (int i = 0; i < 5; ++i) R.xhat[i] = rs.take(ACS_LN_MULT[i] * s.n_state);
+    R.st = rs.take((size_t)10 * s.B);
+}
 
-struct ACSReserve { float *hc, *ac, *save, *mem, *o, *tl, *xhat[5], *st[5]; };
-static ACSReserve acs_carve_reserve(void* reserve, const ACS& s, bool ln) {
-    char* r = (char*)reserve;
-    const size_t plane = align256(s.n_state * 4);
-    ACSReserve R{};
-    auto take = [&](int planes) { float* p = (float*)r; r += planes * plane; return p; };
-    R.hc = take(4); R.ac = take(4); R.save = take(6); R.mem = take(2); R.o = take(1); R.tl = take(1);
-    if (ln) {
-        for (int i = 0; i < 5; ++i) R.xhat[i] = take(ACS_LN_MULT[i]);
-        for (int i = 0; i < 5; ++i) R.st[i] = (float*)r + 2 * s.B * i;
+// ---- the workspaces: each direction's slots in the order they are taken (see CarveMeasure, vpx_host.h) ----
+struct ACSFwdSlots { float *wpk, *partial, *st_tmp, *xc, *mc, *hc, *ac, *mem, *o_pre, *oc, *lc, *gam[5], *bet[5]; };   // partial: doubles, taken as floats
+template <class WS>
+static void carve_acs_fwd(WS& ws, const vpx_acstlstm_desc* d, const ACS& s, ACSFwdSlots& w) {
+    w.wpk = ws.take(s.wpk_max); w.partial = ws.take((size_t)s.B * 64 * 2 * 2); w.st_tmp = ws.take((size_t)10 * s.B);
+    w.xc = ws.take(7 * s.n_state); w.mc = ws.take(3 * s.n_state);
+    if (!(d->flags & VPX_FLAG_SAVE_FOR_BWD)) { w.hc = ws.take(4 * s.n_state); w.ac = ws.take(4 * s.n_state); w.mem = ws.take(2 * s.n_state); }   // (a saving call writes them into the reserve)
+    for (float** p : {&w.o_pre, &w.oc, &w.lc}) *p = ws.take(s.n_state);
+    if (d->layer_norm)   // the LayerNorm parameters transposed ([C,H,W] -> [HW,C])
+        for (int i = 0; i < 5; ++i) { w.gam[i] = ws.take(s.HW * ACS_LN_MULT[i] * s.Ch); w.bet[i] = ws.take(s.HW * ACS_LN_MULT[i] * s.Ch); }
+}
+struct ACSBwdSlots { float *wpk, *partial, *sums, *d_o, *d_lc, *dmem, *dxc, *dhc, *dac, *dmc, *dc_s, *dm_s, *slabs, *db_part, *du[5], *gam[5], *dgam[5], *dbet[5]; };
+template <class WS>
+static void carve_acs_bwd(WS& ws, const vpx_acstlstm_desc* d, const ACS& s, ACSBwdSlots& w) {
+    w.wpk = ws.take(s.wpk_max); w.partial = ws.take((size_t)s.B * 64 * 2 * 2); w.sums = ws.take((size_t)10 * s.B);
+    w.d_o = ws.take(s.n_state); w.d_lc = ws.take(s.n_state); w.dmem = ws.take(2 * s.n_state);
+    w.dxc = ws.take(7 * s.n_state); w.dhc = ws.take(4 * s.n_state); w.dac = ws.take(4 * s.n_state); w.dmc = ws.take(3 * s.n_state);
+    w.dc_s = ws.take(s.n_state); w.dm_s = ws.take(s.n_state);
+    w.slabs = ws.take(s.slab_floats); w.db_part = ws.take((size_t)COLSUM_BLOCKS * 7 * s.Ch);
+    float* const dy[5] = {w.dxc, w.dhc, w.dac, w.dmc, w.d_o};
+    for (int i = 0; i < 5; ++i) {   // du: the gradient of each convolution's output — below its LayerNorm where there is one
+        if (!d->layer_norm) { w.du[i] = dy[i]; continue; }
+        w.du[i] = ws.take(ACS_LN_MULT[i] * s.n_state);
+        w.gam[i] = ws.take(s.HW * ACS_LN_MULT[i] * s.Ch); w.dgam[i] = ws.take(s.HW * ACS_LN_MULT[i] * s.Ch); w.dbet[i] = ws.take(s.HW * ACS_LN_MULT[i] * s.Ch);
     }
-    return R;
 }
 
 }  // namespace vpx
@@ -155,22 +179,18 @@ extern "C" {
 
 size_t vpx_acstlstm_reserve_bytes(const vpx_acstlstm_desc* d) {
     if (acs_check(d) || !(d->flags & VPX_FLAG_SAVE_FOR_BWD)) return 0;
-    const ACS s = acs_sizes(d);
-    return (size_t)(18 + (d->layer_norm ? ACS_LN_PLANES : 0)) * align256(s.n_state * 4) + align256((size_t)10 * d->B * 4) + 256;
+    CarveMeasure m; ACSReserve R{};
+    acs_carve_reserve(m, d, acs_sizes(d), R);
+    return m.off + 256;   // (+ what a Carver skips at a base that is not 256-byte aligned)
 }
 
 size_t vpx_acstlstm_workspace_bytes(const vpx_acstlstm_desc* d) {
     if (const char* e = acs_check(d)) { set_error("vpx_acstlstm_workspace_bytes: %s", e); return 0; }
     const ACS s = acs_sizes(d);
-    const size_t plane = align256(s.n_state * 4), per_sample = align256(s.HW * d->Ch * 4);
-    const size_t ln_fwd = d->layer_norm ? 2 * ACS_LN_PLANES * per_sample : 0;
-    // forward: xc(7) hc(4) ac(4) mc(3) o_pre oc lc mem(2) save-less gates; LayerNorm parameters transposed (gamma, beta)
-    const size_t fwd = 23 * plane + ln_fwd;
-    // backward: d_o d_lc du_o dmem(2) dxc(7) dhc(4) dac(4) dmc(3) dm + LayerNorm: du_x(7) du_h(4) du_a(4) du_m(3); slabs; bias partials;
-    // LayerNorm parameters (gamma: 19) and their gradients (2 x 19)
-    const size_t bwd = (size_t)(24 + (d->layer_norm ? ACS_LN_PLANES : 0)) * plane + align256(s.slab_floats * 4) +
-                       align256((size_t)COLSUM_BLOCKS * 7 * d->Ch * 4) + (d->layer_norm ? 3 * ACS_LN_PLANES * per_sample : 0);
-    return (fwd > bwd ? fwd : bwd) + align256(s.wpk_max * 4) + align256((size_t)d->B * 64 * 2 * 8) + align256((size_t)10 * d->B * 4) + 64 * 256;
+    CarveMeasure f, b; ACSFwdSlots wf{}; ACSBwdSlots wb{};
+    carve_acs_fwd(f, d, s, wf);
+    if (d->flags & VPX_FLAG_SAVE_FOR_BWD) carve_acs_bwd(b, d, s, wb);   // (only a saving call is followed by a backward)
+    return (f.off > b.off ? f.off : b.off) + 256;
 }
 
 // params: (conv_x, conv_h, conv_a, conv_m, conv_o, conv_last) x (weight OIHW, bias); ln: (x, h, a, m, o) x (gamma, beta), [C,H,W] each
@@ -191,53 +211,42 @@ int vpx_acstlstm_step_fwd(const vpx_acstlstm_desc* d, const float* x, const floa
     const ACS s = acs_sizes(d);
     const int B = s.B, Cin = s.Cin, Ch = s.Ch, k = s.k, prec = d->precision;
     const ConvGeo g{B, s.H, s.W};
-    ACSReserve R{};
-    if (save) R = acs_carve_reserve(reserve, s, use_ln);
     Carver ws(workspace, workspace_bytes);
-    float* wpk = ws.take(s.wpk_max);
-    double* partial = (double*)ws.take((size_t)B * 64 * 2 * 2);
-    float* st_tmp = ws.take((size_t)10 * B);
-    float* xc = ws.take(7 * s.n_state);
-    float* mc = ws.take(3 * s.n_state);
-    float* hc = save ? R.hc : ws.take(4 * s.n_state);
-    float* ac = save ? R.ac : ws.take(4 * s.n_state);
-    float* mem = save ? R.mem : ws.take(2 * s.n_state);
-    float* o_pre = ws.take(s.n_state);
-    float* oc = ws.take(s.n_state);
-    float* lc = ws.take(s.n_state);
-    float *gam[5] = {}, *bet[5] = {};
-    if (use_ln)
-        for (int i = 0; i < 5; ++i) { gam[i] = ws.take(s.HW * ACS_LN_MULT[i] * Ch); bet[i] = ws.take(s.HW * ACS_LN_MULT[i] * Ch); }
+    ACSFwdSlots w{};
+    carve_acs_fwd(ws, d, s, w);
     VPX_CHECK_CARVE(ws, "vpx_acstlstm_step_fwd");
+    Carver rs(save ? reserve : nullptr, save ? reserve_bytes : 0);   // (registered like the workspace: a slot written past its end is an error, not a write)
+    ACSReserve R{};
+    acs_carve_reserve(rs, d, s, R);
+    VPX_CHECK_CARVE(rs, "vpx_acstlstm_step_fwd (reserve)");
+    double* partial = (double*)w.partial;
+    float *hc = save ? R.hc : w.hc, *ac = save ? R.ac : w.ac, *mem = save ? R.mem : w.mem, *st = save ? R.st : w.st_tmp;   // (st: LayerNorm only)
     if (use_ln)
         for (int i = 0; i < 5; ++i) {
-            VPX_CHECK_HIP(launch_nchw_to_nhwc(ln[2 * i], gam[i], 1, ACS_LN_MULT[i] * Ch, s.H, s.W, stream));
-            VPX_CHECK_HIP(launch_nchw_to_nhwc(ln[2 * i + 1], bet[i], 1, ACS_LN_MULT[i] * Ch, s.H, s.W, stream));
+            VPX_CHECK_HIP(launch_nchw_to_nhwc(ln[2 * i], w.gam[i], 1, ACS_LN_MULT[i] * Ch, s.H, s.W, stream));
+            VPX_CHECK_HIP(launch_nchw_to_nhwc(ln[2 * i + 1], w.bet[i], 1, ACS_LN_MULT[i] * Ch, s.H, s.W, stream));
         }
     const long long n1 = (long long)s.HW * Ch;
     int rc;
     // the four input convolutions, each with its bias and (optionally) its LayerNorm (predrnn.py:139-142 with :102-136)
-    struct In { const float* src; int C; int mult; float* dst; int pi; } in[4] = {{x, Cin, 7, xc, 0}, {h, Ch, 4, hc, 1}, {act, Ch, 4, ac, 2}, {m, Ch, 3, mc, 3}};
+    struct In { const float* src; int C; int mult; float* dst; int pi; } in[4] = {{x, Cin, 7, w.xc, 0}, {h, Ch, 4, hc, 1}, {act, Ch, 4, ac, 2}, {m, Ch, 3, w.mc, 3}};
     for (int i = 0; i < 4; ++i) {
         const In& L = in[i];
         if ((rc = plain_conv(stream, prec, g, L.src, L.C, L.C, params[2 * L.pi], (long long)L.C * k * k, k * k, k, k, L.mult * Ch, false, params[2 * L.pi + 1],
-                             L.dst, L.mult * Ch, false, wpk))) return rc;
-        if (use_ln)
-            VPX_CHECK_HIP(launch_layernorm_fwd(L.dst, gam[i], bet[i], L.dst, save ? R.xhat[i] : nullptr, save ? R.st[i] : st_tmp + 2 * B * i, partial, B,
-                                               L.mult * n1, stream));
+                             L.dst, L.mult * Ch, false, w.wpk))) return rc;
+        if (use_ln) VPX_CHECK_HIP(launch_layernorm_fwd(L.dst, w.gam[i], w.bet[i], L.dst, R.xhat[i], st + 2 * B * i, partial, B, L.mult * n1, stream));
     }
     // conv_h(h) * conv_a(a), both gate groups, the state updates, mem = (c_new | m_new)  (predrnn.py:143-164)
     {
-        AcstGateArgs a{(long long)((size_t)B * s.HW), Ch, d->forget_bias, xc, hc, ac, mc, c, m, c_new, m_new, delta_c, delta_m, o_pre, mem, save ? R.save : nullptr};
+        AcstGateArgs a{(long long)((size_t)B * s.HW), Ch, d->forget_bias, w.xc, hc, ac, w.mc, c, m, c_new, m_new, delta_c, delta_m, w.o_pre, mem, R.save};
         VPX_LAUNCH(acst_gates_fwd_kernel, dim3((unsigned)((a.npix * Ch + 255) / 256)), dim3(256), 0, stream, a);
         VPX_CHECK_HIP(vpx_hip_last_error());
     }
     // conv_o(mem) (+ LayerNorm), conv_last(mem), output gate  (predrnn.py:165-167)
-    if ((rc = plain_conv(stream, prec, g, mem, 2 * Ch, 2 * Ch, params[8], (long long)2 * Ch * k * k, k * k, k, k, Ch, false, params[9], oc, Ch, false, wpk))) return rc;
-    if (use_ln)
-        VPX_CHECK_HIP(launch_layernorm_fwd(oc, gam[4], bet[4], oc, save ? R.xhat[4] : nullptr, save ? R.st[4] : st_tmp + 8 * B, partial, B, n1, stream));
-    if ((rc = plain_conv(stream, prec, g, mem, 2 * Ch, 2 * Ch, params[10], (long long)2 * Ch, 1, 1, 1, Ch, false, params[11], lc, Ch, false, wpk))) return rc;
-    VPX_CHECK_HIP(launch_st_ln_out(o_pre, oc, lc, h_new, save ? R.o : nullptr, save ? R.tl : nullptr, (long long)s.n_state, stream));
+    if ((rc = plain_conv(stream, prec, g, mem, 2 * Ch, 2 * Ch, params[8], (long long)2 * Ch * k * k, k * k, k, k, Ch, false, params[9], w.oc, Ch, false, w.wpk))) return rc;
+    if (use_ln) VPX_CHECK_HIP(launch_layernorm_fwd(w.oc, w.gam[4], w.bet[4], w.oc, R.xhat[4], st + 8 * B, partial, B, n1, stream));
+    if ((rc = plain_conv(stream, prec, g, mem, 2 * Ch, 2 * Ch, params[10], (long long)2 * Ch, 1, 1, 1, Ch, false, params[11], w.lc, Ch, false, w.wpk))) return rc;
+    VPX_CHECK_HIP(launch_st_ln_out(w.o_pre, w.oc, w.lc, h_new, R.o, R.tl, (long long)s.n_state, stream));
     return VPX_OK;
 }
 
@@ -261,58 +270,44 @@ int vpx_acstlstm_step_bwd(const vpx_acstlstm_desc* d, const float* x, const floa
     const int B = s.B, Cin = s.Cin, Ch = s.Ch, k = s.k, prec = d->precision, HW = (int)s.HW;
     const long long npix = (long long)B * HW;
     const ConvGeo g{B, s.H, s.W};
-    const ACSReserve R = acs_carve_reserve(const_cast<void*>(reserve), s, use_ln);
+    Carver rs(const_cast<void*>(reserve), reserve_bytes);
+    ACSReserve R{};
+    acs_carve_reserve(rs, d, s, R);
+    VPX_CHECK_CARVE(rs, "vpx_acstlstm_step_bwd (reserve)");
     Carver ws(workspace, workspace_bytes);
-    float* wpk = ws.take(s.wpk_max);
-    double* partial = (double*)ws.take((size_t)B * 64 * 2 * 2);
-    float* sums = ws.take((size_t)10 * B);
-    float* d_o = ws.take(s.n_state);
-    float* d_lc = ws.take(s.n_state);
-    float* dmem = ws.take(2 * s.n_state);
-    float* dxc = ws.take(7 * s.n_state);
-    float* dhc = ws.take(4 * s.n_state);
-    float* dac = ws.take(4 * s.n_state);
-    float* dmc = ws.take(3 * s.n_state);
-    float* dc_s = ws.take(s.n_state);
-    float* dm_s = ws.take(s.n_state);
-    float* slabs = ws.take(s.slab_floats);
-    float* db_part = ws.take((size_t)COLSUM_BLOCKS * 7 * Ch);
-    float *du[5] = {dxc, dhc, dac, dmc, d_o}, *gam[5] = {}, *dgam[5] = {}, *dbet[5] = {};
-    if (use_ln)
-        for (int i = 0; i < 5; ++i) {
-            du[i] = ws.take(ACS_LN_MULT[i] * s.n_state);
-            gam[i] = ws.take(s.HW * ACS_LN_MULT[i] * Ch); dgam[i] = ws.take(s.HW * ACS_LN_MULT[i] * Ch); dbet[i] = ws.take(s.HW * ACS_LN_MULT[i] * Ch);
-        }
+    ACSBwdSlots w{};
+    carve_acs_bwd(ws, d, s, w);
     VPX_CHECK_CARVE(ws, "vpx_acstlstm_step_bwd");
+    double* partial = (double*)w.partial;
     if (use_ln)
-        for (int i = 0; i < 5; ++i) VPX_CHECK_HIP(launch_nchw_to_nhwc(ln[2 * i], gam[i], 1, ACS_LN_MULT[i] * Ch, s.H, s.W, stream));
+        for (int i = 0; i < 5; ++i) VPX_CHECK_HIP(launch_nchw_to_nhwc(ln[2 * i], w.gam[i], 1, ACS_LN_MULT[i] * Ch, s.H, s.W, stream));
     float* const* dp = dparams;
     auto want = [&](int i) { return dp && dp[i]; };
     const int blk[8] = {0, 1, 2, 3, 4, 5, 6, 0};
     int rc;
     // A: h_new = sigmoid(o_pre + oc) * tanh(lc): the gradient of the sigmoid's argument (goes to o_pre and to conv_o's output alike) and of lc
-    VPX_LAUNCH(st_out_bwd_kernel, dim3((unsigned)((s.n_state + 255) / 256)), dim3(256), 0, stream, dh_new, R.o, R.tl, d_o, d_lc, (long long)s.n_state);
+    VPX_LAUNCH(st_out_bwd_kernel, dim3((unsigned)((s.n_state + 255) / 256)), dim3(256), 0, stream, dh_new, R.o, R.tl, w.d_o, w.d_lc, (long long)s.n_state);
     VPX_CHECK_HIP(vpx_hip_last_error());
     // B: conv_o (through its LayerNorm) and conv_last back to mem = (c_new | m_new); their weight and bias gradients
-    if (use_ln) VPX_CHECK_HIP(launch_layernorm_bwd(d_o, Ch, Ch, blk, R.xhat[4], R.st[4], gam[4], B, HW, Ch, partial, sums, du[4], dgam[4], dbet[4], stream));
-    if ((rc = plain_conv(stream, prec, g, du[4], Ch, Ch, params[8], (long long)2 * Ch * k * k, k * k, k, k, 2 * Ch, true, nullptr, dmem, 2 * Ch, false, wpk))) return rc;
-    if ((rc = plain_conv(stream, prec, g, d_lc, Ch, Ch, params[10], (long long)2 * Ch, 1, 1, 1, 2 * Ch, true, nullptr, dmem, 2 * Ch, true, wpk))) return rc;
-    if (want(8) && (rc = plain_wgrad(stream, prec, g, du[4], Ch, R.mem, 2 * Ch, k, k, slabs, dp[8]))) return rc;
-    if (want(9)) VPX_CHECK_HIP(launch_colsum(du[4], nullptr, 0.f, nullptr, dp[9], db_part, npix, Ch, stream));
-    if (want(10) && (rc = plain_wgrad(stream, prec, g, d_lc, Ch, R.mem, 2 * Ch, 1, 1, slabs, dp[10]))) return rc;
-    if (want(11)) VPX_CHECK_HIP(launch_colsum(d_lc, nullptr, 0.f, nullptr, dp[11], db_part, npix, Ch, stream));
+    if (use_ln) VPX_CHECK_HIP(launch_layernorm_bwd(w.d_o, Ch, Ch, blk, R.xhat[4], R.st + 2 * B * 4, w.gam[4], B, HW, Ch, partial, w.sums, w.du[4], w.dgam[4], w.dbet[4], stream));
+    if ((rc = plain_conv(stream, prec, g, w.du[4], Ch, Ch, params[8], (long long)2 * Ch * k * k, k * k, k, k, 2 * Ch, true, nullptr, w.dmem, 2 * Ch, false, w.wpk))) return rc;
+    if ((rc = plain_conv(stream, prec, g, w.d_lc, Ch, Ch, params[10], (long long)2 * Ch, 1, 1, 1, 2 * Ch, true, nullptr, w.dmem, 2 * Ch, true, w.wpk))) return rc;
+    if (want(8) && (rc = plain_wgrad(stream, prec, g, w.du[4], Ch, R.mem, 2 * Ch, k, k, w.slabs, dp[8]))) return rc;
+    if (want(9)) VPX_CHECK_HIP(launch_colsum(w.du[4], nullptr, 0.f, nullptr, dp[9], w.db_part, npix, Ch, stream));
+    if (want(10) && (rc = plain_wgrad(stream, prec, g, w.d_lc, Ch, R.mem, 2 * Ch, 1, 1, w.slabs, dp[10]))) return rc;
+    if (want(11)) VPX_CHECK_HIP(launch_colsum(w.d_lc, nullptr, 0.f, nullptr, dp[11], w.db_part, npix, Ch, stream));
     // C: the gate stage: gradients of the four (normalised) conv outputs, dc and the direct part of dm
     {
-        AcstGateBwdArgs a{npix, Ch, R.hc, R.ac, c, m, R.save, dc_new, dm_new, ddc, ddm, d_o, dmem, dxc, dhc, dac, dmc, dc ? dc : dc_s, dm ? dm : dm_s};
+        AcstGateBwdArgs a{npix, Ch, R.hc, R.ac, c, m, R.save, dc_new, dm_new, ddc, ddm, w.d_o, w.dmem, w.dxc, w.dhc, w.dac, w.dmc, dc ? dc : w.dc_s, dm ? dm : w.dm_s};
         VPX_LAUNCH(acst_gates_bwd_kernel, dim3((unsigned)((npix * Ch + 255) / 256)), dim3(256), 0, stream, a);
         VPX_CHECK_HIP(vpx_hip_last_error());
     }
     // D: through the LayerNorms of conv_x / conv_h / conv_a / conv_m
     if (use_ln) {
-        float* dy4[4] = {dxc, dhc, dac, dmc};
+        float* const dy4[4] = {w.dxc, w.dhc, w.dac, w.dmc};
         for (int i = 0; i < 4; ++i)
-            VPX_CHECK_HIP(launch_layernorm_bwd(dy4[i], ACS_LN_MULT[i] * Ch, Ch, blk, R.xhat[i], R.st[i], gam[i], B, HW, ACS_LN_MULT[i] * Ch, partial, sums, du[i],
-                                               dgam[i], dbet[i], stream));
+            VPX_CHECK_HIP(launch_layernorm_bwd(dy4[i], ACS_LN_MULT[i] * Ch, Ch, blk, R.xhat[i], R.st + 2 * B * i, w.gam[i], B, HW, ACS_LN_MULT[i] * Ch, partial, w.sums, w.du[i],
+                                               w.dgam[i], w.dbet[i], stream));
     }
     // E / F: data, weight and bias gradients of the four input convolutions (dm: the conv part adds to the gate stage's direct part)
     struct In { const float* src; int C; int mult; float* dsrc; int pi; bool acc; } in[4] = {{x, Cin, 7, dx, 0, false}, {h, Ch, 4, dh, 1, false},
@@ -320,16 +315,16 @@ int vpx_acstlstm_step_bwd(const vpx_acstlstm_desc* d, const float* x, const floa
     for (int i = 0; i < 4; ++i) {
         const In& L = in[i];
         const int Co = L.mult * Ch;
-        if (L.dsrc && (rc = plain_conv(stream, prec, g, du[i], Co, Co, params[2 * L.pi], (long long)L.C * k * k, k * k, k, k, L.C, true, nullptr, L.dsrc, L.C, L.acc, wpk)))
+        if (L.dsrc && (rc = plain_conv(stream, prec, g, w.du[i], Co, Co, params[2 * L.pi], (long long)L.C * k * k, k * k, k, k, L.C, true, nullptr, L.dsrc, L.C, L.acc, w.wpk)))
             return rc;
-        if (want(2 * L.pi) && (rc = plain_wgrad(stream, prec, g, du[i], Co, L.src, L.C, k, k, slabs, dp[2 * L.pi]))) return rc;
-        if (want(2 * L.pi + 1)) VPX_CHECK_HIP(launch_colsum(du[i], nullptr, 0.f, nullptr, dp[2 * L.pi + 1], db_part, npix, Co, stream));
+        if (want(2 * L.pi) && (rc = plain_wgrad(stream, prec, g, w.du[i], Co, L.src, L.C, k, k, w.slabs, dp[2 * L.pi]))) return rc;
+        if (want(2 * L.pi + 1)) VPX_CHECK_HIP(launch_colsum(w.du[i], nullptr, 0.f, nullptr, dp[2 * L.pi + 1], w.db_part, npix, Co, stream));
     }
     // G: LayerNorm parameter gradients back to the reference's [C,H,W]
     if (use_ln && dln)
         for (int i = 0; i < 5; ++i) {
-            if (dln[2 * i]) VPX_CHECK_HIP(launch_nhwc_to_nchw(dgam[i], dln[2 * i], 1, ACS_LN_MULT[i] * Ch, s.H, s.W, stream));
-            if (dln[2 * i + 1]) VPX_CHECK_HIP(launch_nhwc_to_nchw(dbet[i], dln[2 * i + 1], 1, ACS_LN_MULT[i] * Ch, s.H, s.W, stream));
+            if (dln[2 * i]) VPX_CHECK_HIP(launch_nhwc_to_nchw(w.dgam[i], dln[2 * i], 1, ACS_LN_MULT[i] * Ch, s.H, s.W, stream));
+            if (dln[2 * i + 1]) VPX_CHECK_HIP(launch_nhwc_to_nchw(w.dbet[i], dln[2 * i + 1], 1, ACS_LN_MULT[i] * Ch, s.H, s.W, stream));
         }
     return VPX_OK;
 }

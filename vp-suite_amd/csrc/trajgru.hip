@@ -359,80 +359,109 @@ int tg_conv_bwd(hipStream_t s, int prec, int N, int H, int W, const float* x, co
     return VPX_OK;
 }
 
+// ---- the buffers: each direction's workspace slots in the order they are taken, and the reserve (see CarveMeasure, vpx_host.h) ----
+struct TGFwdSlots { float *wpk, *i2h_all, *warped, *zero_h, *fl1, *f11, *h2h1; };
+template <class WS>
+void carve_tg_fwd(WS& ws, const vpx_trajgru_desc* d, const TGLayout& L, TGFwdSlots& s) {
+    s.wpk = ws.take(L.wpk);
+    s.i2h_all = ws.take((size_t)d->T * L.n3);   // the input projection of all frames
+    s.warped = ws.take(L.n_warp); s.zero_h = ws.take(L.n_h);
+    s.fl1 = ws.take(L.n_fl); s.f11 = ws.take(L.n_f1); s.h2h1 = ws.take(L.n3);   // one step's flows / features / `ret` output, where the call does not save
+}
+struct TGBwdSlots { float *wpk, *slabs, *cpart, *det_ws, *carry, *dprev, *dh_tmp, *zero_h, *di2h_all, *dx_i2f, *dh2h, *dwarped, *warped, *dflows, *df1, *df1s, *t_w, *t_b; };
+template <class WS>
+void carve_tg_bwd(WS& ws, const vpx_trajgru_desc* d, const TGLayout& L, TGBwdSlots& s) {
+    s.wpk = ws.take(L.wpk); s.slabs = ws.take(L.slabs); s.cpart = ws.take(L.colsum); s.det_ws = ws.take(L.det);
+    for (float** p : {&s.carry, &s.dprev, &s.dh_tmp, &s.zero_h}) *p = ws.take(L.n_h);
+    s.di2h_all = ws.take((size_t)d->T * L.n3); s.dx_i2f = ws.take((size_t)d->T * L.n_x);   // d(input projection) and the flow branch's dx, all steps
+    s.dh2h = ws.take(L.n3); s.dwarped = ws.take(L.n_warp); s.warped = ws.take(L.n_warp);
+    s.dflows = ws.take(L.n_fl); s.df1 = ws.take(L.n_f1); s.df1s = ws.take(L.n_f1);
+    s.t_w = ws.take(L.w_max); s.t_b = ws.take(L.b_max);
+}
+// The reserve a saving forward fills and the backward reads, all steps of each: flows, flow features, the `ret` output, the gate kernel's
+// (r, u, candidate). A descriptor that does not save has none (all null, nothing taken).
+struct TGReserve { float *flows, *f1, *h2h, *gsave; };
+template <class WS>
+void carve_tg_reserve(WS& rs, const vpx_trajgru_desc* d, const TGLayout& L, TGReserve& r) {
+    if (!(d->flags & VPX_FLAG_SAVE_FOR_BWD)) return;
+    const size_t T = (size_t)d->T;
+    r.flows = rs.take(T * L.n_fl); r.f1 = rs.take(T * L.n_f1); r.h2h = rs.take(T * L.n3); r.gsave = rs.take(T * L.n3);
+}
+
+// what both directions refuse, in their order: the descriptor, (backward) one that does not save, NULL operands, NULL parameters and
+// (backward: dparams, want_dx) the gradients they ask for, short buffers. args_ok: the direction's own tensors.
+int tg_call_check(const char* who, const vpx_trajgru_desc* d, bool bwd, bool args_ok, const float* x, const float* const* params, float* const* dparams,
+                  bool want_dx, const void* reserve, size_t reserve_bytes, const void* workspace, size_t workspace_bytes) {
+    int rc = tg_check(d, who);
+    if (rc != VPX_OK) return rc;
+    const bool save = (d->flags & VPX_FLAG_SAVE_FOR_BWD) != 0;
+    if (bwd && !save) { set_error("%s: desc lacks VPX_FLAG_SAVE_FOR_BWD", who); return VPX_ERR_ARG; }
+    if (!args_ok) { set_error("%s: NULL tensor argument%s", who, bwd ? "" : " (x and h0 must not both be NULL)"); return VPX_ERR_ARG; }
+    for (int i = 0; i < 10; ++i) {
+        if (!params[i]) { set_error("%s: parameter %d is NULL", who, i); return VPX_ERR_ARG; }
+        if (bwd && !dparams[i] && (x || i >= 4)) { set_error("%s: parameter gradient %d is NULL", who, i); return VPX_ERR_ARG; }
+    }
+    if (want_dx && !x) { set_error("%s: dx requested but x is NULL", who); return VPX_ERR_ARG; }
+    if (save && (!reserve || reserve_bytes < vpx_trajgru_reserve_bytes(d))) { set_error("%s: reserve too small", who); return VPX_ERR_WORKSPACE; }
+    if (!workspace || workspace_bytes < vpx_trajgru_workspace_bytes(d)) { set_error("%s: workspace too small", who); return VPX_ERR_WORKSPACE; }
+    return VPX_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t vpx_trajgru_reserve_bytes(const vpx_trajgru_desc* d) {
     if (tg_check(d, "vpx_trajgru_reserve_bytes") != VPX_OK || !(d->flags & VPX_FLAG_SAVE_FOR_BWD)) return 0;
-    const TGLayout L = tg_layout(d);
-    // per step: flows, flow features, the `ret` output, the gate kernel's (r, u, candidate)
-    return (size_t)d->T * (align256(L.n_fl * 4) + align256(L.n_f1 * 4) + 2 * align256(L.n3 * 4)) + 256;
+    CarveMeasure m; TGReserve r{};
+    carve_tg_reserve(m, d, tg_layout(d), r);
+    return m.off + 256;   // (+ what a Carver skips at a base that is not 256-byte aligned)
 }
 
 size_t vpx_trajgru_workspace_bytes(const vpx_trajgru_desc* d) {
     if (tg_check(d, "vpx_trajgru_workspace_bytes") != VPX_OK) return 0;
     const TGLayout L = tg_layout(d);
-    const size_t T = (size_t)d->T;
-    // forward: pack, input projection of all frames, warped operand, a zero state, one step's flows / features / ret output
-    size_t fwd = align256(L.wpk * 4) + align256(T * L.n3 * 4) + align256(L.n_warp * 4) + align256(L.n_h * 4) +
-                 align256(L.n_fl * 4) + align256(L.n_f1 * 4) + 2 * align256(L.n3 * 4);
-    size_t bwd = 0;
-    if (d->flags & VPX_FLAG_SAVE_FOR_BWD)
-        bwd = align256(L.wpk * 4) + align256(L.slabs * 4) + align256(L.colsum * 4) + align256(L.det * 4) +
-              4 * align256(L.n_h * 4) +                                  // carry, dprev, dh_tmp, zero state
-              align256(T * L.n3 * 4) + align256(T * L.n_x * 4) +         // d(input projection) and the flow branch's dx, all steps
-              align256(L.n3 * 4) + 2 * align256(L.n_warp * 4) + align256(L.n_fl * 4) + 2 * align256(L.n_f1 * 4) +
-              align256(L.w_max * 4) + align256(L.b_max * 4);
-    return (fwd > bwd ? fwd : bwd) + 512;
+    CarveMeasure f, b; TGFwdSlots sf{}; TGBwdSlots sb{};
+    carve_tg_fwd(f, d, L, sf);
+    if (d->flags & VPX_FLAG_SAVE_FOR_BWD) carve_tg_bwd(b, d, L, sb);   // (only a saving call is followed by a backward)
+    return (f.off > b.off ? f.off : b.off) + 256;
 }
 
 int vpx_trajgru_seq_fwd(const vpx_trajgru_desc* d, const float* x, const float* h0, const float* const* params, float* hs, void* reserve,
                         size_t reserve_bytes, void* workspace, size_t workspace_bytes, void* stream_) {
-    int rc = tg_check(d, "vpx_trajgru_seq_fwd");
+    int rc = tg_call_check("vpx_trajgru_seq_fwd", d, false, (x || h0) && params && hs, x, params, nullptr, false, reserve, reserve_bytes, workspace, workspace_bytes);
     if (rc != VPX_OK) return rc;
-    if ((!x && !h0) || !params || !hs) { set_error("vpx_trajgru_seq_fwd: NULL tensor argument (x and h0 must not both be NULL)"); return VPX_ERR_ARG; }
-    for (int i = 0; i < 10; ++i) if (!params[i]) { set_error("vpx_trajgru_seq_fwd: parameter %d is NULL", i); return VPX_ERR_ARG; }
     const bool save = (d->flags & VPX_FLAG_SAVE_FOR_BWD) != 0;
-    if (save && (!reserve || reserve_bytes < vpx_trajgru_reserve_bytes(d))) { set_error("vpx_trajgru_seq_fwd: reserve too small"); return VPX_ERR_WORKSPACE; }
-    if (!workspace || workspace_bytes < vpx_trajgru_workspace_bytes(d)) { set_error("vpx_trajgru_seq_fwd: workspace too small"); return VPX_ERR_WORKSPACE; }
     const float *i2h_w = params[0], *i2h_b = params[1], *i2f_w = params[2], *i2f_b = params[3], *h2f_w = params[4], *h2f_b = params[5],
                 *fl_w = params[6], *fl_b = params[7], *ret_w = params[8], *ret_b = params[9];
     hipStream_t stream = (hipStream_t)stream_;
     const TGLayout L = tg_layout(d);
     const int B = d->B, T = d->T, C = d->C, Cin = d->Cin, H = d->H, W = d->W, HW = H * W, k = d->k_i2h, F = TG_F, prec = d->precision;
     Carver ws(workspace, workspace_bytes);
-    float* wpk = ws.take(L.wpk);
-    float* i2h_all = ws.take((size_t)T * L.n3);
-    float* warped = ws.take(L.n_warp);
-    float* zero_h = ws.take(L.n_h);
-    float* fl1 = ws.take(L.n_fl);
-    float* f11 = ws.take(L.n_f1);
-    float* h2h1 = ws.take(L.n3);
+    TGFwdSlots w{};
+    carve_tg_fwd(ws, d, L, w);
     VPX_CHECK_CARVE(ws, "vpx_trajgru_seq_fwd");
-    float *flows = nullptr, *f1 = nullptr, *h2h = nullptr, *gsave = nullptr;
-    if (save) {
-        Carver rs(reserve, reserve_bytes);
-        flows = rs.take((size_t)T * L.n_fl); f1 = rs.take((size_t)T * L.n_f1); h2h = rs.take((size_t)T * L.n3); gsave = rs.take((size_t)T * L.n3);
-        VPX_CHECK_CARVE(rs, "vpx_trajgru_seq_fwd (reserve)");
-    }
-    if (x && (rc = tg_conv(stream, prec, T * B, H, W, x, i2h_w, i2h_b, i2h_all, Cin, 3 * C, k, false, 0.f, wpk))) return rc;   // (:171-173) all frames, one launch
-    if (!h0) VPX_CHECK_HIP(vpx_memset_async(zero_h, 0, L.n_h * 4, stream));
+    Carver rs(save ? reserve : nullptr, save ? reserve_bytes : 0);
+    TGReserve R{};
+    carve_tg_reserve(rs, d, L, R);
+    VPX_CHECK_CARVE(rs, "vpx_trajgru_seq_fwd (reserve)");
+    if (x && (rc = tg_conv(stream, prec, T * B, H, W, x, i2h_w, i2h_b, w.i2h_all, Cin, 3 * C, k, false, 0.f, w.wpk))) return rc;   // (:171-173) all frames, one launch
+    if (!h0) VPX_CHECK_HIP(vpx_memset_async(w.zero_h, 0, L.n_h * 4, stream));
     for (int t = 0; t < T; ++t) {
-        const float* prev = t == 0 ? (h0 ? h0 : zero_h) : hs + (size_t)(t - 1) * L.n_h;
-        float* fl_t = save ? flows + (size_t)t * L.n_fl : fl1;
-        float* f1_t = save ? f1 + (size_t)t * L.n_f1 : f11;
-        float* h2h_t = save ? h2h + (size_t)t * L.n3 : h2h1;
+        const float* prev = t == 0 ? (h0 ? h0 : w.zero_h) : hs + (size_t)(t - 1) * L.n_h;
+        float* fl_t = save ? R.flows + (size_t)t * L.n_fl : w.fl1;
+        float* f1_t = save ? R.f1 + (size_t)t * L.n_f1 : w.f11;
+        float* h2h_t = save ? R.h2h + (size_t)t * L.n3 : w.h2h1;
         // flow generator (:134-146): f1 = leaky(i2f(x_t) + h2f(h_{t-1})), flows = conv5x5(f1)
-        if ((rc = tg_conv(stream, prec, B, H, W, prev, h2f_w, h2f_b, f1_t, C, F, 5, false, x ? 0.f : d->slope, wpk))) return rc;
-        if (x && (rc = tg_conv(stream, prec, B, H, W, x + (size_t)t * L.n_x, i2f_w, i2f_b, f1_t, Cin, F, 5, true, d->slope, wpk))) return rc;
-        if ((rc = tg_conv(stream, prec, B, H, W, f1_t, fl_w, fl_b, fl_t, F, 2 * d->L, 5, false, 0.f, wpk))) return rc;
+        if ((rc = tg_conv(stream, prec, B, H, W, prev, h2f_w, h2f_b, f1_t, C, F, 5, false, x ? 0.f : d->slope, w.wpk))) return rc;
+        if (x && (rc = tg_conv(stream, prec, B, H, W, x + (size_t)t * L.n_x, i2f_w, i2f_b, f1_t, Cin, F, 5, true, d->slope, w.wpk))) return rc;
+        if ((rc = tg_conv(stream, prec, B, H, W, f1_t, fl_w, fl_b, fl_t, F, 2 * d->L, 5, false, 0.f, w.wpk))) return rc;
         // L warps of h_{t-1} along -flow (:148-162, :184-187), then the 1x1 `ret` convolution (:188)
-        if ((rc = tg_warp_fwd(prev, fl_t, warped, B, H, W, C, d->L, stream))) return rc;
-        if ((rc = tg_conv(stream, prec, B, H, W, warped, ret_w, ret_b, h2h_t, d->L * C, 3 * C, 1, false, 0.f, wpk))) return rc;
+        if ((rc = tg_warp_fwd(prev, fl_t, w.warped, B, H, W, C, d->L, stream))) return rc;
+        if ((rc = tg_conv(stream, prec, B, H, W, w.warped, ret_w, ret_b, h2h_t, d->L * C, 3 * C, 1, false, 0.f, w.wpk))) return rc;
         // gates + state update (:190-203)
-        if ((rc = tg_gates_fwd(x ? i2h_all + (size_t)t * L.n3 : nullptr, (long long)HW * 3 * C, h2h_t, prev, hs + (size_t)t * L.n_h,
-                               save ? gsave + (size_t)t * L.n3 : nullptr, B, HW, C, 0, d->slope, stream))) return rc;
+        if ((rc = tg_gates_fwd(x ? w.i2h_all + (size_t)t * L.n3 : nullptr, (long long)HW * 3 * C, h2h_t, prev, hs + (size_t)t * L.n_h,
+                               save ? R.gsave + (size_t)t * L.n3 : nullptr, B, HW, C, 0, d->slope, stream))) return rc;
     }
     return VPX_OK;
 }
@@ -440,17 +469,9 @@ int vpx_trajgru_seq_fwd(const vpx_trajgru_desc* d, const float* x, const float* 
 int vpx_trajgru_seq_bwd(const vpx_trajgru_desc* d, const float* x, const float* h0, const float* const* params, const float* hs,
                         const void* reserve, size_t reserve_bytes, const float* dout, const float* dhT, float* dx, float* dh0,
                         float* const* dparams, void* workspace, size_t workspace_bytes, void* stream_) {
-    int rc = tg_check(d, "vpx_trajgru_seq_bwd");
+    int rc = tg_call_check("vpx_trajgru_seq_bwd", d, true, (x || h0) && params && hs && reserve && dparams, x, params, dparams, dx != nullptr, reserve, reserve_bytes,
+                           workspace, workspace_bytes);
     if (rc != VPX_OK) return rc;
-    if (!(d->flags & VPX_FLAG_SAVE_FOR_BWD)) { set_error("vpx_trajgru_seq_bwd: desc lacks VPX_FLAG_SAVE_FOR_BWD"); return VPX_ERR_ARG; }
-    if ((!x && !h0) || !params || !hs || !reserve || !dparams) { set_error("vpx_trajgru_seq_bwd: NULL tensor argument"); return VPX_ERR_ARG; }
-    for (int i = 0; i < 10; ++i) {
-        if (!params[i]) { set_error("vpx_trajgru_seq_bwd: parameter %d is NULL", i); return VPX_ERR_ARG; }
-        if (!dparams[i] && (x || i >= 4)) { set_error("vpx_trajgru_seq_bwd: parameter gradient %d is NULL", i); return VPX_ERR_ARG; }
-    }
-    if (dx && !x) { set_error("vpx_trajgru_seq_bwd: dx requested but x is NULL"); return VPX_ERR_ARG; }
-    if (reserve_bytes < vpx_trajgru_reserve_bytes(d)) { set_error("vpx_trajgru_seq_bwd: reserve too small"); return VPX_ERR_WORKSPACE; }
-    if (!workspace || workspace_bytes < vpx_trajgru_workspace_bytes(d)) { set_error("vpx_trajgru_seq_bwd: workspace too small"); return VPX_ERR_WORKSPACE; }
     const float *i2h_w = params[0], *i2f_w = params[2], *h2f_w = params[4], *fl_w = params[6], *ret_w = params[8];
     float *d_i2h_w = dparams[0], *d_i2h_b = dparams[1], *d_i2f_w = dparams[2], *d_i2f_b = dparams[3], *d_h2f_w = dparams[4], *d_h2f_b = dparams[5],
           *d_fl_w = dparams[6], *d_fl_b = dparams[7], *d_ret_w = dparams[8], *d_ret_b = dparams[9];
@@ -459,31 +480,14 @@ int vpx_trajgru_seq_bwd(const vpx_trajgru_desc* d, const float* x, const float* 
     const int B = d->B, T = d->T, C = d->C, Cin = d->Cin, H = d->H, W = d->W, HW = H * W, k = d->k_i2h, F = TG_F, prec = d->precision, LC = d->L * C, L2 = 2 * d->L;
     const float slope = d->slope;
     Carver rs(const_cast<void*>(reserve), reserve_bytes);
-    const float* flows = rs.take((size_t)T * L.n_fl);
-    const float* f1 = rs.take((size_t)T * L.n_f1);
-    const float* h2h = rs.take((size_t)T * L.n3);
-    const float* gsave = rs.take((size_t)T * L.n3);
+    TGReserve R{};
+    carve_tg_reserve(rs, d, L, R);
     VPX_CHECK_CARVE(rs, "vpx_trajgru_seq_bwd (reserve)");
     Carver ws(workspace, workspace_bytes);
-    float* wpk = ws.take(L.wpk);
-    float* slabs = ws.take(L.slabs);
-    float* cpart = ws.take(L.colsum);
-    float* det_ws = ws.take(L.det);
-    float* carry = ws.take(L.n_h);
-    float* dprev = ws.take(L.n_h);
-    float* dh_tmp = ws.take(L.n_h);
-    float* zero_h = ws.take(L.n_h);
-    float* di2h_all = ws.take((size_t)T * L.n3);
-    float* dx_i2f = ws.take((size_t)T * L.n_x);
-    float* dh2h = ws.take(L.n3);
-    float* dwarped = ws.take(L.n_warp);
-    float* warped = ws.take(L.n_warp);
-    float* dflows = ws.take(L.n_fl);
-    float* df1 = ws.take(L.n_f1);
-    float* df1s = ws.take(L.n_f1);
-    float* t_w = ws.take(L.w_max);
-    float* t_b = ws.take(L.b_max);
+    TGBwdSlots w{};
+    carve_tg_bwd(ws, d, L, w);
     VPX_CHECK_CARVE(ws, "vpx_trajgru_seq_bwd");
+    float *carry = w.carry, *dprev = w.dprev;   // exchanged after every step
     const bool det = vpx::g_deterministic != 0;
     auto axpy = [&](float* y, const float* v, size_t n) -> int { VPX_CHECK_HIP(launch_axpy(y, v, (long long)n, stream)); return VPX_OK; };
     auto zero = [&](float* p, size_t n) -> int { VPX_CHECK_HIP(vpx_memset_async(p, 0, n * 4, stream)); return VPX_OK; };
@@ -492,40 +496,40 @@ int vpx_trajgru_seq_bwd(const vpx_trajgru_desc* d, const float* x, const float* 
     if ((rc = zero(d_ret_w, n_ret)) || (rc = zero(d_ret_b, 3 * C)) || (rc = zero(d_fl_w, n_fl_w)) || (rc = zero(d_fl_b, L2)) ||
         (rc = zero(d_h2f_w, n_h2f)) || (rc = zero(d_h2f_b, F))) return rc;
     if (x && (rc = zero(d_i2f_w, n_i2f))) return rc;
-    if (!h0 && (rc = zero(zero_h, L.n_h))) return rc;
+    if (!h0 && (rc = zero(w.zero_h, L.n_h))) return rc;
     if (dhT) VPX_CHECK_HIP(vpx_memcpy_async(carry, dhT, L.n_h * 4, hipMemcpyDeviceToDevice, stream));
     else if ((rc = zero(carry, L.n_h))) return rc;
     for (int t = T - 1; t >= 0; --t) {
-        const float* prev = t == 0 ? (h0 ? h0 : zero_h) : hs + (size_t)(t - 1) * L.n_h;
-        const float* fl_t = flows + (size_t)t * L.n_fl;
-        const float* f1_t = f1 + (size_t)t * L.n_f1;
+        const float* prev = t == 0 ? (h0 ? h0 : w.zero_h) : hs + (size_t)(t - 1) * L.n_h;
+        const float* fl_t = R.flows + (size_t)t * L.n_fl;
+        const float* f1_t = R.f1 + (size_t)t * L.n_f1;
         if (dout && (rc = axpy(carry, dout + (size_t)t * L.n_h, L.n_h))) return rc;   // total gradient of h_t
-        if ((rc = tg_gates_bwd(carry, h2h + (size_t)t * L.n3, prev, gsave + (size_t)t * L.n3, x ? di2h_all + (size_t)t * L.n3 : nullptr,
-                               (long long)HW * 3 * C, dh2h, dprev, B, HW, C, 0, slope, stream))) return rc;
+        if ((rc = tg_gates_bwd(carry, R.h2h + (size_t)t * L.n3, prev, R.gsave + (size_t)t * L.n3, x ? w.di2h_all + (size_t)t * L.n3 : nullptr,
+                               (long long)HW * 3 * C, w.dh2h, dprev, B, HW, C, 0, slope, stream))) return rc;
         // `ret` (1x1) backward needs the warped operand again: recomputed (a streaming kernel) instead of stored for all t
-        if ((rc = tg_warp_fwd(prev, fl_t, warped, B, H, W, C, d->L, stream))) return rc;
-        if ((rc = tg_conv_bwd(stream, prec, B, H, W, warped, ret_w, dh2h, dwarped, t_w, t_b, LC, 3 * C, 1, wpk, slabs, cpart))) return rc;
-        if ((rc = axpy(d_ret_w, t_w, n_ret)) || (rc = axpy(d_ret_b, t_b, 3 * C))) return rc;
-        if (det) rc = tg_warp_bwd_det(prev, fl_t, dwarped, dprev, dflows, B, H, W, C, d->L, det_ws, L.det * 4, stream);
-        else rc = tg_warp_bwd(prev, fl_t, dwarped, dprev, dflows, B, H, W, C, d->L, stream);
+        if ((rc = tg_warp_fwd(prev, fl_t, w.warped, B, H, W, C, d->L, stream))) return rc;
+        if ((rc = tg_conv_bwd(stream, prec, B, H, W, w.warped, ret_w, w.dh2h, w.dwarped, w.t_w, w.t_b, LC, 3 * C, 1, w.wpk, w.slabs, w.cpart))) return rc;
+        if ((rc = axpy(d_ret_w, w.t_w, n_ret)) || (rc = axpy(d_ret_b, w.t_b, 3 * C))) return rc;
+        if (det) rc = tg_warp_bwd_det(prev, fl_t, w.dwarped, dprev, w.dflows, B, H, W, C, d->L, w.det_ws, L.det * 4, stream);
+        else rc = tg_warp_bwd(prev, fl_t, w.dwarped, dprev, w.dflows, B, H, W, C, d->L, stream);
         if (rc) return rc;
-        if ((rc = tg_conv_bwd(stream, prec, B, H, W, f1_t, fl_w, dflows, df1, t_w, t_b, F, L2, 5, wpk, slabs, cpart))) return rc;
-        if ((rc = axpy(d_fl_w, t_w, n_fl_w)) || (rc = axpy(d_fl_b, t_b, L2))) return rc;
-        VPX_CHECK_HIP(launch_colsum(df1, f1_t, slope, df1s, t_b, cpart, (long long)B * HW, F, stream));   // LeakyReLU' and the bias sum, one pass
-        if ((rc = axpy(d_h2f_b, t_b, F))) return rc;
-        if ((rc = tg_conv_bwd(stream, prec, B, H, W, prev, h2f_w, df1s, dh_tmp, t_w, nullptr, C, F, 5, wpk, slabs, cpart))) return rc;
-        if ((rc = axpy(d_h2f_w, t_w, n_h2f)) || (rc = axpy(dprev, dh_tmp, L.n_h))) return rc;
+        if ((rc = tg_conv_bwd(stream, prec, B, H, W, f1_t, fl_w, w.dflows, w.df1, w.t_w, w.t_b, F, L2, 5, w.wpk, w.slabs, w.cpart))) return rc;
+        if ((rc = axpy(d_fl_w, w.t_w, n_fl_w)) || (rc = axpy(d_fl_b, w.t_b, L2))) return rc;
+        VPX_CHECK_HIP(launch_colsum(w.df1, f1_t, slope, w.df1s, w.t_b, w.cpart, (long long)B * HW, F, stream));   // LeakyReLU' and the bias sum, one pass
+        if ((rc = axpy(d_h2f_b, w.t_b, F))) return rc;
+        if ((rc = tg_conv_bwd(stream, prec, B, H, W, prev, h2f_w, w.df1s, w.dh_tmp, w.t_w, nullptr, C, F, 5, w.wpk, w.slabs, w.cpart))) return rc;
+        if ((rc = axpy(d_h2f_w, w.t_w, n_h2f)) || (rc = axpy(dprev, w.dh_tmp, L.n_h))) return rc;
         if (x) {
-            if ((rc = tg_conv_bwd(stream, prec, B, H, W, x + (size_t)t * L.n_x, i2f_w, df1s, dx_i2f + (size_t)t * L.n_x, t_w, nullptr, Cin, F, 5,
-                                  wpk, slabs, cpart))) return rc;
-            if ((rc = axpy(d_i2f_w, t_w, n_i2f))) return rc;
+            if ((rc = tg_conv_bwd(stream, prec, B, H, W, x + (size_t)t * L.n_x, i2f_w, w.df1s, w.dx_i2f + (size_t)t * L.n_x, w.t_w, nullptr, Cin, F, 5,
+                                  w.wpk, w.slabs, w.cpart))) return rc;
+            if ((rc = axpy(d_i2f_w, w.t_w, n_i2f))) return rc;
         }
         float* sw = carry; carry = dprev; dprev = sw;   // gradient of h_{t-1} through this step
     }
     if (x) {
         VPX_CHECK_HIP(vpx_memcpy_async(d_i2f_b, d_h2f_b, (size_t)F * 4, hipMemcpyDeviceToDevice, stream));
-        if ((rc = tg_conv_bwd(stream, prec, T * B, H, W, x, i2h_w, di2h_all, dx, d_i2h_w, d_i2h_b, Cin, 3 * C, k, wpk, slabs, cpart))) return rc;
-        if (dx && (rc = axpy(dx, dx_i2f, (size_t)T * L.n_x))) return rc;
+        if ((rc = tg_conv_bwd(stream, prec, T * B, H, W, x, i2h_w, w.di2h_all, dx, d_i2h_w, d_i2h_b, Cin, 3 * C, k, w.wpk, w.slabs, w.cpart))) return rc;
+        if (dx && (rc = axpy(dx, w.dx_i2f, (size_t)T * L.n_x))) return rc;
     }
     if (dh0) VPX_CHECK_HIP(vpx_memcpy_async(dh0, carry, L.n_h * 4, hipMemcpyDeviceToDevice, stream));
     return VPX_OK;
