@@ -486,7 +486,7 @@ int vpx_lpips_stem_bwd(const float* x, const float* w, const float* dz, long lon
  * vpx_frechet_distance: *out (ONE double on the device) = fact sum Ep^2 + fact sum Et^2 - 2 sum_i sqrt(sigma_i^2 + 1e-15) + |mu_p - mu_t|^2
  *   for pred, target [b, n] float32, E the centred tables, fact = 1 / (b - 1) (1 for b = 1), sigma_i the singular values of the b x b
  *   matrix fact Ep Et^T: the reference's calculate_2_wasserstein_dist restated, in float64, every sum in one fixed order. The singular
- *   values come from a one-sided Jacobi iteration of at most 40 sweeps; input on which a 40th sweep still rotates gives NaN, never an
+ *   values come from a one-sided Jacobi iteration of at most 80 sweeps; input on which an 80th sweep still rotates gives NaN, never an
  *   unconverged number. b <= 256 (VPX_ERR_UNSUPPORTED beyond). */
 #define VPX_FVD_ROW 16
 enum { VPX_FVD_CONV = 0, VPX_FVD_POOL = 1, VPX_FVD_HEAD = 2 };

@@ -59,7 +59,7 @@ def clips(shape, seed):
     return a.contiguous(), b.contiguous()
 
 
-# ---- the parity record: with VPX_FVD_PARITY_OUT=FILE in the environment every figure the GPU tests of both FVD modules hand to record() is
+# ---- the parity record: with VPX_FVD_PARITY_OUT=FILE in the environment every figure the GPU tests of the three FVD modules hand to record() is
 #      written there ONCE, when the process ends (how profiles/fvd_parity.json is made) -------------------------------------------------------
 _FIGURES = {}
 
@@ -68,7 +68,7 @@ def _write_figures():
     out = os.environ.get("VPX_FVD_PARITY_OUT")
     if out and _FIGURES:
         with open(out, "w") as fh:
-            json.dump({"what": "FVD on one MI355X against float64 on the CPU, from tests/test_gpu_fvd_kernels.py and tests/test_gpu_fvd.py",
+            json.dump({"what": "FVD on one MI355X against float64 on the CPU, from tests/test_gpu_fvd_kernels.py, tests/test_gpu_fvd_edges.py and tests/test_gpu_fvd.py",
                        "metric": "kernels and trunk: max|got - ref| / max|ref|; the trunk's bound is max(4 x the float32 CPU chain's own error, 1e-6); distances: "
                                  "|got - ref| in absolute terms against the stated bound",
                        "cases": _FIGURES}, fh, indent=1)
@@ -90,7 +90,10 @@ FRECHET_KINDS = ("shifted", "identical", "rank1")
 
 
 def feature_tables(b, n, kind, seed=0):
-    """Two float32 tables [b, n]: "shifted" (different spreads and means), "identical", "rank1" (every centred table of rank <= 1)."""
+    """Two float32 tables [b, n]: "shifted" (different spreads and means), "identical", "rank1" (every centred table of rank <= 1); the
+    kinds of FRECHET_EDGE_KINDS are built by edge_feature_tables() below."""
+    if kind in FRECHET_EDGE_KINDS:
+        return edge_feature_tables(b, n, kind, seed)
     g = torch.Generator().manual_seed(3000 + 17 * b + n + seed)
     if kind == "rank1":
         p = torch.randn(b, 1, generator=g) * torch.randn(1, n, generator=g) + torch.randn(1, n, generator=g)
@@ -183,3 +186,144 @@ def conv3d_same_ref(x, w, bias, stride, relu):
 
 def maxpool3d_same_ref(x, kernel, stride):
     return F.max_pool3d(M._fvd_pad(x, kernel, stride), kernel, stride)
+
+
+# ---- edge cases (tests/test_gpu_fvd_edges.py; host checks of these tables in tests/test_fvd_host.py) ---------------------------------------
+def same_rule(size, k, s):
+    """(front, out) of one axis, the SAME rule written out on its own (not measure.same_pad, not the library's)."""
+    pad = max(k - s, 0) if size % s == 0 else max(k - size % s, 0)
+    return pad // 2, -(-size // s)
+
+
+# (kernel, stride, map T x H x W): anisotropic on every axis; narrower than the kernel on W; even kernels; stride above the kernel on every axis
+EDGE_FORMS = (((2, 3, 5), (1, 2, 3), (4, 6, 9)), ((3, 1, 7), (2, 1, 1), (5, 3, 3)), ((1, 4, 2), (1, 3, 2), (2, 7, 5)), ((1, 1, 2), (2, 3, 3), (5, 7, 8)))
+ADJACENT_FORMS = tuple((k, s, m) for k, s in (((1, 3, 3), (1, 2, 2)), ((3, 1, 1), (2, 1, 1))) for m in (ODD_MAP, EVEN_MAP))   # pool-adjacent
+EDGE_WIDTHS = ((3, 5), (4, 64), (12, 70), (16, 130))   # (Ci, Co): run below, at and above one K step; one, two and three N tiles
+TAP_CO = 5
+
+
+def form_id(form):
+    return "k" + "".join(map(str, form[0])) + "s" + "".join(map(str, form[1])) + "-" + "x".join(map(str, form[2]))
+
+
+def out_positions(form, n):
+    """M of the implicit GEMM: output positions of n maps."""
+    m = n
+    for size, k, s in zip(form[2], form[0], form[1]):
+        m *= same_rule(size, k, s)[1]
+    return m
+
+
+def ragged_batch(form):
+    """The smallest N >= 3 at which M spans several 64-position tiles with a ragged last one."""
+    n = 3
+    while out_positions(form, n) <= 64 or out_positions(form, n) % 64 == 0:
+        n += 1
+    return n
+
+
+def unit_taps(kernel, ci_count, co_count=TAP_CO):
+    """(co, ci, dt, dh, dw) of the eight corners of the kernel and its centre (corners coincide where a side is 1: they stay, on other
+    channels); tap i sits on input channel i % Ci and output channel i % Co, so nine taps reach every channel of both."""
+    corners = [(a, b, c) for a in (0, kernel[0] - 1) for b in (0, kernel[1] - 1) for c in (0, kernel[2] - 1)]
+    taps = corners + [tuple(k // 2 for k in kernel)]
+    return tuple((i % co_count, i % ci_count, *t) for i, t in enumerate(taps))
+
+
+def unit_tap_expected(x, co_count, tap, kernel, stride):
+    """float32 [N, Co, To, Ho, Wo]: what a convolution whose only non-zero weight is 1.0 at `tap` gives on x [N, Ci, T, H, W] — output
+    (ot, oh, ow) of channel co is x[ci, ot st - front_t + dt, ...] where that index lies in the map, 0 where it lies in the padding and in
+    every other channel. Index arithmetic only."""
+    co, ci, *d = tap
+    index, inside = [], []
+    for size, k, s, dd in zip(x.shape[2:], kernel, stride, d):
+        front, out = same_rule(size, k, s)
+        i = torch.arange(out) * s - front + dd
+        inside.append((i >= 0) & (i < size))
+        index.append(i.clamp(0, size - 1))
+    y = torch.zeros(x.shape[0], co_count, *(len(i) for i in index))
+    picked = x[:, ci][:, index[0]][:, :, index[1]][:, :, :, index[2]]
+    keep = inside[0][:, None, None] & inside[1][None, :, None] & inside[2][None, None, :]
+    y[:, co] = torch.where(keep, picked, torch.zeros(()))
+    return y, keep
+
+
+def edge_conv_case(form, ci, co, n, seed=0):
+    """(x [n, Ci, T, H, W], w [Co, Ci, kt, kh, kw] scaled to unit-size outputs, bias)."""
+    k, _, shape = form
+    g = torch.Generator().manual_seed(5000 + seed + ci * 131 + co * 7 + sum(v * (i + 1) for i, v in enumerate(k + shape)))
+    x = torch.randn(n, ci, *shape, generator=g)
+    w = torch.randn(co, ci, *k, generator=g) / (ci * k[0] * k[1] * k[2]) ** 0.5
+    return x, w, torch.randn(co, generator=g) * 0.3
+
+
+def window_mask(shape, kernel, stride, at):
+    """bool [To, Ho, Wo]: the pooling windows that hold the element `at` of a map of `shape` (same_rule again)."""
+    axes = []
+    for size, k, s, a in zip(shape, kernel, stride, at):
+        front, out = same_rule(size, k, s)
+        first = torch.arange(out) * s - front
+        axes.append((first <= a) & (a < first + k))
+    return axes[0][:, None, None] & axes[1][None, :, None] & axes[2][None, None, :]
+
+
+# (kernel, stride, map, {what the element is: its index}): one NaN per channel, in the order of the dict
+POOL_NAN_CASES = (
+    ((3, 3, 3), (3, 3, 3), (6, 6, 6), {"first of a window": (3, 3, 3), "inner": (4, 1, 4), "last of a window": (2, 5, 2)}),
+    ((3, 3, 3), (2, 2, 2), (5, 5, 5), {"shared by eight windows": (1, 1, 1), "shared by two": (2, 3, 2), "inner of one": (2, 2, 2),
+                                       "in a border window that holds padding": (0, 4, 0)}),
+    ((3, 3, 3), (1, 1, 1), (4, 4, 4), {"shared by 27 windows": (1, 2, 1), "in border windows that hold padding": (0, 0, 3), "last element of the map": (3, 3, 3)}),
+    ((1, 3, 3), (1, 2, 2), (2, 5, 6), {"shared by four windows": (1, 1, 2), "last of the last window, next to padding": (0, 4, 5)}),
+)
+POOL_EDGE_FORMS = (((1, 2, 2), (1, 2, 2)), ((3, 1, 1), (2, 1, 1)), ((2, 3, 1), (1, 3, 2)))
+POOL_EDGE_MAPS = (ODD_MAP, EVEN_MAP, (1, 1, 1))
+POOL_EDGE_C = 70   # an output row of channels crosses a 256-thread block
+
+STAGE_SIZES = ((1, 1), (224, 100), (100, 224), (225, 223), (300, 448), (7, 500))   # one-pixel, one scale 1, down, up, both at once
+
+FRECHET_EDGE_KINDS = ("equal_sigma", "graded", "scaled_up", "scaled_down")
+FRECHET_LANE_CASES = tuple((b, n, "shifted") for b in (63, 64, 65, 127, 128, 129, 255) for n in (1, 7, 400))
+FRECHET_KIND_CASES = tuple((b, 400, kind) for kind in FRECHET_EDGE_KINDS for b in (2, 3, 33, 64, 65, 256))
+FRECHET_EDGE_CASES = FRECHET_LANE_CASES + FRECHET_KIND_CASES
+GRADED_SPAN = 1e-9
+
+
+def _centred_factors(g, b, n):
+    """(U [b, b - 1] with orthonormal columns that sum to zero, Q [b - 1, n] with orthonormal rows), float64: U S Q is a centred table of
+    rank b - 1 whose singular values are the diagonal of S."""
+    a = torch.randn(b, b - 1, generator=g, dtype=torch.float64)
+    u = torch.linalg.qr(a - a.mean(dim=0))[0]
+    q = torch.linalg.qr(torch.randn(n, b - 1, generator=g, dtype=torch.float64))[0].t()
+    return u, q
+
+
+def edge_feature_tables(b, n, kind, seed=0):
+    """The kinds feature_tables() hands over to: "equal_sigma" (both centred tables multiples of one U Q: G = c (I - 1 1^T / b), b - 1 equal
+    singular values and the zero centring forces), "graded" (centred tables U S Q with S falling geometrically from 1 to 1e-9, own factors per
+    table; float32 storage lifts the smallest values to its rounding, about 1e-8), "scaled_up" / "scaled_down" ("shifted" times 2^20 / 2^-6)."""
+    if kind in ("scaled_up", "scaled_down"):
+        p, t = feature_tables(b, n, "shifted", seed)
+        f = 2.0 ** 20 if kind == "scaled_up" else 2.0 ** -6
+        return p * f, t * f
+    if b - 1 > n:
+        raise ValueError(f"{kind}: b - 1 <= n (got b={b}, n={n})")
+    g = torch.Generator().manual_seed(6000 + 17 * b + n + seed)
+    if kind == "equal_sigma":
+        u, q = _centred_factors(g, b, n)
+        e = u @ q
+        mp, mt = torch.randn(1, n, generator=g, dtype=torch.float64), torch.randn(1, n, generator=g, dtype=torch.float64)
+        return (3.0 * e + mp).float().contiguous(), (2.0 * e + mt).float().contiguous()
+    if kind == "graded":
+        s = torch.logspace(0, -9, b - 1, dtype=torch.float64) if b > 2 else torch.ones(1, dtype=torch.float64)
+        tables = []
+        for scale in (1.0, 1.5):
+            u, q = _centred_factors(g, b, n)
+            tables.append((scale * (u * s) @ q).float().contiguous())
+        return tuple(tables)
+    raise ValueError(f"unknown kind {kind!r}")
+
+
+def centred_sigma(table):
+    """Singular values (float64, descending) of the centred table."""
+    t = table.double()
+    return torch.linalg.svdvals(t - t.mean(dim=0))

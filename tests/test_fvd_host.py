@@ -142,6 +142,119 @@ def test_same_padding_rule_against_the_table(L):
     assert L.vpx_same_padding(0, 3, 1, ctypes.byref(front), ctypes.byref(out)) == E_ARG and L.vpx_same_padding(5, 3, 1, None, ctypes.byref(out)) == E_ARG
 
 
+def test_written_out_rule_equals_the_package(L):
+    """fvd_ref.same_rule, which the GPU edge tests build their expected maps from, against measure.same_pad and the library."""
+    for size in range(1, 21):
+        for k in range(1, 8):
+            for s in range(1, 5):
+                front, back, out = M.same_pad(size, k, s)
+                assert fvd_ref.same_rule(size, k, s) == (front, out) and ops.same_padding(size, k, s) == (front, back, out), (size, k, s)
+
+
+# ---- the case tables of tests/test_gpu_fvd_edges.py -----------------------------------------------------------------------------------
+def _tap_by_conv(x, tap, kernel, stride, co_count=fvd_ref.TAP_CO):
+    w = torch.zeros(co_count, x.shape[1], *kernel, dtype=torch.float64)
+    w[tap] = 1.0
+    return torch.nn.functional.conv3d(M._fvd_pad(x.double(), kernel, stride), w, stride=stride)
+
+
+def _shift_by(x, tap, outs, strides, fronts):
+    """x[:, ci] read at o * stride - front + d per axis, 0 outside the map: unit_tap_expected's arithmetic with the strides and front pads
+    handed in, to restate what a kernel with a mistake in them would write."""
+    y, keep = x[:, tap[1]], None
+    for axis, (out, s, f, d) in enumerate(zip(outs, strides, fronts, tap[2:])):
+        i = torch.arange(out) * s - f + d
+        ok = ((i >= 0) & (i < x.shape[2 + axis])).view([-1 if a == axis else 1 for a in range(3)])
+        keep = ok if keep is None else keep & ok
+        y = y.index_select(1 + axis, i.clamp(0, x.shape[2 + axis] - 1))
+    return torch.where(keep, y, torch.zeros(()))
+
+
+def test_unit_tap_expectation_is_a_shift():
+    """The index arithmetic of fvd_ref.unit_tap_expected against float64 F.conv3d with a one-hot weight (exact: one product by 1.0 per
+    output), the taps' reach over the channels, and what the table can tell apart: on the forms with sh != sw the expected maps differ from
+    those of a kernel that swapped the two strides, and on the forms with an odd total pad on some axis from those of one that put the
+    larger half of it in front."""
+    told_swap = told_front = 0
+    for form in fvd_ref.EDGE_FORMS:
+        kernel, stride, shape = form
+        assert kernel[1] != kernel[2] and len(set(kernel)) > 1
+        fronts, outs = zip(*(fvd_ref.same_rule(n, k, s) for n, k, s in zip(shape, kernel, stride)))
+        pads = [sum(M.same_pad(n, k, s)[:2]) for n, k, s in zip(shape, kernel, stride)]
+        swap_differs = front_differs = False
+        for ci_count in (3, 4):
+            taps = fvd_ref.unit_taps(kernel, ci_count)
+            assert len(taps) == 9 and {t[0] for t in taps} == set(range(fvd_ref.TAP_CO)) and {t[1] for t in taps} == set(range(ci_count))
+            assert all(0 <= d < k for t in taps for d, k in zip(t[2:], kernel))
+            x = fvd_ref.edge_conv_case(form, ci_count, fvd_ref.TAP_CO, 2)[0]
+            for tap in taps:
+                want, keep = fvd_ref.unit_tap_expected(x, fvd_ref.TAP_CO, tap, kernel, stride)
+                ref = _tap_by_conv(x, tap, kernel, stride)
+                assert want.shape == ref.shape and torch.equal(want.double(), ref), (form, tap)
+                assert int((want != 0).sum()) == 2 * int(keep.sum()) and torch.equal(_shift_by(x, tap, outs, stride, fronts), want[:, tap[0]])
+                swap_differs |= not torch.equal(_shift_by(x, tap, outs, (stride[0], stride[2], stride[1]), fronts), want[:, tap[0]])
+                front_differs |= not torch.equal(_shift_by(x, tap, outs, stride, [(p + 1) // 2 for p in pads]), want[:, tap[0]])
+        assert front_differs == any(p % 2 for p in pads) and swap_differs == (stride[1] != stride[2]), form
+        told_swap, told_front = told_swap + swap_differs, told_front + front_differs
+    assert told_swap >= 2 and told_front >= 2
+
+
+def test_edge_case_tables():
+    for form in fvd_ref.EDGE_FORMS + fvd_ref.ADJACENT_FORMS:
+        n = fvd_ref.ragged_batch(form)
+        m = fvd_ref.out_positions(form, n)
+        assert n in (3, 4) and m > 64 and m % 64 != 0, (form, n, m)
+    assert [fvd_ref.ragged_batch(f) for f in fvd_ref.EDGE_FORMS] == [3, 3, 4, 3]     # 2x7x5 under stride (1, 3, 2) has 18 outputs: 54 at N = 3
+    kernel, stride, shape = fvd_ref.EDGE_FORMS[1]
+    assert shape[2] < kernel[2] and fvd_ref.same_rule(shape[2], kernel[2], stride[2]) == (3, 3)   # every column: taps before AND behind the map
+    assert all(s > k for k, s in zip(*fvd_ref.EDGE_FORMS[3][:2])) and not any(s > k for k, s in zip(*fvd_ref.EDGE_FORMS[2][:2]))
+    counts = {}
+    for kernel, stride, shape, spots in fvd_ref.POOL_NAN_CASES:
+        for what, at in spots.items():
+            counts[(kernel, stride, what)] = int(fvd_ref.window_mask(shape, kernel, stride, at).sum())
+    assert counts[((3, 3, 3), (3, 3, 3), "first of a window")] == counts[((3, 3, 3), (3, 3, 3), "inner")] == counts[((3, 3, 3), (3, 3, 3), "last of a window")] == 1
+    assert counts[((3, 3, 3), (2, 2, 2), "shared by eight windows")] == 8 and counts[((3, 3, 3), (2, 2, 2), "shared by two")] == 2
+    assert counts[((3, 3, 3), (2, 2, 2), "inner of one")] == 1 and counts[((3, 3, 3), (2, 2, 2), "in a border window that holds padding")] == 1
+    assert counts[((3, 3, 3), (1, 1, 1), "shared by 27 windows")] == 27 and counts[((3, 3, 3), (1, 1, 1), "in border windows that hold padding")] == 8
+    assert counts[((3, 3, 3), (1, 1, 1), "last element of the map")] == 8 and counts[((1, 3, 3), (1, 2, 2), "shared by four windows")] == 4
+    assert counts[((1, 3, 3), (1, 2, 2), "last of the last window, next to padding")] == 1
+
+
+def test_frechet_edge_tables_and_what_the_reference_supports():
+    """The new kinds are what they claim to be, the old kinds' tables are untouched by them, and the float64 reference alone is good for
+    the bound the GPU test uses: permuting the rows of both tables (the same distance) moves it by less than a tenth of frechet_bound, and
+    the distance of the kinds that are not near zero by construction is more than 100 bounds away from zero."""
+    g = torch.Generator().manual_seed(3000 + 17 * 8 + 7)   # "shifted" restated: the existing kinds draw as they always did
+    p = torch.randn(8, 7, generator=g) * (torch.rand(1, 7, generator=g) * 2 + 0.5) + torch.randn(1, 7, generator=g)
+    assert torch.equal(fvd_ref.feature_tables(8, 7, "shifted")[0], p) and fvd_ref.FRECHET_KINDS == ("shifted", "identical", "rank1")
+    assert len(fvd_ref.FRECHET_EDGE_CASES) == 21 + 24
+    for b, n, kind in fvd_ref.FRECHET_EDGE_CASES:
+        p, t = fvd_ref.feature_tables(b, n, kind)
+        assert p.dtype == t.dtype == torch.float32 and p.shape == t.shape == (b, n) and bool(torch.isfinite(p).all() and torch.isfinite(t).all())
+        if kind in ("scaled_up", "scaled_down"):
+            f = 2.0 ** 20 if kind == "scaled_up" else 2.0 ** -6
+            p0, t0 = fvd_ref.feature_tables(b, n, "shifted")
+            assert torch.equal(p / f, p0) and torch.equal(t / f, t0)                  # exact in float32
+        if kind in ("equal_sigma", "graded"):
+            for table in (p, t):
+                s = fvd_ref.centred_sigma(table)
+                assert int((s > s[0] * 400 * 2.3e-16).sum()) == b - 1, (b, kind, s)   # rank b - 1: centring takes one, nothing else is lost
+                if kind == "equal_sigma":
+                    assert float(s[0] / s[b - 2]) < 1 + 1e-5
+                elif b > 2:
+                    assert float(s[0] / s[b - 2]) > 1e6 and float(s[b // 2] / s[0]) < 1e-3
+            if kind == "equal_sigma":
+                sg = torch.linalg.svdvals((p.double() - p.double().mean(0)) @ (t.double() - t.double().mean(0)).t())
+                assert float(sg[0] / sg[b - 2]) < 1 + 1e-5 and float(sg[b - 1]) < 1e-12 * float(sg[0])
+        ref = float(M.frechet_distance_host(p, t))
+        gp = torch.Generator().manual_seed(b + n)
+        moved = float(M.frechet_distance_host(p[torch.randperm(b, generator=gp)], t[torch.randperm(b, generator=gp)]))
+        bound = fvd_ref.frechet_bound(p, t)
+        assert abs(moved - ref) < 0.1 * bound, (b, n, kind, ref, moved, bound)
+        if kind in ("shifted", "scaled_up", "graded"):
+            assert abs(ref) > 100 * bound, (b, n, kind, ref, bound)
+
+
 # ---- the chunk rule ----------------------------------------------------------------------------------------------------------------
 def test_chunk_table_against_the_reference():
     table = _golden("fvd_chunks.npz")["table"]

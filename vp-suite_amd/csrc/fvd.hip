@@ -142,7 +142,7 @@ __global__ __launch_bounds__(FC_THREADS) void fvd_conv3d_kernel(FvConv a) {
         const long long mo = (long long)blockIdx.x * FC_M + wm + (v & 3) + 8 * (v >> 2) + 4 * hh;
         if (mo >= a.M) continue;
         float o = acc[v] + b;
-        if (a.relu) o = o > 0.0f ? o : 0.0f;
+        if (a.relu) o = (o > 0.0f || o != o) ? o : 0.0f;   // NaN stays NaN, as in torch; every other value as before, -0 included
         a.y[mo * a.ldy + a.coff + co] = o;
     }
 }
@@ -247,7 +247,10 @@ __global__ __launch_bounds__(FS_THREADS) void fvd_stage_kernel(FvStage a) {
 // d = fact sum Ep^2 + fact sum Et^2 - 2 sum_i sqrt(sigma_i^2 + 1e-15) + |mu_p - mu_t|^2, sigma_i the singular values of G = fact Ep Et^T
 // (b x b; E the centred tables, fact = 1 / (b - 1), 1 for b = 1). All of it in float64, every sum in one fixed order.
 constexpr int FD_MAX_B = 256;       // the cap on b: rows of a pair are held four elements per lane
-constexpr int FD_SWEEPS = 40;       // the fixed maximum of Jacobi sweeps (a sweep without a rotation ends the iteration; none within the maximum: NaN)
+// the fixed maximum of Jacobi sweeps (a sweep without a rotation ends the iteration; none within the maximum: NaN). Well-conditioned tables
+// end within 15 sweeps at b = 256; tables whose singular values fall over nine decades (G's over eighteen) need 28 at b = 64, 36 at 129 and
+// 44 .. 47 at 256 in this pair order, so the maximum leaves those a factor of 1.7
+constexpr int FD_SWEEPS = 80;
 constexpr int FD_THREADS = 1024, FD_WAVES = FD_THREADS / 64, FD_PER_LANE = FD_MAX_B / 64;
 constexpr double FD_EPS = 1e-15;    // the reference's constant under the square root
 constexpr double FD_TOL = 1e-13;    // rows count as orthogonal below this cosine: the error left in sum sigma is of its square
