@@ -170,6 +170,14 @@ int vpx_set_deterministic(int on);
  *                        rule of a `*_workspace_bytes` query that disagrees with the launch code returns VPX_ERR_WORKSPACE. For the
  *                        CPU test-suite (tests/test_workspace_contract.py). Leaves no state behind: switch it off again and launch. */
 #define VPX_OPT_DRY_RUN 5
+/*   VPX_OPT_SEQ_CHAINS   launch chains of vpx_convlstm_seq_fwd's time loop on the second-generation routes (CELL2, C3): 1 (default) = from
+ *                        B = 8 on, the two halves of the batch ([0, (B + 1) / 2) and the rest) as two chains of step launches, one on
+ *                        the caller's stream and one on a stream the library keeps per device, forked after the call's packs and joined
+ *                        before its final copies, so that one half's next step fills the tail of the other's; 2 = the same from B = 2
+ *                        on (tests, A/B runs); 0 = one chain on the caller's stream. All launch the kernel chosen for the whole call:
+ *                        results are bit-identical, workspace and reserve sizes the same. A call with B = 1, on another route or on a
+ *                        capturing stream runs one chain whatever the value (vpx_convlstm_seq_chains tells). */
+#define VPX_OPT_SEQ_CHAINS 6
 int vpx_set_option(int option, int value);
 /* A counter that advances with every vpx_set_option / vpx_set_deterministic call: callers that cache anything kernel-selection
  * dependent (a workspace with weight packs, VPX_FLAG_WEIGHTS_PACKED) key it on this value. */
@@ -222,6 +230,9 @@ typedef struct vpx_convlstm_plan_info {
     int32_t dgrad, dgrad_qform, d_mw, dgrad_cols, wgrad, n_slices, dG_f32, gate_slices;
 } vpx_convlstm_plan_info;
 int vpx_convlstm_plan(const vpx_convlstm_desc* d, int x_present, int want_dx, int want_dW, vpx_convlstm_plan_info* out);
+/* Launch chains (VPX_OPT_SEQ_CHAINS) a vpx_convlstm_seq_fwd call with this descriptor on `stream` would run right now: 2 or 1; 0 for a
+ * descriptor the call refuses. Asks the stream whether it is capturing (a dry run does not: it answers as for a stream that is not). */
+int vpx_convlstm_seq_chains(const vpx_convlstm_desc* d, int x_present, void* stream);
 
 /* ---- ST-LSTM cell step (PredRNN-V2) -------------------------------------------------------------------------- */
 size_t vpx_stlstm_workspace_bytes(const vpx_stlstm_desc* d);

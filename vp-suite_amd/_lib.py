@@ -32,6 +32,7 @@ OPT_CELL2 = 1
 OPT_CELL3 = 2
 OPT_EXPERIMENT = 4
 OPT_DRY_RUN = 5      # host-side work only, no HIP call (tests/test_workspace_contract.py)
+OPT_SEQ_CHAINS = 6   # a ConvLSTM sequence forward on CELL2 / C3 runs the batch halves as two launch chains: 1 from B = 8 on, 2 from B = 2 on, 0 never
 OPT_MFMA_SHAPE = 3   # 0: v_mfma_f32_32x32x16_bf16, 1: v_mfma_f32_16x16x32_bf16 in the second-generation kernels' main loop
 
 
@@ -148,6 +149,7 @@ SIGNATURES = {
     "vpx_convlstm_seq_fwd": (ci, [_clstm] + [vp] * 8 + [vp] * 3 + _rs_ws),                     # x h0 c0 W bias Wci Wcf Wco | out hT cT
     "vpx_convlstm_seq_bwd": (ci, [_clstm] + [vp] * 8 + [vp, sz] + [vp] * 3 + [vp] * 8 + _ws),  # x h0 c0 W Wci Wcf Wco out | reserve | dout dhT dcT | 8 gradients
     "vpx_convlstm_plan": (ci, [_clstm, ci, ci, ci, vp]),
+    "vpx_convlstm_seq_chains": (ci, [_clstm, ci, vp]),
     # ST-LSTM cell step
     "vpx_stlstm_workspace_bytes": (sz, [_stlstm]),
     "vpx_stlstm_reserve_bytes": (sz, [_stlstm]),

@@ -1,6 +1,8 @@
 // convlstm_fwd_api.hip — vpx_convlstm_seq_fwd and its queries (include/vpx.h). Host code only: the route of a call is decided once
 // (convlstm_route), one function carves the workspace for the call and for the size query (carve_fwd), each route has its own functions.
 #include "vpx_host.h"
+
+#include <mutex>
 using namespace vpx;
 
 // c3 (convq.hip: c5_kernel<NT, 3>, round 4): the fused step on 16x16-pixel tiles x (4 gates x NT * 4 channels) with 8-channel stages, for the
@@ -171,6 +173,11 @@ struct FwdCtx {
     bool save, wp, x_split, out_split;   // wp: the caller's workspace still holds every weight pack of an earlier call with the same descriptor, weights and operand set
     bool hoist_q; ConvQProblem hq;       // the hoisted projection runs on convq: `hq` is its problem
 };
+
+// A launch chain of the time loop: the samples [b0, b0 + B) of the call, step after step on one stream. Every operand of a step carries a
+// batch stride, so a chain is the call's base pointers advanced by b0 strides and a launch over B samples — of the kernel the route chose
+// for the WHOLE call (c.r, c.L: a chain never re-decides them from its own grid).
+struct Chain { int b0, B; hipStream_t stream; };
 
 // ---- layout adaptation (reference NCHW -> native NHWC) ----
 static int stage_in_nchw(FwdCtx& c) {
@@ -395,26 +402,27 @@ static int cell2_pack(FwdCtx& c) {
     if (c.h0) VPX_CHECK_HIP(launch_split_convert(c.h0, c.ws.h0_sp, (long long)d->B * (long long)c.HW, Ch, c.stream));
     return VPX_OK;
 }
-static int cell2_step(const FwdCtx& c, int t, ConvLSTMStepArgs ea) {
-    const vpx_convlstm_desc* d = c.d; const int T = d->T, Cin = d->Cin, Ch = d->Ch; const size_t HW = c.HW;
+static int cell2_step(const FwdCtx& c, int t, ConvLSTMStepArgs ea, const Chain& ch) {
+    const vpx_convlstm_desc* d = c.d; const int T = d->T, Cin = d->Cin, Ch = d->Ch; const size_t HW = c.HW, b0 = (size_t)ch.b0;
     Cell2Plan P2{};
-    P2.B = d->B; P2.H = d->H; P2.W = d->W; P2.tiles_x = (d->W + 15) / 16; P2.tiles_y = (d->H + 31) / 32; P2.n_tiles = c.L->n_tiles;
+    P2.B = ch.B; P2.H = d->H; P2.W = d->W; P2.tiles_x = (d->W + 15) / 16; P2.tiles_y = (d->H + 31) / 32; P2.n_tiles = c.L->n_tiles;
     P2.chunks_total = 3 * ((Cin + Ch) / 16); P2.wpk = c.ws.wpk2;
     P2.qform = c.r.qform; P2.plain = d->precision == VPX_PREC_BF16 ? 1 : 0;
     const long long hsp_bs = c.out_split ? (long long)((size_t)T * HW * Ch * 4) : (long long)(HW * Ch * 4);
     // OUT_SPLIT: no fp32 sequence; the last step still hands h_T out in fp32 where the caller wants it
-    if (c.out_split) { ea.h_out = (t == T - 1) ? c.hT : nullptr; ea.h_bstride = (long long)(HW * Ch); }
+    if (c.out_split) { ea.h_out = (t == T - 1 && c.hT) ? c.hT + b0 * HW * Ch : nullptr; ea.h_bstride = (long long)(HW * Ch); }
     const char* hprev_sp = (t == 0) ? (c.h0 ? c.ws.h0_sp : nullptr) : cell2_h_slot(c, t - 1);
     P2.seg[0] = Cell2Seg{c.x ? c.ws.x_sp + (size_t)t * HW * Cin * 4 : nullptr, (long long)((size_t)T * HW * Cin * 4), Cin, 0};
     P2.seg[1] = Cell2Seg{hprev_sp, (t == 0) ? (long long)(HW * Ch * 4) : hsp_bs, Ch, 0};
+    for (Cell2Seg& sg : P2.seg) if (sg.sp) sg.sp += b0 * (size_t)sg.bstride;   // the chain's first sample
     P2.nx = c.x ? Cin / 16 : 0; P2.nh = hprev_sp ? Ch / 16 : 0; P2.hs_off = Cin / 16;
     if (c.r.qform) {   // the pack of this step's operand set
         P2.chunks_total = cell2_qchunks(P2.nx + P2.nh);
         P2.wpk = cell2_pack_of(c, (P2.nx ? 1 : 0) | (P2.nh ? 2 : 0));
     }
     // the split copy of h_t feeds step t+1 only: the last step does not need it
-    char* const hsp_t = (t + 1 < T || c.out_split) ? cell2_h_slot(c, t) : nullptr;
-    if (c.r.route == Route::CELL2) { VPX_CHECK_HIP(launch_cell2(P2, ea, hsp_t, hsp_bs, c.stream)); return VPX_OK; }
+    char* const hsp_t = (t + 1 < T || c.out_split) ? cell2_h_slot(c, t) + b0 * (size_t)hsp_bs : nullptr;
+    if (c.r.route == Route::CELL2) { VPX_CHECK_HIP(launch_cell2(P2, ea, hsp_t, hsp_bs, ch.stream)); return VPX_OK; }
     C5Plan cp{};   // C3: the same step as one job of the c5 machinery
     cp.B = P2.B; cp.H = P2.H; cp.W = P2.W; cp.ks = 3;
     cp.src[0] = C5Src{P2.seg[0].sp, P2.seg[0].bstride, Cin * 4, 0};
@@ -427,29 +435,84 @@ static int cell2_step(const FwdCtx& c, int t, ConvLSTMStepArgs ea) {
     for (int g = 0; g < 4; ++g) j.gate_pos[g] = ea.gate_pos[g];
     j.e_out[0] = ea.h_out; j.e_out[1] = ea.c_out; j.h_bstride = ea.h_bstride;
     j.e_sp = hsp_t; j.sp_bstride = hsp_bs;
-    const int rcj = c5_prepare_job(j, c.r.c3nt, nullptr, 4, 0, true, c.stream, 0, 3);   // (derived fields only: the pack is in place)
+    const int rcj = c5_prepare_job(j, c.r.c3nt, nullptr, 4, 0, true, ch.stream, 0, 3);   // (derived fields only: the pack is in place)
     if (rcj) return rcj;
-    VPX_CHECK_HIP(launch_c5(cp, c.r.c3nt, c.stream));
+    VPX_CHECK_HIP(launch_c5(cp, c.r.c3nt, ch.stream));
     return VPX_OK;
 }
 
 // ---- the entry point: what every route's step is handed: bias, peepholes, where c and h of step t go, and the saved gates
-static ConvLSTMStepArgs step_args(const FwdCtx& c, int t) {
-    const size_t n = c.L->n_state;
+// ... of the chain's samples: the per-sample tensors (c, gates, h) start at sample ch.b0, bias and peepholes are shared
+static ConvLSTMStepArgs step_args(const FwdCtx& c, int t, const Chain& ch) {
+    const size_t n = c.L->n_state, off = (size_t)ch.b0 * c.HW * c.d->Ch;   // off: sample b0 of a [B][HW][Ch] tensor
     ConvLSTMStepArgs ea{};
     ea.bias = c.bias; ea.Ch = c.d->Ch;
     memcpy(ea.gate_pos, c.gp, sizeof(c.gp));
     if (c.save) {   // c_t and the gates of every step stay in the reserve
         ea.c_in = (t == 0) ? c.c0 : c.res.cs + (size_t)(t - 1) * n;
-        ea.c_out = c.res.cs + (size_t)t * n; ea.gates = c.res.gates + (size_t)t * n * 4;
+        ea.c_out = c.res.cs + (size_t)t * n + off; ea.gates = c.res.gates + (size_t)t * n * 4 + 4 * off;
     } else {
-        ea.c_in = (t == 0) ? c.c0 : c.ws.c_scratch;
-        ea.c_out = (t == c.d->T - 1 && c.cT) ? c.cT : c.ws.c_scratch;  // the last step writes c_T where the caller wants it
+        ea.c_in = (t == 0) ? c.c0 : c.ws.c_scratch;   // (updated in place per sample: each chain walks its own slice)
+        ea.c_out = ((t == c.d->T - 1 && c.cT) ? c.cT : c.ws.c_scratch) + off;  // the last step writes c_T where the caller wants it
     }
+    if (ea.c_in) ea.c_in += off;
     ea.wci = c.wci; ea.wcf = c.wcf; ea.wco = c.wco;
-    ea.h_out = c.out + (size_t)t * c.HW * c.d->Ch;
     ea.h_bstride = (long long)((size_t)c.d->T * c.HW * c.d->Ch);
+    ea.h_out = c.out + (size_t)t * c.HW * c.d->Ch + (size_t)ch.b0 * (size_t)ea.h_bstride;
     return ea;
+}
+
+// ---- two launch chains ----
+// One launch per step on one stream leaves holes nothing of the same call can fill: step t + 1 waits for the last workgroup of step t, so
+// a launch's tail (CUs down to one workgroup), its cold-weights prologue and, on the 16x16 maps' 384 workgroups for 512 slots, a quarter
+// of the chip are idle. The samples of a batch are independent through the whole sequence: the CELL2 and C3 routes run the two halves of
+// the batch as two chains, chain 0 on the caller's stream, chain 1 on a stream of the library's, issued step by step in turn. Each chain
+// launches the kernel the whole call chose, on its own samples: results are bit for bit those of the single chain, the workspace and the
+// reserve are those of the whole call. vpx_set_option(VPX_OPT_SEQ_CHAINS, 0) keeps the single chain (A/B runs, tests); a capturing
+// stream takes it too (the captured graph then holds no stream of the library's).
+// The batch floor (convlstm-shi inference, ms per forward, one chain -> two, medians; DESIGN.md §4 has every run): B = 128 23.03 -> 22.67 and
+// 22.85 -> 22.51 (two sessions), B = 64 11.72 -> 11.50, B = 32 6.34 -> 6.25, B = 16 3.59 -> 3.27, B = 8 2.366 -> 2.345, but B = 4 1.53 -> 1.67:
+// there the chained launches are C3's, 128 workgroups that already leave half the chip empty, and twice the launches plus the fork and
+// the join cost more than there is to fill. VPX_OPT_SEQ_CHAINS = 2 chains from B = 2 on (tests).
+constexpr int SEQ_CHAINS_MIN_B = 8;
+static int seq_chains(const vpx_convlstm_desc* d, const RouteChoice& r, hipStream_t stream) {
+    if (!on_cell2(r) || g_seq_chains == 0 || d->B < (g_seq_chains == 2 ? 2 : SEQ_CHAINS_MIN_B)) return 1;
+    if (g_dry_run) return 2;   // (no HIP call: the chains' host-side work runs, on the caller's stream handle)
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &st) != hipSuccess) { (void)hipGetLastError(); return 1; }
+    return st == hipStreamCaptureStatusNone ? 2 : 1;
+}
+// The side stream of a device and the two events of a fork / join, created on first use and kept. Non-blocking: the caller's stream may be
+// the null stream, which every blocking stream synchronises with launch by launch. The events are shared by every call on the device, so
+// a record and the wait that belongs to it are issued under the lock (a wait takes the event's record as of that moment).
+struct SeqSide { hipStream_t stream; hipEvent_t fork, join; bool made; };
+static std::mutex g_side_mutex;
+static SeqSide g_side[64];
+static int seq_side(SeqSide*& out) {
+    int dev = 0;
+    VPX_CHECK_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64) { set_error("vpx_convlstm_seq_fwd: device %d beyond the side-stream table", dev); return VPX_ERR_UNSUPPORTED; }
+    std::lock_guard<std::mutex> lock(g_side_mutex);
+    SeqSide& sd = g_side[dev];
+    if (!sd.made) {
+        VPX_CHECK_HIP(hipStreamCreateWithFlags(&sd.stream, hipStreamNonBlocking));
+        VPX_CHECK_HIP(hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming));
+        VPX_CHECK_HIP(hipEventCreateWithFlags(&sd.join, hipEventDisableTiming));
+        sd.made = true;
+    }
+    out = &sd;
+    return VPX_OK;
+}
+// `to` goes on only after everything issued to `from` so far
+static hipError_t seq_order(hipEvent_t ev, hipStream_t from, hipStream_t to) {
+    std::lock_guard<std::mutex> lock(g_side_mutex);
+    const hipError_t e = hipEventRecord(ev, from);
+    return e != hipSuccess ? e : hipStreamWaitEvent(to, ev, 0);
+}
+extern "C" int vpx_convlstm_seq_chains(const vpx_convlstm_desc* d, int x_present, void* stream) {
+    ConvLSTMLayout L;
+    if (check_convlstm_desc(d) != VPX_OK || convlstm_layout(d, L) != VPX_OK) return 0;
+    return seq_chains(d, convlstm_route(d, L, x_present != 0), (hipStream_t)stream);
 }
 extern "C" int vpx_convlstm_seq_fwd(const vpx_convlstm_desc* d, const float* x, const float* h0, const float* c0,
                                     const float* W, const float* bias, const float* Wci, const float* Wcf, const float* Wco,
@@ -493,17 +556,37 @@ extern "C" int vpx_convlstm_seq_fwd(const vpx_convlstm_desc* d, const float* x, 
     if (rc != VPX_OK) return rc;
     if ((c.r.route == Route::HOIST || c.r.route == Route::CELL3) && c.x && (rc = hoisted_projection(c)) != VPX_OK) return rc;
     // ---- time loop: one fused conv + gate + state-update launch per step (KSPLIT, HOIST: a convolution and the pointwise kernel) ----
-    for (int t = 0; t < d->T; ++t) {
-        const ConvLSTMStepArgs ea = step_args(c, t);
-        switch (c.r.route) {
-            case Route::FUSED: rc = fused_step(c, t, ea); break;
-            case Route::KSPLIT: rc = ksplit_step(c, t, ea); break;
-            case Route::HOIST: rc = hoist_step(c, t, ea); break;
-            case Route::CELL3: rc = cell3_step(c, t, ea); break;
-            case Route::CELL2: case Route::C3: rc = cell2_step(c, t, ea); break;
+    // CELL2, C3: the batch as two chains of such launches (seq_chains), chain 1 forked from the caller's stream here and joined below
+    Chain chain[2] = {{0, d->B, c.stream}, {0, 0, c.stream}};
+    const int nchain = seq_chains(d, c.r, c.stream);
+    SeqSide* side = nullptr;
+    if (nchain == 2) {
+        chain[0].B = (d->B + 1) / 2;
+        chain[1].b0 = chain[0].B; chain[1].B = d->B - chain[0].B;
+        if (!g_dry_run) {
+            if ((rc = seq_side(side)) != VPX_OK) return rc;
+            VPX_CHECK_HIP(c5_flush_packs(c.stream));   // (C3's packs wait for the first launch: chain 1 must find them behind the fork)
+            VPX_CHECK_HIP(seq_order(side->fork, c.stream, side->stream));
+            chain[1].stream = side->stream;
         }
-        if (rc != VPX_OK) return rc;
     }
+    for (int t = 0; t < d->T && rc == VPX_OK; ++t)
+        for (int k = 0; k < nchain && rc == VPX_OK; ++k) {   // A(t), B(t), A(t + 1), ...: neither queue runs dry on the host side
+            const Chain& ch = chain[k];
+            const ConvLSTMStepArgs ea = step_args(c, t, ch);
+            switch (c.r.route) {
+                case Route::FUSED: rc = fused_step(c, t, ea); break;
+                case Route::KSPLIT: rc = ksplit_step(c, t, ea); break;
+                case Route::HOIST: rc = hoist_step(c, t, ea); break;
+                case Route::CELL3: rc = cell3_step(c, t, ea); break;
+                case Route::CELL2: case Route::C3: rc = cell2_step(c, t, ea, ch); break;
+            }
+        }
+    if (side) {   // also after a failed launch: nothing of the call stays outstanding outside the caller's stream
+        const hipError_t ej = seq_order(side->join, side->stream, c.stream);
+        if (rc == VPX_OK) VPX_CHECK_HIP(ej);
+    }
+    if (rc != VPX_OK) return rc;
     // ---- final states ----
     const int B = d->B, T = d->T, Ch = d->Ch;
     if (c.cT && c.save)

@@ -55,6 +55,7 @@ int g_deterministic = 0;
 int g_cell3_mode = 1;
 int g_cell2_mode = 1;
 int g_experiment = 0;
+int g_seq_chains = 1;   // (convlstm_fwd_api.hip, seq_chains; the measurements behind the default and its batch floor: DESIGN.md §4)
 int g_mfma_shape = 1;   // measured (tools/ab_shape.py, B=128, one process, interleaved): 1.05-1.11x per fused step, every block shape
 
 }  // namespace vpx
@@ -88,6 +89,11 @@ int vpx_set_option(int option, int value) {
     if (option == VPX_OPT_DRY_RUN) {
         const int prev = vpx::g_dry_run;
         vpx::g_dry_run = value ? 1 : 0;
+        return prev;
+    }
+    if (option == VPX_OPT_SEQ_CHAINS) {
+        const int prev = g_seq_chains;
+        vpx::g_seq_chains = value < 0 ? 0 : (value > 2 ? 2 : value);
         return prev;
     }
     if (option == VPX_OPT_CELL3) {

@@ -218,6 +218,7 @@ size_t cell2_packed_bytes_q(int n_tiles, int S);             // q form: cell2_qc
 extern int g_experiment;   // vpx_api.hip: VPX_EXP_* bits of kernel experiments in flight (vpx_set_option(VPX_OPT_EXPERIMENT)); 0 in the product
 static inline bool exp_on(int bit) { return (g_experiment & bit) != 0; }   // the one reader of the selection bits
 extern int g_mfma_shape;   // vpx_api.hip: 0 / 1 (vpx_set_option(VPX_OPT_MFMA_SHAPE)), default 1
+extern int g_seq_chains;   // vpx_api.hip: 0 / 1 / 2 (vpx_set_option(VPX_OPT_SEQ_CHAINS)), default 1: two launch chains of a ConvLSTM sequence forward on CELL2 / C3
 hipError_t launch_cell2(const Cell2Plan& plan, const ConvLSTMStepArgs& ea, void* h_sp, long long h_sp_bstride, hipStream_t s);
 // the same step on the eight-wave half tile (cell2x.hip, round 6: 64-register wave tiles, four waves per SIMD); plan.qform launches only
 // (maps in whole 16x16 tiles, whole 32-channel N tiles), tiles_y / grid_m set for 16-row tiles. VPX_EXP_CELL2X selects it
