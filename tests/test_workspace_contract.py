@@ -573,6 +573,150 @@ def test_small_workspaces(L):
     _ok(L, L.vpx_mse_loss(_fake(1), _fake(2), 128 * 10 * 64 * 64, 1280, 1.0, _fake(3), _fake(4), ctypes.c_void_p(WS_BASE), nb, None), "mse", False)
 
 
+# ---- the small operators: each query measures the carve its call runs (csrc: carve_rconv_fwd, carve_merge_bwd, carve_ssim, ...) ----------
+def _exact(L, what, nb, call):
+    """The queried size is accepted at an aligned and at an odd base; one byte less is refused with VPX_ERR_WORKSPACE."""
+    assert nb > 0, (what, L.vpx_last_error())
+    for base in (WS_BASE, WS_BASE_ODD):
+        _ok(L, call(ctypes.c_void_p(base), nb), f"{what} base={base:#x}", allow_unsupported=False)
+    assert call(ctypes.c_void_p(WS_BASE), nb - 1) == E_WS, what
+
+
+RC_PIX, RC_VEC, RC_SLAB_FLOATS = 256, 4, 4 << 20          # csrc/unet3d.hip
+# (B, T, H, W, Ca, Cb, Co, kt, mode): one and two sources, kt 1 / 3 and the collapse, Co off RC_VEC, npix = 2, 127, 128, 129 (the slice
+# rule's /128), more than one RC_PIX block, and weights whose size caps the slices: 37 of 40 wanted (64 -> 64, 27 taps), 1 of 2 (512 -> 256)
+RCONV_DESCS = ([(1, 1, 1, npix, Ca, Cb, Co, 1, 0) for npix in (2, 127, 128, 129) for (Ca, Cb, Co) in ((3, 0, 5), (4, 6, 8))] +
+               [(2, 1, 9, 15, 8, 0, 7, 1, 0), (1, 4, 9, 15, 6, 3, 10, 3, 0), (2, 4, 9, 15, 5, 0, 5, 4, 1), (1, 3, 1, 2, 4, 4, 6, 3, 1),
+                (1, 5, 32, 32, 64, 0, 64, 3, 0), (1, 1, 3, 43, 256, 256, 256, 3, 0)])
+
+
+def _rconv_slices(B, T, H, W, Ca, Cb, Co, kt, mode):      # the slice rule, written out: (wanted, the weight's cap)
+    npix = B * (1 if mode else T) * H * W
+    nel = kt * (1 if mode else 9) * Co * (Ca + Cb) + Co
+    return min((npix + 127) // 128, 256), RC_SLAB_FLOATS // nel
+
+
+def test_rconv_and_bn_relu(L):
+    from vp_suite_amd._lib import RConvDesc
+    assert [c for c in RCONV_DESCS if _rconv_slices(*c)[1] < _rconv_slices(*c)[0]] == RCONV_DESCS[-2:]
+    assert any(c[6] % RC_VEC for c in RCONV_DESCS) and any(c[0] * c[1] * c[2] * c[3] > RC_PIX for c in RCONV_DESCS)
+    for c in RCONV_DESCS:
+        d = RConvDesc(*c)
+        b = _fake(2) if c[5] else None
+        for epi in (_lib.RCONV_EPI_PLAIN, _lib.RCONV_EPI_EVAL, _lib.RCONV_EPI_STATS):
+            _exact(L, f"rconv fwd {c} epilogue={epi}", L.vpx_rconv_workspace_bytes(ctypes.byref(d), epi),
+                   lambda ws, nb: L.vpx_rconv_fwd(ctypes.byref(d), epi, _fake(1), b, _fake(3), _fake(4), _fake(5), _fake(6), _fake(7), 1e-5, 0.1,
+                                                  _fake(8), _fake(9), ws, nb, None))
+        for (da, db, dw, dbias) in ((1, 1, 1, 1), (1, 0, 0, 0), (0, 0, 1, 0), (0, 0, 0, 1)):
+            _exact(L, f"rconv bwd {c} wanted={(da, db, dw, dbias)}", L.vpx_rconv_bwd_workspace_bytes(ctypes.byref(d)),
+                   lambda ws, nb: L.vpx_rconv_bwd(ctypes.byref(d), _fake(1), b, _fake(3), _fake(4), _fake(5) if da else None,
+                                                  _fake(6) if db and c[5] else None, _fake(7) if dw else None, _fake(8) if dbias else None, ws, nb, None))
+    # N*H*W = 1, one below / at / one above a multiple of RC_PIX, several blocks
+    for (N, H, W), C in itertools.product(((1, 1, 1), (3, 5, 17), (1, 16, 16), (1, 1, 257), (2, 2, 128), (5, 33, 31)), (1, 6, 64)):
+        for (dact, dpool) in ((1, 0), (1, 1), (0, 1)):
+            if dpool and (H & 1 or W & 1):
+                continue
+            _exact(L, f"bn_relu bwd {(N, H, W, C)} dact={dact} dpool={dpool}", L.vpx_bn_relu_bwd_workspace_bytes(N, H, W, C),
+                   lambda ws, nb: L.vpx_bn_relu_bwd(_fake(1), _fake(2), _fake(3), _fake(4), _fake(5) if dact else None, _fake(6) if dpool else None,
+                                                    _fake(7), _fake(8), _fake(9), N, H, W, C, ws, nb, None))
+
+
+MERGE_SHAPES = [(8, 24, 16), (24, 8, 16), (16, 16, 16), (32, 96, 64), (96, 32, 64), (64, 64, 64), (64, 160, 96), (3, 5, 7)]   # (Cs, Cp, Co)
+
+
+def test_merge1x1(L):
+    """Cs < Cp, Cs > Cp and Cs == Cp, on both sides of the 64-channel bar of the weight gradient's slice cap; 1x1 and 67x83 maps."""
+    for (Cs, Cp, Co), (N, H, W), prec in itertools.product(MERGE_SHAPES, ((1, 1, 1), (2, 67, 83), (128, 16, 16)), (0, 1)):
+        tag = f"merge1x1 {(Cs, Cp, Co)} geo={(N, H, W)} prec={prec}"
+        _exact(L, tag + " fwd", L.vpx_merge1x1_workspace_bytes(Cs, Cp, Co),
+               lambda ws, nb: L.vpx_merge1x1_fwd(_fake(1), _fake(2), _fake(3), _fake(4), _fake(5), N, H, W, Cs, Cp, Co, prec, ws, nb, None))
+        for (da, db, dw, dbias) in ((1, 1, 1, 1), (0, 0, 1, 0), (1, 1, 0, 0), (0, 0, 0, 1)):
+            _exact(L, tag + f" bwd wanted={(da, db, dw, dbias)}", L.vpx_merge1x1_bwd_workspace_bytes(N, H, W, Cs, Cp, Co),
+                   lambda ws, nb: L.vpx_merge1x1_bwd(_fake(1), _fake(2), _fake(3), _fake(4), _fake(5) if da else None, _fake(6) if db else None,
+                                                     _fake(7) if dw else None, _fake(8) if dbias else None, N, H, W, Cs, Cp, Co, prec, ws, nb, None))
+
+
+PM_CHUNK, SS_TAPS, SS_TH, SS_TW = 256 * 16, 11, 16, 32     # csrc/measure.hip
+# the SSIM map is (H - 10) x (W - 10): one entry, one tile exactly, one entry more than a tile in either direction and in both, non-square maps
+SSIM_SIZES = [(SS_TAPS, SS_TAPS), (SS_TH + 10, SS_TW + 10), (SS_TH + 11, SS_TW + 10), (SS_TH + 10, SS_TW + 11), (SS_TH + 11, SS_TW + 11),
+              (SS_TAPS, 100), (75, 13), (64, 64), (67, 83)]
+
+
+def test_pixel_measures_and_ssim(L):
+    for n_frames, elems in itertools.product((1, 3, 40), (1, PM_CHUNK - 1, PM_CHUNK, PM_CHUNK + 1, 3 * 67 * 83)):
+        _exact(L, f"pixel_measures {(n_frames, elems)}", L.vpx_pixel_measures_workspace_bytes(n_frames, elems),
+               lambda ws, nb: L.vpx_pixel_measures_fwd(_fake(1), _fake(2), n_frames, elems, _fake(3), ws, nb, None))
+    for n_frames, (H, W), layout in itertools.product((1, 3, 40), SSIM_SIZES, (0, 1)):
+        _exact(L, f"ssim {(n_frames, H, W)} layout={layout}", L.vpx_ssim_workspace_bytes(n_frames, H, W),
+               lambda ws, nb: L.vpx_ssim_fwd(_fake(1), _fake(2), n_frames, 3, H, W, layout, _fake(3), ws, nb, None))
+    assert L.vpx_ssim_workspace_bytes(1, SS_TAPS - 1, 64) == 0 and L.vpx_ssim_workspace_bytes(1, 64, SS_TAPS - 1) == 0
+
+
+def test_groupnorm_bwd(L):
+    """With dgamma / dbeta the partial sums need the queried size; without them there is nothing to carve and a NULL workspace is accepted."""
+    for (N, HW, C, G), act in itertools.product(((1, 1, 1, 1), (2, 64, 16, 4), (3, 67 * 83, 24, 3), (128, 256, 64, 16), (5, 7, 256, 1)), (0, 1)):
+        def call(ws, nb, params=True):
+            return L.vpx_groupnorm_bwd(_fake(1), _fake(2), _fake(3), _fake(4), _fake(5), _fake(6), _fake(7) if params else None,
+                                       _fake(8) if params else None, N, HW, C, G, act, 0.2, ws, nb, None)
+        _exact(L, f"groupnorm bwd {(N, HW, C, G)} act={act}", L.vpx_groupnorm_bwd_workspace_bytes(N, C), call)
+        assert call(None, L.vpx_groupnorm_bwd_workspace_bytes(N, C)) == E_WS
+        _ok(L, call(None, 0, params=False), f"groupnorm bwd {(N, HW, C, G)} without dgamma / dbeta", allow_unsupported=False)
+
+
+MSE_BLOCK, MSE_MAX_BLOCKS, GS_BLOCK, GS_MAX_BLOCKS = 256 * 4, 1024, 256 * 4, 1024     # csrc/train_tail.hip: elements per block, block cap
+
+
+def test_mse_and_grad_stats(L):
+    """One element, the last n whose blocks are all launched, the first beyond the block cap, and far beyond it."""
+    for n in (1, MSE_BLOCK * MSE_MAX_BLOCKS, MSE_BLOCK * MSE_MAX_BLOCKS + 1, 1 << 33):
+        for dpred in (_fake(4), None):
+            _exact(L, f"mse n={n}", L.vpx_mse_loss_workspace_bytes(),
+                   lambda ws, nb: L.vpx_mse_loss(_fake(1), _fake(2), n, 1 + n % 7, 1.0, _fake(3), dpred, ws, nb, None))
+    for n in (1, GS_BLOCK * GS_MAX_BLOCKS, GS_BLOCK * GS_MAX_BLOCKS + 1, 1 << 33):
+        _exact(L, f"grad_stats n={n}", L.vpx_grad_stats_workspace_bytes(),
+               lambda ws, nb: L.vpx_grad_stats(_fake(1), n, 1.0, _fake(2), ws, nb, None))
+
+
+def test_layernorm(L):
+    """One query for both directions: the larger carve (the backward's); each direction carves its own slots out of it."""
+    for B, (HW, C) in itertools.product((1, 2, 63, 64, 65, 128), ((1, 1), (35, 20), (256, 128))):
+        nb = L.vpx_layernorm_workspace_bytes(B)
+        _exact(L, f"layernorm fwd B={B} n={HW * C}", nb,
+               lambda ws, nb: L.vpx_layernorm_fwd(_fake(1), _fake(2), _fake(3), _fake(4), _fake(5), _fake(6), B, HW * C, ws, nb, None))
+        _exact(L, f"layernorm bwd B={B} {(HW, C)}", nb,
+               lambda ws, nb: L.vpx_layernorm_bwd(_fake(1), _fake(2), _fake(3), _fake(4), _fake(5), _fake(6), _fake(7), B, HW, C, ws, nb, None))
+
+
+HD_PIX = 64     # csrc/lpips.hip: pixels per workgroup of the head
+
+
+def test_lpips_stem_and_head(L):
+    for (n0, n1), (H, W) in itertools.product(((1, 0), (2, 2), (16, 16)), ((7, 7), (31, 33), (64, 64), (67, 83))):
+        _exact(L, f"lpips stem fwd {(n0, n1, H, W)}", L.vpx_lpips_stem_workspace_bytes(),
+               lambda ws, nb: L.vpx_lpips_stem_fwd(_fake(1), _fake(2) if n1 else None, n0, n1, H, W, _fake(3), _fake(4), _fake(5), ws, nb, None))
+        _exact(L, f"lpips stem bwd {(n0, H, W)}", L.vpx_lpips_stem_workspace_bytes(),
+               lambda ws, nb: L.vpx_lpips_stem_bwd(_fake(1), _fake(2), _fake(3), n0, H, W, _fake(4), ws, nb, None))
+    for n, HW, C in itertools.product((1, 3, 40), (1, HD_PIX - 1, HD_PIX, HD_PIX + 1, 3 * HD_PIX - 1, 3 * HD_PIX, 3 * HD_PIX + 1, 15 * 15), (1, 64, 384)):
+        _exact(L, f"lpips head {(n, HW, C)}", L.vpx_lpips_head_workspace_bytes(n, HW),
+               lambda ws, nb: L.vpx_lpips_head_fwd(_fake(1), _fake(2), _fake(3), n, HW, C, _fake(4), ws, nb, None))
+
+
+def test_fvd_features(L):
+    """The table tests/test_fvd_host.py builds, one and two clip sets (its own dry run holds the refusals)."""
+    import fvd_ref
+    from vp_suite_amd import measure as M
+    M.register_fvd_weights(fvd_ref.state_dict())
+    try:
+        trunk = M._fvd_trunk("cpu")
+        table, rows, n_params = trunk["table"], trunk["n_rows"], len(trunk["params"])
+        params = (ctypes.c_void_p * n_params)(*[0x200000000000 + i * (1 << 30) for i in range(n_params)])
+        for (n0, n1), (T, h, w) in itertools.product(((1, 0), (3, 0), (1, 1), (2, 5)), ((9, 20, 28), (16, 64, 64), (12, 224, 224), (10, 67, 83))):
+            _exact(L, f"fvd_features {(n0, n1, T, h, w)}", L.vpx_fvd_features_workspace_bytes(n0 + n1, T, 3, h, w, table, rows),
+                   lambda ws, nb: L.vpx_fvd_features(_fake(1), _fake(2) if n1 else None, n0, n1, T, 3, h, w, table, rows, params, n_params, _fake(3), ws, nb, None))
+    finally:
+        M.clear_fvd_weights()
+
+
 def test_random_shapes_fuzz():
     """tools/fuzz_contract.py: 4 000 random descriptors (odd map sizes, channel counts that are multiples of nothing, every kernel size,
     layout, operand mode and option bit) through every entry point that takes a workspace, in its own process (it switches the library

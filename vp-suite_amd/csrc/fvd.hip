@@ -521,6 +521,12 @@ static int fv_features_check(const char* who, long long n0, long long n1, int T,
     return VPX_OK;
 }
 
+// the trunk's buffers, each as large as the walk found its largest map
+template <class WS>
+static void carve_fvd(WS& ws, const size_t floats[FV_BUFS], float* buf[FV_BUFS]) {
+    for (int i = 0; i < FV_BUFS; ++i) buf[i] = ws.take(floats[i]);
+}
+
 static int fd_check(const char* who, int b, int n) {
     if (b < 1 || n < 1) { set_error("%s: b and n must be >= 1 (got %d, %d)", who, b, n); return VPX_ERR_ARG; }
     if (b > FD_MAX_B) { set_error("%s: %d feature vectors per set, this build supports at most %d", who, b, FD_MAX_B); return VPX_ERR_UNSUPPORTED; }
@@ -584,8 +590,8 @@ size_t vpx_fvd_features_workspace_bytes(long long n_clips, int T, int C, int h, 
     size_t floats[FV_BUFS];
     int F = 0;
     if (fv_walk(who, n_clips, T, C, table, n_rows, nullptr, 0, nullptr, nullptr, floats, &F, nullptr) != VPX_OK) return 0;
-    CarveMeasure m;
-    for (int i = 0; i < FV_BUFS; ++i) m.take(floats[i]);
+    CarveMeasure m; float* buf[FV_BUFS];
+    carve_fvd(m, floats, buf);
     return m.off + 256;
 }
 
@@ -602,7 +608,7 @@ int vpx_fvd_features(const float* x0, const float* x1, long long n0, long long n
     if (!workspace || !need || workspace_bytes < need) { set_error("%s: workspace too small", who); return VPX_ERR_WORKSPACE; }
     Carver ws(workspace, workspace_bytes);
     float* buf[FV_BUFS];
-    for (int i = 0; i < FV_BUFS; ++i) buf[i] = ws.take(floats[i]);
+    carve_fvd(ws, floats, buf);
     VPX_CHECK_CARVE(ws, who);
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = fv_stage(who, x0, x1, n0, n1, T, C, h, w, buf[0], stream)) return rc;

@@ -126,6 +126,14 @@ static int gn_check_shape(const char* who, int N, int HW, int C, int G) {
     return VPX_OK;
 }
 
+// The backward's workspace (only a call that wants dgamma / dbeta has one): their per-image partial sums, [2][N][C]
+struct GnBwdSlots { float* part; size_t part_floats; };
+template <class WS>
+static void carve_groupnorm_bwd(WS& ws, int N, int C, GnBwdSlots& s) {
+    s.part_floats = (size_t)2 * N * C;
+    s.part = ws.take(s.part_floats);
+}
+
 }  // namespace vpx
 
 extern "C" {
@@ -145,7 +153,9 @@ int vpx_groupnorm_fwd(const float* x, const float* gamma, const float* beta, con
 
 size_t vpx_groupnorm_bwd_workspace_bytes(int N, int C) {
     if (N < 1 || C < 1) return 0;
-    return vpx::align256((size_t)2 * N * C * sizeof(float)) + 256;
+    vpx::CarveMeasure m; vpx::GnBwdSlots s{};
+    vpx::carve_groupnorm_bwd(m, N, C, s);
+    return m.off + 256;
 }
 
 int vpx_groupnorm_bwd(const float* x, const float* stats, const float* gamma, const float* beta, const float* dy, float* dx, float* dgamma,
@@ -166,9 +176,11 @@ int vpx_groupnorm_bwd(const float* x, const float* stats, const float* gamma, co
             return VPX_ERR_WORKSPACE;
         }
         Carver ws(workspace, workspace_bytes);
-        a.part = ws.take((size_t)2 * N * C);
+        GnBwdSlots sl{};
+        carve_groupnorm_bwd(ws, N, C, sl);
         VPX_CHECK_CARVE(ws, "vpx_groupnorm_bwd");
-        if (!ws_write_ok(a.part, (size_t)2 * N * C * sizeof(float), "vpx_groupnorm_bwd partials")) {
+        a.part = sl.part;
+        if (!ws_write_ok(a.part, sl.part_floats * sizeof(float), "vpx_groupnorm_bwd partials")) {
             set_error("%s", ws_violation());
             ws_violation_clear();
             return VPX_ERR_WORKSPACE;

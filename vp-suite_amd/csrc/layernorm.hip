@@ -221,6 +221,15 @@ hipError_t launch_st_ln_out(const float* o_pre, const float* oc, const float* lc
     return vpx_hip_last_error();
 }
 
+// The stand-alone calls' workspace: the per-chunk partial sums in double (the backward's pair per chunk; the forward fills half of the
+// slot; take() counts floats: a double is two), and the backward's per-sample means.
+struct LnSlots { double* partial; float* sums; };
+template <class WS>
+static void carve_layernorm(WS& ws, int B, bool bwd, LnSlots& s) {
+    s.partial = reinterpret_cast<double*>(ws.take((size_t)B * LN_CHUNKS * 2 * 2));
+    if (bwd) s.sums = ws.take((size_t)B * 2);
+}
+
 }  // namespace vpx
 
 
@@ -230,7 +239,10 @@ extern "C" {
 
 size_t vpx_layernorm_workspace_bytes(int B) {
     if (B < 1) return 0;
-    return vpx::align256((size_t)B * vpx::LN_CHUNKS * 2 * sizeof(double)) + vpx::align256((size_t)B * 2 * sizeof(float)) + 256;
+    vpx::CarveMeasure f, b; vpx::LnSlots s{};
+    vpx::carve_layernorm(f, B, false, s);
+    vpx::carve_layernorm(b, B, true, s);
+    return (f.off > b.off ? f.off : b.off) + 256;
 }
 
 int vpx_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* xhat, float* stats, int B, long long n,
@@ -238,8 +250,11 @@ int vpx_layernorm_fwd(const float* x, const float* gamma, const float* beta, flo
     using namespace vpx;
     if (!x || !gamma || !beta || !y || !stats || B < 1 || n < 1) { set_error("vpx_layernorm_fwd: bad argument"); return VPX_ERR_ARG; }
     if (!workspace || workspace_bytes < vpx_layernorm_workspace_bytes(B)) { set_error("vpx_layernorm_fwd: workspace too small"); return VPX_ERR_WORKSPACE; }
-    double* partial = reinterpret_cast<double*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    VPX_CHECK_HIP(launch_layernorm_fwd(x, gamma, beta, y, xhat, stats, partial, B, n, (hipStream_t)stream));
+    Carver ws(workspace, workspace_bytes);
+    LnSlots s{};
+    carve_layernorm(ws, B, false, s);
+    VPX_CHECK_CARVE(ws, "vpx_layernorm_fwd");
+    VPX_CHECK_HIP(launch_layernorm_fwd(x, gamma, beta, y, xhat, stats, s.partial, B, n, (hipStream_t)stream));
     return VPX_OK;
 }
 
@@ -248,10 +263,11 @@ int vpx_layernorm_bwd(const float* dy, const float* xhat, const float* stats, co
     using namespace vpx;
     if (!dy || !xhat || !stats || !gamma || !dx || !dgamma || !dbeta || B < 1 || HW < 1 || C < 1) { set_error("vpx_layernorm_bwd: bad argument"); return VPX_ERR_ARG; }
     if (!workspace || workspace_bytes < vpx_layernorm_workspace_bytes(B)) { set_error("vpx_layernorm_bwd: workspace too small"); return VPX_ERR_WORKSPACE; }
-    char* w = reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    double* partial = reinterpret_cast<double*>(w);
-    float* sums = reinterpret_cast<float*>(w + align256((size_t)B * LN_CHUNKS * 2 * sizeof(double)));
-    VPX_CHECK_HIP(launch_layernorm_bwd(dy, C, 0, nullptr, xhat, stats, gamma, B, HW, C, partial, sums, dx, dgamma, dbeta, (hipStream_t)stream));
+    Carver ws(workspace, workspace_bytes);
+    LnSlots s{};
+    carve_layernorm(ws, B, true, s);
+    VPX_CHECK_CARVE(ws, "vpx_layernorm_bwd");
+    VPX_CHECK_HIP(launch_layernorm_bwd(dy, C, 0, nullptr, xhat, stats, gamma, B, HW, C, s.partial, s.sums, dx, dgamma, dbeta, (hipStream_t)stream));
     return VPX_OK;
 }
 

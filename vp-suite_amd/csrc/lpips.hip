@@ -586,6 +586,14 @@ static int lpips_forward(const char* who, const float* pred, const float* target
     return head(4);
 }
 
+// The stand-alone stem (either direction) and head: one slot each
+template <class WS>
+static void carve_lpips_stem(WS& ws, float*& wT) { wT = ws.take(ST_PACK_FLOATS); }
+template <class WS>
+static void carve_lpips_head(WS& ws, long long n, long long HW, double*& partial) {   // (take() counts floats: a double is two)
+    partial = reinterpret_cast<double*>(ws.take((size_t)n * lp_head_chunks(HW) * 2));
+}
+
 static int lpips_params_check(const char* who, const float* const* params) {
     if (!g_dry_run)   // (a dry run hands over an address it never reads)
         for (int i = 0; i < 15; ++i)
@@ -599,7 +607,11 @@ using namespace vpx;
 
 extern "C" {
 
-size_t vpx_lpips_stem_workspace_bytes(void) { return align256(ST_PACK_FLOATS * sizeof(float)) + 256; }
+size_t vpx_lpips_stem_workspace_bytes(void) {
+    CarveMeasure m; float* wT;
+    carve_lpips_stem(m, wT);
+    return m.off + 256;
+}
 
 int vpx_lpips_stem_fwd(const float* x0, const float* x1, long long n0, long long n1, int H, int W, const float* w, const float* bias, float* y,
                        void* workspace, size_t workspace_bytes, void* stream_) {
@@ -608,7 +620,8 @@ int vpx_lpips_stem_fwd(const float* x0, const float* x1, long long n0, long long
     if (H < LP_K - 2 * LP_PAD || W < LP_K - 2 * LP_PAD) { set_error("vpx_lpips_stem_fwd: images must be at least 7x7 for the padded 11x11 window (got %dx%d)", H, W); return VPX_ERR_ARG; }
     if (!workspace || workspace_bytes < vpx_lpips_stem_workspace_bytes()) { set_error("vpx_lpips_stem_fwd: workspace too small"); return VPX_ERR_WORKSPACE; }
     Carver ws(workspace, workspace_bytes);
-    float* wT = ws.take(ST_PACK_FLOATS);
+    float* wT;
+    carve_lpips_stem(ws, wT);
     VPX_CHECK_CARVE(ws, "vpx_lpips_stem_fwd");
     return lp_stem("vpx_lpips_stem_fwd", x0, x1, n0, n1, H, W, w, bias, y, wT, (hipStream_t)stream_);
 }
@@ -621,7 +634,9 @@ int vpx_lpips_maxpool_fwd(const float* x, float* y, long long N, int H, int W, i
 
 size_t vpx_lpips_head_workspace_bytes(long long n, long long HW) {
     if (n < 1 || HW < 1) return 0;
-    return align256((size_t)n * lp_head_chunks(HW) * sizeof(double)) + 256;
+    CarveMeasure m; double* partial;
+    carve_lpips_head(m, n, HW, partial);
+    return m.off + 256;
 }
 
 int vpx_lpips_head_fwd(const float* fx, const float* fy, const float* w, long long n, long long HW, int C, double* table, void* workspace,
@@ -630,7 +645,8 @@ int vpx_lpips_head_fwd(const float* fx, const float* fy, const float* w, long lo
     if (n < 1 || HW < 1 || C < 1) { set_error("vpx_lpips_head_fwd: n, HW and C must be >= 1 (got %lld, %lld, %d)", n, HW, C); return VPX_ERR_ARG; }
     if (!workspace || workspace_bytes < vpx_lpips_head_workspace_bytes(n, HW)) { set_error("vpx_lpips_head_fwd: workspace too small"); return VPX_ERR_WORKSPACE; }
     Carver ws(workspace, workspace_bytes);
-    double* partial = reinterpret_cast<double*>(ws.take((size_t)n * lp_head_chunks(HW) * 2));
+    double* partial;
+    carve_lpips_head(ws, n, HW, partial);
     VPX_CHECK_CARVE(ws, "vpx_lpips_head_fwd");
     return lp_head("vpx_lpips_head_fwd", fx, fy, w, n, HW, C, table, partial, (hipStream_t)stream_);
 }
@@ -715,7 +731,8 @@ int vpx_lpips_stem_bwd(const float* x, const float* w, const float* dz, long lon
     if (H < LP_K - 2 * LP_PAD || W < LP_K - 2 * LP_PAD) { set_error("vpx_lpips_stem_bwd: images must be at least 7x7 for the padded 11x11 window (got %dx%d)", H, W); return VPX_ERR_ARG; }
     if (!workspace || workspace_bytes < vpx_lpips_stem_workspace_bytes()) { set_error("vpx_lpips_stem_bwd: workspace too small"); return VPX_ERR_WORKSPACE; }
     Carver ws(workspace, workspace_bytes);
-    float* wT = ws.take(ST_PACK_FLOATS);
+    float* wT;
+    carve_lpips_stem(ws, wT);
     VPX_CHECK_CARVE(ws, "vpx_lpips_stem_bwd");
     return lp_stem_bwd("vpx_lpips_stem_bwd", x, w, dz, n, H, W, dx, wT, (hipStream_t)stream_);
 }

@@ -298,6 +298,26 @@ __global__ __launch_bounds__(SS_THREADS) void ssim_bwd_kernel(const SsimArgs a, 
 }
 
 static inline int pm_chunks(long long frame_elems) { return (int)((frame_elems + PM_CHUNK - 1) / PM_CHUNK); }
+// SS_TH x SS_TW tiles over a tile_h x tile_w area of one frame (forward: the valid SSIM map; backward: the image)
+static inline int ssim_tiles(int tile_h, int tile_w, int* tiles_x) {
+    *tiles_x = (tile_w + SS_TW - 1) / SS_TW;
+    return *tiles_x * ((tile_h + SS_TH - 1) / SS_TH);
+}
+
+// The forward workspaces: per-workgroup partial sums in double (take() counts floats: a double is two)
+struct PmSlots { double* partial; int chunks; };
+template <class WS>
+static void carve_pixel_measures(WS& ws, long long n_frames, long long frame_elems, PmSlots& s) {
+    s.chunks = pm_chunks(frame_elems);
+    s.partial = reinterpret_cast<double*>(ws.take((size_t)n_frames * s.chunks * 3 * 2));
+}
+struct SsimSlots { double* partial; int tiles; };
+template <class WS>
+static void carve_ssim(WS& ws, long long n_frames, int H, int W, SsimSlots& s) {
+    int tiles_x;
+    s.tiles = ssim_tiles(H - SS_HALO, W - SS_HALO, &tiles_x);
+    s.partial = reinterpret_cast<double*>(ws.take((size_t)n_frames * s.tiles * 3 * 2));
+}
 
 static int pixel_measures_check(const char* who, const void* pred, const void* target, const void* io0, const void* io1, long long n_frames,
                                 long long frame_elems) {
@@ -316,8 +336,7 @@ static int ssim_check(const char* who, const void* pred, const void* target, con
     if (layout != VPX_LAYOUT_NHWC && layout != VPX_LAYOUT_NCHW) { set_error("%s: unknown layout %d", who, layout); return VPX_ERR_ARG; }
     a.pred = (const float*)pred; a.target = (const float*)target;
     a.H = H; a.W = W; a.layout = layout;
-    a.tiles_x = (tile_w + SS_TW - 1) / SS_TW;
-    a.tiles = a.tiles_x * ((tile_h + SS_TH - 1) / SS_TH);
+    a.tiles = ssim_tiles(tile_h, tile_w, &a.tiles_x);
     if ((long long)a.tiles * n_frames > 0x7fffffffLL) { set_error("%s: %lld frames of %dx%d exceed one launch", who, n_frames, H, W); return VPX_ERR_UNSUPPORTED; }
     double g[SS_TAPS], sum = 0.0;   // piqa's gaussian_kernel(11, sigma = 1.5), normalised to sum 1
     for (int j = 0; j < SS_TAPS; ++j) { const double x = (j - SS_TAPS / 2) / 1.5; g[j] = exp(-0.5 * x * x); sum += g[j]; }
@@ -333,7 +352,9 @@ extern "C" {
 
 size_t vpx_pixel_measures_workspace_bytes(long long n_frames, long long frame_elems) {
     if (n_frames < 1 || frame_elems < 1) return 0;
-    return align256((size_t)n_frames * pm_chunks(frame_elems) * 3 * sizeof(double)) + 256;
+    CarveMeasure m; PmSlots s{};
+    carve_pixel_measures(m, n_frames, frame_elems, s);
+    return m.off + 256;
 }
 
 int vpx_pixel_measures_fwd(const float* pred, const float* target, long long n_frames, long long frame_elems, double* sums,
@@ -341,13 +362,13 @@ int vpx_pixel_measures_fwd(const float* pred, const float* target, long long n_f
     if (int rc = pixel_measures_check("vpx_pixel_measures_fwd", pred, target, sums, sums, n_frames, frame_elems)) return rc;
     if (!workspace || workspace_bytes < vpx_pixel_measures_workspace_bytes(n_frames, frame_elems)) { set_error("vpx_pixel_measures_fwd: workspace too small"); return VPX_ERR_WORKSPACE; }
     hipStream_t stream = (hipStream_t)stream_;
-    const int chunks = pm_chunks(frame_elems);
     Carver ws(workspace, workspace_bytes);
-    double* partial = reinterpret_cast<double*>(ws.take((size_t)n_frames * chunks * 3 * 2));
+    PmSlots s{};
+    carve_pixel_measures(ws, n_frames, frame_elems, s);
     VPX_CHECK_CARVE(ws, "vpx_pixel_measures_fwd");
-    VPX_LAUNCH(pixel_measures_partial_kernel, dim3((unsigned)(n_frames * chunks)), dim3(PM_THREADS), 0, stream, pred, target, frame_elems, chunks, partial);
+    VPX_LAUNCH(pixel_measures_partial_kernel, dim3((unsigned)(n_frames * s.chunks)), dim3(PM_THREADS), 0, stream, pred, target, frame_elems, s.chunks, s.partial);
     VPX_CHECK_HIP(vpx_hip_last_error());
-    VPX_LAUNCH(pixel_measures_final_kernel, dim3((unsigned)n_frames), dim3(64), 0, stream, partial, chunks, n_frames, sums);
+    VPX_LAUNCH(pixel_measures_final_kernel, dim3((unsigned)n_frames), dim3(64), 0, stream, s.partial, s.chunks, n_frames, sums);
     VPX_CHECK_HIP(vpx_hip_last_error());
     return VPX_OK;
 }
@@ -364,8 +385,9 @@ int vpx_pixel_measures_bwd(const float* pred, const float* target, const float* 
 
 size_t vpx_ssim_workspace_bytes(long long n_frames, int H, int W) {
     if (n_frames < 1 || H < SS_TAPS || W < SS_TAPS) return 0;
-    const size_t tiles = (size_t)((W - SS_HALO + SS_TW - 1) / SS_TW) * ((H - SS_HALO + SS_TH - 1) / SS_TH);
-    return align256((size_t)n_frames * tiles * 3 * sizeof(double)) + 256;
+    CarveMeasure m; SsimSlots s{};
+    carve_ssim(m, n_frames, H, W, s);
+    return m.off + 256;
 }
 
 int vpx_ssim_fwd(const float* pred, const float* target, long long n_frames, int C, int H, int W, int layout, float* ssim,
@@ -375,11 +397,12 @@ int vpx_ssim_fwd(const float* pred, const float* target, long long n_frames, int
     if (!workspace || workspace_bytes < vpx_ssim_workspace_bytes(n_frames, H, W)) { set_error("vpx_ssim_fwd: workspace too small"); return VPX_ERR_WORKSPACE; }
     hipStream_t stream = (hipStream_t)stream_;
     Carver ws(workspace, workspace_bytes);
-    double* partial = reinterpret_cast<double*>(ws.take((size_t)n_frames * a.tiles * 3 * 2));
+    SsimSlots s{};
+    carve_ssim(ws, n_frames, H, W, s);   // (s.tiles == a.tiles: ssim_check counted the same area with the same function)
     VPX_CHECK_CARVE(ws, "vpx_ssim_fwd");
-    VPX_LAUNCH(ssim_fwd_kernel, dim3((unsigned)(n_frames * a.tiles)), dim3(SS_THREADS), 0, stream, a, partial);
+    VPX_LAUNCH(ssim_fwd_kernel, dim3((unsigned)(n_frames * s.tiles)), dim3(SS_THREADS), 0, stream, a, s.partial);
     VPX_CHECK_HIP(vpx_hip_last_error());
-    VPX_LAUNCH(ssim_final_kernel, dim3((unsigned)n_frames), dim3(64), 0, stream, partial, 3 * a.tiles, 1.0 / (3.0 * (H - SS_HALO) * (double)(W - SS_HALO)), ssim);
+    VPX_LAUNCH(ssim_final_kernel, dim3((unsigned)n_frames), dim3(64), 0, stream, s.partial, 3 * s.tiles, 1.0 / (3.0 * (H - SS_HALO) * (double)(W - SS_HALO)), ssim);
     VPX_CHECK_HIP(vpx_hip_last_error());
     return VPX_OK;
 }

@@ -131,13 +131,28 @@ static int merge_check(const char* who, int N, int H, int W, int Cs, int Cp, int
     return VPX_OK;
 }
 
-static inline size_t merge_wpk_floats(int Cs, int Cp, int Co) {
+// The workspaces: every slot in the order the call takes it. One weight pack serves both halves, so it holds the larger one.
+struct MergeFwdSlots { float* wpk; };
+template <class WS>
+static void carve_merge_fwd(WS& ws, int Cs, int Cp, int Co, MergeFwdSlots& s) {
     const size_t a = plain_conv_wpk_floats(Cs, Co, 1, 1), b = plain_conv_wpk_floats(Cp, Co, 1, 1);
-    return a > b ? a : b;
+    s.wpk = ws.take(a > b ? a : b);
 }
-static inline size_t merge_bwd_wpk_floats(int Cs, int Cp, int Co) {
+// ... and one slab slot both weight gradients, sized for the wider half (Cm channels); cap_a, cap_b: the slice cap each half's launch gets
+// (its own geometry's, within what the slot was sized for)
+struct MergeBwdSlots { float *wpk, *slabs, *db_part, *dWa, *dWb; int Cm, cap_a, cap_b; };
+template <class WS>
+static void carve_merge_bwd(WS& ws, int N, int H, int W, int Cs, int Cp, int Co, MergeBwdSlots& s) {
     const size_t a = plain_conv_wpk_floats(Co, Cs, 1, 1), b = plain_conv_wpk_floats(Co, Cp, 1, 1);
-    return a > b ? a : b;
+    s.Cm = Cs > Cp ? Cs : Cp;
+    const int cap_m = wgrad_slices_for(N, H, W, Co, s.Cm, 1, 1);
+    s.cap_a = std::min(wgrad_slices_for(N, H, W, Co, Cs, 1, 1), cap_m);
+    s.cap_b = std::min(wgrad_slices_for(N, H, W, Co, Cp, 1, 1), cap_m);
+    s.wpk = ws.take(a > b ? a : b);
+    s.slabs = ws.take((size_t)cap_m * Co * s.Cm);
+    s.db_part = ws.take((size_t)COLSUM_BLOCKS * Co);
+    s.dWa = ws.take((size_t)Co * Cs);
+    s.dWb = ws.take((size_t)Co * Cp);
 }
 
 }  // namespace vpx
@@ -172,7 +187,9 @@ int vpx_relu_rownorm_bwd(const float* x, const float* norm, const float* dy, flo
 
 size_t vpx_merge1x1_workspace_bytes(int Cs, int Cp, int Co) {
     if (Cs < 1 || Cp < 1 || Co < 1) return 0;
-    return align256(merge_wpk_floats(Cs, Cp, Co) * 4) + 512;
+    CarveMeasure m; MergeFwdSlots s{};
+    carve_merge_fwd(m, Cs, Cp, Co, s);
+    return m.off + 512;
 }
 
 int vpx_merge1x1_fwd(const float* a, const float* b, const float* w, const float* bias, float* y, int N, int H, int W, int Cs, int Cp,
@@ -182,20 +199,21 @@ int vpx_merge1x1_fwd(const float* a, const float* b, const float* w, const float
     if (!workspace || workspace_bytes < vpx_merge1x1_workspace_bytes(Cs, Cp, Co)) { set_error("vpx_merge1x1_fwd: workspace too small"); return VPX_ERR_WORKSPACE; }
     hipStream_t stream = (hipStream_t)stream_;
     Carver ws(workspace, workspace_bytes);
-    float* wpk = ws.take(merge_wpk_floats(Cs, Cp, Co));
+    MergeFwdSlots s{};
+    carve_merge_fwd(ws, Cs, Cp, Co, s);
     VPX_CHECK_CARVE(ws, "vpx_merge1x1_fwd");
     const ConvGeo g{N, H, W};
     const long long K = (long long)Cs + Cp;
     int rc;
-    if ((rc = plain_conv(stream, precision, g, a, Cs, Cs, w, K, 1, 1, 1, Co, false, bias, y, Co, false, wpk))) return rc;
-    return plain_conv(stream, precision, g, b, Cp, Cp, w + Cs, K, 1, 1, 1, Co, false, nullptr, y, Co, true, wpk);
+    if ((rc = plain_conv(stream, precision, g, a, Cs, Cs, w, K, 1, 1, 1, Co, false, bias, y, Co, false, s.wpk))) return rc;
+    return plain_conv(stream, precision, g, b, Cp, Cp, w + Cs, K, 1, 1, 1, Co, false, nullptr, y, Co, true, s.wpk);
 }
 
 size_t vpx_merge1x1_bwd_workspace_bytes(int N, int H, int W, int Cs, int Cp, int Co) {
     if (N < 1 || H < 1 || W < 1 || Cs < 1 || Cp < 1 || Co < 1) return 0;
-    const int Cm = Cs > Cp ? Cs : Cp;
-    return align256(merge_bwd_wpk_floats(Cs, Cp, Co) * 4) + align256((size_t)wgrad_slices_for(N, H, W, Co, Cm, 1, 1) * Co * Cm * 4) +
-           align256((size_t)COLSUM_BLOCKS * Co * 4) + align256((size_t)Co * Cs * 4) + align256((size_t)Co * Cp * 4) + 1024;
+    CarveMeasure m; MergeBwdSlots s{};
+    carve_merge_bwd(m, N, H, W, Cs, Cp, Co, s);
+    return m.off + 1024;
 }
 
 int vpx_merge1x1_bwd(const float* a, const float* b, const float* w, const float* dy, float* da, float* db, float* dw, float* dbias, int N,
@@ -204,29 +222,22 @@ int vpx_merge1x1_bwd(const float* a, const float* b, const float* w, const float
     if (!a || !b || !w || !dy) { set_error("vpx_merge1x1_bwd: NULL tensor argument"); return VPX_ERR_ARG; }
     if (!workspace || workspace_bytes < vpx_merge1x1_bwd_workspace_bytes(N, H, W, Cs, Cp, Co)) { set_error("vpx_merge1x1_bwd: workspace too small"); return VPX_ERR_WORKSPACE; }
     hipStream_t stream = (hipStream_t)stream_;
-    const int Cm = Cs > Cp ? Cs : Cp;
     Carver ws(workspace, workspace_bytes);
-    float* wpk = ws.take(merge_bwd_wpk_floats(Cs, Cp, Co));
-    const int cap_a = wgrad_slices_for(N, H, W, Co, Cs, 1, 1), cap_b = wgrad_slices_for(N, H, W, Co, Cp, 1, 1);
-    float* slabs = ws.take((size_t)wgrad_slices_for(N, H, W, Co, Cm, 1, 1) * Co * Cm);
-    float* db_part = ws.take((size_t)COLSUM_BLOCKS * Co);
-    float* dWa = ws.take((size_t)Co * Cs);
-    float* dWb = ws.take((size_t)Co * Cp);
+    MergeBwdSlots s{};
+    carve_merge_bwd(ws, N, H, W, Cs, Cp, Co, s);
     VPX_CHECK_CARVE(ws, "vpx_merge1x1_bwd");
     const ConvGeo g{N, H, W};
     const long long K = (long long)Cs + Cp;
     int rc;
-    if (da && (rc = plain_conv(stream, precision, g, dy, Co, Co, w, K, 1, 1, 1, Cs, true, nullptr, da, Cs, false, wpk))) return rc;
-    if (db && (rc = plain_conv(stream, precision, g, dy, Co, Co, w + Cs, K, 1, 1, 1, Cp, true, nullptr, db, Cp, false, wpk))) return rc;
+    if (da && (rc = plain_conv(stream, precision, g, dy, Co, Co, w, K, 1, 1, 1, Cs, true, nullptr, da, Cs, false, s.wpk))) return rc;
+    if (db && (rc = plain_conv(stream, precision, g, dy, Co, Co, w + Cs, K, 1, 1, 1, Cp, true, nullptr, db, Cp, false, s.wpk))) return rc;
     if (dw) {
-        // (the slice caps of the two halves may differ: each launch gets the cap its own geometry allows, both within the slab slot)
-        const int cap_m = wgrad_slices_for(N, H, W, Co, Cm, 1, 1);
-        if ((rc = plain_wgrad(stream, precision, g, dy, Co, a, Cs, 1, 1, slabs, dWa, nullptr, cap_a < cap_m ? cap_a : cap_m))) return rc;
-        if ((rc = plain_wgrad(stream, precision, g, dy, Co, b, Cp, 1, 1, slabs, dWb, nullptr, cap_b < cap_m ? cap_b : cap_m))) return rc;
-        VPX_LAUNCH(merge_dw_kernel, dim3((unsigned)((Co * K + 255) / 256)), dim3(256), 0, stream, dWa, dWb, dw, Co, Cs, Cp);
+        if ((rc = plain_wgrad(stream, precision, g, dy, Co, a, Cs, 1, 1, s.slabs, s.dWa, nullptr, s.cap_a))) return rc;
+        if ((rc = plain_wgrad(stream, precision, g, dy, Co, b, Cp, 1, 1, s.slabs, s.dWb, nullptr, s.cap_b))) return rc;
+        VPX_LAUNCH(merge_dw_kernel, dim3((unsigned)((Co * K + 255) / 256)), dim3(256), 0, stream, s.dWa, s.dWb, dw, Co, Cs, Cp);
         VPX_CHECK_HIP(vpx_hip_last_error());
     }
-    if (dbias) VPX_CHECK_HIP(launch_colsum(dy, nullptr, 0.f, nullptr, dbias, db_part, (long long)N * H * W, Co, stream));
+    if (dbias) VPX_CHECK_HIP(launch_colsum(dy, nullptr, 0.f, nullptr, dbias, s.db_part, (long long)N * H * W, Co, stream));
     return VPX_OK;
 }
 

@@ -222,27 +222,46 @@ static unsigned adam_blocks(long long n) {
     return (unsigned)(blocks > 2048 ? 2048 : blocks);
 }
 
+// The reductions' workspaces: per-workgroup partial sums in double (take() counts floats: a double is two). The queries have no size
+// argument, so the slot holds the block cap's worth whatever n is; `blocks` is what this n launches.
+struct TailSlots { double* partial; long long blocks; };
+template <class WS>
+static void carve_mse(WS& ws, long long n, TailSlots& s) {
+    s.blocks = std::min<long long>((n + MSE_THREADS * 4 - 1) / (MSE_THREADS * 4), MSE_MAX_BLOCKS);
+    s.partial = reinterpret_cast<double*>(ws.take((size_t)MSE_MAX_BLOCKS * 2));
+}
+template <class WS>
+static void carve_grad_stats(WS& ws, long long n, TailSlots& s) {
+    s.blocks = std::min<long long>((n + GS_THREADS * 4 - 1) / (GS_THREADS * 4), GS_MAX_BLOCKS);
+    s.partial = reinterpret_cast<double*>(ws.take((size_t)GS_MAX_BLOCKS * 3 * 2));
+}
+
 }  // namespace vpx
 
 using namespace vpx;
 
 extern "C" {
 
-size_t vpx_mse_loss_workspace_bytes(void) { return MSE_MAX_BLOCKS * sizeof(double) + 256; }
+size_t vpx_mse_loss_workspace_bytes(void) {
+    CarveMeasure m; TailSlots s{};
+    carve_mse(m, 1, s);
+    return m.off + 256;
+}
 
 int vpx_mse_loss(const float* pred, const float* target, long long n_elements, long long n_frames, float scale, float* loss,
                  float* dpred, void* workspace, size_t workspace_bytes, void* stream_) {
     if (!pred || !target || !loss || n_elements < 1 || n_frames < 1) { set_error("vpx_mse_loss: bad argument"); return VPX_ERR_ARG; }
     if (!workspace || workspace_bytes < vpx_mse_loss_workspace_bytes()) { set_error("vpx_mse_loss: workspace too small"); return VPX_ERR_WORKSPACE; }
     hipStream_t stream = (hipStream_t)stream_;
-    double* partial = reinterpret_cast<double*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    long long blocks = (n_elements + MSE_THREADS * 4 - 1) / (MSE_THREADS * 4);
-    if (blocks > MSE_MAX_BLOCKS) blocks = MSE_MAX_BLOCKS;
+    Carver ws(workspace, workspace_bytes);
+    TailSlots s{};
+    carve_mse(ws, n_elements, s);
+    VPX_CHECK_CARVE(ws, "vpx_mse_loss");
     const double mult = (double)scale / (double)n_frames;
-    VPX_LAUNCH(mse_partial_kernel, dim3((unsigned)blocks), dim3(MSE_THREADS), 0, stream, pred, target, n_elements,
-                       (float)(2.0 * mult), dpred, partial);
+    VPX_LAUNCH(mse_partial_kernel, dim3((unsigned)s.blocks), dim3(MSE_THREADS), 0, stream, pred, target, n_elements,
+                       (float)(2.0 * mult), dpred, s.partial);
     VPX_CHECK_HIP(vpx_hip_last_error());
-    VPX_LAUNCH(mse_final_kernel, dim3(1), dim3(64), 0, stream, partial, (int)blocks, mult, loss);
+    VPX_LAUNCH(mse_final_kernel, dim3(1), dim3(64), 0, stream, s.partial, (int)s.blocks, mult, loss);
     VPX_CHECK_HIP(vpx_hip_last_error());
     return VPX_OK;
 }
@@ -256,7 +275,11 @@ int vpx_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
     return VPX_OK;
 }
 
-size_t vpx_grad_stats_workspace_bytes(void) { return GS_MAX_BLOCKS * 3 * sizeof(double) + 256; }
+size_t vpx_grad_stats_workspace_bytes(void) {
+    CarveMeasure m; TailSlots s{};
+    carve_grad_stats(m, 1, s);
+    return m.off + 256;
+}
 
 int vpx_grad_stats(const float* grad, long long n, double grad_scale, double* stats, void* workspace, size_t workspace_bytes,
                    void* stream_) {
@@ -265,14 +288,13 @@ int vpx_grad_stats(const float* grad, long long n, double grad_scale, double* st
     if (!(grad_scale >= 0.0)) { set_error("vpx_grad_stats: grad_scale must not be negative or NaN"); return VPX_ERR_ARG; }
     if (!workspace || workspace_bytes < vpx_grad_stats_workspace_bytes()) { set_error("vpx_grad_stats: workspace too small"); return VPX_ERR_WORKSPACE; }
     hipStream_t stream = (hipStream_t)stream_;
-    long long blocks = (n + GS_THREADS * 4 - 1) / (GS_THREADS * 4);
-    if (blocks > GS_MAX_BLOCKS) blocks = GS_MAX_BLOCKS;
     Carver ws(workspace, workspace_bytes);
-    double* partial = reinterpret_cast<double*>(ws.take((size_t)blocks * 3 * 2));
+    TailSlots s{};
+    carve_grad_stats(ws, n, s);
     VPX_CHECK_CARVE(ws, "vpx_grad_stats");
-    VPX_LAUNCH(grad_stats_partial_kernel, dim3((unsigned)blocks), dim3(GS_THREADS), 0, stream, grad, n, partial);
+    VPX_LAUNCH(grad_stats_partial_kernel, dim3((unsigned)s.blocks), dim3(GS_THREADS), 0, stream, grad, n, s.partial);
     VPX_CHECK_HIP(vpx_hip_last_error());
-    VPX_LAUNCH(grad_stats_final_kernel, dim3(1), dim3(64), 0, stream, partial, (int)blocks, grad_scale, stats);
+    VPX_LAUNCH(grad_stats_final_kernel, dim3(1), dim3(64), 0, stream, s.partial, (int)s.blocks, grad_scale, stats);
     VPX_CHECK_HIP(vpx_hip_last_error());
     return VPX_OK;
 }

@@ -254,7 +254,7 @@ int tg_warp_bwd_det(const float* h, const float* flows, const float* dwarped, fl
         return VPX_ERR_WORKSPACE;
     }
     hipStream_t stream = (hipStream_t)stream_;
-    long long* acc = dh ? reinterpret_cast<long long*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255) : nullptr;
+    long long* acc = dh ? static_cast<long long*>(workspace) : nullptr;   // (a slot of the sequence call's carve: on a 256-byte boundary as it is)
     const long long n = (long long)B * H * W * C, total = (long long)B * H * W * L;
     if (acc) VPX_CHECK_HIP(vpx_memset_async(acc, 0, (size_t)n * sizeof(long long), stream));
     VPX_LAUNCH(trajgru_warp_bwd_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, g, h, flows, dwarped, dh,

@@ -402,6 +402,28 @@ static inline int rc_slices(const RcArgs& A, long long nel) {
 }
 static inline long long rc_nel(const RcArgs& A, bool bias) { return (long long)A.kt * A.ks * A.ks * A.Co * (A.Ca + A.Cb) + (bias ? A.Co : 0); }
 
+// The workspaces: every slot in the order the call takes it, and the counts the launches are sized by.
+struct RcFwdSlots { float* part; long long nblk; };   // per-workgroup statistics of the training epilogue (else one unused float)
+template <class WS>
+static void carve_rconv_fwd(WS& ws, const RcArgs& A, int epilogue, RcFwdSlots& s) {
+    s.nblk = rc_blocks(A.npix);
+    s.part = ws.take(epilogue == VPX_RCONV_EPI_STATS ? (size_t)s.nblk * 2 * A.Co : 1);
+}
+struct RcBwdSlots { float* slab; int ns; };   // ns K slices of [dw | dbias], sized with the bias whether or not the call wants it
+template <class WS>
+static void carve_rconv_bwd(WS& ws, const RcArgs& A, RcBwdSlots& s) {
+    const long long nel = rc_nel(A, true);
+    s.ns = rc_slices(A, nel);
+    s.slab = ws.take((size_t)s.ns * nel);
+}
+struct BnBwdSlots { float *part, *sums; long long nblk; };
+template <class WS>
+static void carve_bn_relu_bwd(WS& ws, long long npix, int C, BnBwdSlots& s) {
+    s.nblk = rc_blocks(npix);
+    s.part = ws.take((size_t)s.nblk * 2 * C);
+    s.sums = ws.take((size_t)2 * C);
+}
+
 static int bn_check(const char* who, long long N, int H, int W, int C, bool pool) {
     const long long dims[3] = {N, H, W};
     if (N < 1 || H < 1 || W < 1 || C < 1 || C > RC_MAX_CH || !rc_fits(dims, 3, C)) { set_error("%s: bad shape (N=%lld H=%d W=%d C=%d)", who, N, H, W, C); return VPX_ERR_ARG; }
@@ -419,7 +441,9 @@ size_t vpx_rconv_workspace_bytes(const vpx_rconv_desc* d, int epilogue) {
     RcArgs A;
     if (rc_check("vpx_rconv_workspace_bytes", d, A)) return 0;
     if (epilogue < VPX_RCONV_EPI_PLAIN || epilogue > VPX_RCONV_EPI_STATS) { set_error("vpx_rconv_workspace_bytes: unknown epilogue %d", epilogue); return 0; }
-    return align256(epilogue == VPX_RCONV_EPI_STATS ? (size_t)rc_blocks(A.npix) * 2 * A.Co * 4 : 4) + 512;
+    CarveMeasure m; RcFwdSlots s{};
+    carve_rconv_fwd(m, A, epilogue, s);
+    return m.off + 512;
 }
 
 int vpx_rconv_fwd(const vpx_rconv_desc* d, int epilogue, const float* a, const float* b, const float* w, const float* gamma_or_bias,
@@ -438,15 +462,15 @@ int vpx_rconv_fwd(const vpx_rconv_desc* d, int epilogue, const float* a, const f
     if (!workspace || workspace_bytes < vpx_rconv_workspace_bytes(d, epilogue)) { set_error("vpx_rconv_fwd: workspace too small"); return VPX_ERR_WORKSPACE; }
     hipStream_t stream = (hipStream_t)stream_;
     Carver ws(workspace, workspace_bytes);
-    const long long nblk = rc_blocks(A.npix);
-    float* part = ws.take(epilogue == VPX_RCONV_EPI_STATS ? (size_t)nblk * 2 * A.Co : 1);
+    RcFwdSlots s{};
+    carve_rconv_fwd(ws, A, epilogue, s);
     VPX_CHECK_CARVE(ws, "vpx_rconv_fwd");
     A.a = a; A.b = b; A.w = w;
-    VPX_LAUNCH(rconv_fwd_kernel, dim3((unsigned)nblk, (unsigned)((A.Co + RC_VEC - 1) / RC_VEC)), dim3(RC_PIX), 0, stream, A, epilogue, gamma_or_bias, beta,
-               (const float*)running_mean, (const float*)running_var, eps, y, part);
+    VPX_LAUNCH(rconv_fwd_kernel, dim3((unsigned)s.nblk, (unsigned)((A.Co + RC_VEC - 1) / RC_VEC)), dim3(RC_PIX), 0, stream, A, epilogue, gamma_or_bias, beta,
+               (const float*)running_mean, (const float*)running_var, eps, y, s.part);
     VPX_CHECK_HIP(vpx_hip_last_error());
     if (epilogue == VPX_RCONV_EPI_STATS) {
-        VPX_LAUNCH(bn_stats_finalize_kernel, dim3((unsigned)((A.Co + 63) / 64)), dim3(64), 0, stream, (const float*)part, (int)nblk, A.Co, A.npix, eps, momentum,
+        VPX_LAUNCH(bn_stats_finalize_kernel, dim3((unsigned)((A.Co + 63) / 64)), dim3(64), 0, stream, (const float*)s.part, (int)s.nblk, A.Co, A.npix, eps, momentum,
                    stats, running_mean, running_var);
         VPX_CHECK_HIP(vpx_hip_last_error());
     }
@@ -456,8 +480,9 @@ int vpx_rconv_fwd(const vpx_rconv_desc* d, int epilogue, const float* a, const f
 size_t vpx_rconv_bwd_workspace_bytes(const vpx_rconv_desc* d) {
     RcArgs A;
     if (rc_check("vpx_rconv_bwd_workspace_bytes", d, A)) return 0;
-    const long long nel = rc_nel(A, true);
-    return align256((size_t)rc_slices(A, nel) * nel * 4) + 512;
+    CarveMeasure m; RcBwdSlots s{};
+    carve_rconv_bwd(m, A, s);
+    return m.off + 512;
 }
 
 int vpx_rconv_bwd(const vpx_rconv_desc* d, const float* a, const float* b, const float* w, const float* dy, float* da, float* db, float* dw,
@@ -469,8 +494,8 @@ int vpx_rconv_bwd(const vpx_rconv_desc* d, const float* a, const float* b, const
     if (!workspace || workspace_bytes < vpx_rconv_bwd_workspace_bytes(d)) { set_error("vpx_rconv_bwd: workspace too small"); return VPX_ERR_WORKSPACE; }
     hipStream_t stream = (hipStream_t)stream_;
     Carver ws(workspace, workspace_bytes);
-    const long long nel_max = rc_nel(A, true);
-    float* slab = ws.take((size_t)rc_slices(A, nel_max) * nel_max);
+    RcBwdSlots s{};
+    carve_rconv_bwd(ws, A, s);
     VPX_CHECK_CARVE(ws, "vpx_rconv_bwd");
     A.a = a; A.b = b; A.w = w;
     const long long nblk_in = rc_blocks((long long)A.B * A.T * A.H * A.W);
@@ -485,11 +510,11 @@ int vpx_rconv_bwd(const vpx_rconv_desc* d, const float* a, const float* b, const
     if (dw || dbias) {
         const bool with_bias = dbias != nullptr;
         const long long nel = rc_nel(A, with_bias), nw = rc_nel(A, false);
-        const int ns = rc_slices(A, nel_max);       // (the rule the slab was sized by)
+        const int ns = s.ns;
         const long long chunk = (A.npix + ns - 1) / ns;
-        VPX_LAUNCH(rconv_wgrad_kernel, dim3((unsigned)((nel + 255) / 256), (unsigned)ns), dim3(256), 0, stream, A, dy, slab, chunk, with_bias ? 1 : 0);
+        VPX_LAUNCH(rconv_wgrad_kernel, dim3((unsigned)((nel + 255) / 256), (unsigned)ns), dim3(256), 0, stream, A, dy, s.slab, chunk, with_bias ? 1 : 0);
         VPX_CHECK_HIP(vpx_hip_last_error());
-        VPX_LAUNCH(rconv_wgrad_reduce_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, stream, (const float*)slab, ns, nw, nel, dw, dbias);
+        VPX_LAUNCH(rconv_wgrad_reduce_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, stream, (const float*)s.slab, ns, nw, nel, dw, dbias);
         VPX_CHECK_HIP(vpx_hip_last_error());
     }
     return VPX_OK;
@@ -508,7 +533,9 @@ int vpx_bn_relu_fwd(const float* x, const float* stats, const float* gamma, cons
 
 size_t vpx_bn_relu_bwd_workspace_bytes(long long N, int H, int W, int C) {
     if (bn_check("vpx_bn_relu_bwd_workspace_bytes", N, H, W, C, false)) return 0;
-    return align256((size_t)rc_blocks(N * H * W) * 2 * C * 4) + align256((size_t)2 * C * 4) + 512;
+    CarveMeasure m; BnBwdSlots s{};
+    carve_bn_relu_bwd(m, N * H * W, C, s);
+    return m.off + 512;
 }
 
 int vpx_bn_relu_bwd(const float* x, const float* act, const float* stats, const float* gamma, const float* dact, const float* dpool, float* dx,
@@ -517,16 +544,16 @@ int vpx_bn_relu_bwd(const float* x, const float* act, const float* stats, const 
     if (!x || !act || !stats || !gamma || !dx || (!dact && !dpool)) { set_error("vpx_bn_relu_bwd: NULL tensor argument"); return VPX_ERR_ARG; }
     if (!workspace || workspace_bytes < vpx_bn_relu_bwd_workspace_bytes(N, H, W, C)) { set_error("vpx_bn_relu_bwd: workspace too small"); return VPX_ERR_WORKSPACE; }
     hipStream_t stream = (hipStream_t)stream_;
-    const long long npix = N * H * W, nblk = rc_blocks(npix);
+    const long long npix = N * H * W;
     Carver ws(workspace, workspace_bytes);
-    float* part = ws.take((size_t)nblk * 2 * C);
-    float* sums = ws.take((size_t)2 * C);
+    BnBwdSlots s{};
+    carve_bn_relu_bwd(ws, npix, C, s);
     VPX_CHECK_CARVE(ws, "vpx_bn_relu_bwd");
-    VPX_LAUNCH(bn_bwd_reduce_kernel, dim3((unsigned)nblk), dim3(256), 0, stream, x, act, stats, dact, dpool, part, npix, H, W, C);
+    VPX_LAUNCH(bn_bwd_reduce_kernel, dim3((unsigned)s.nblk), dim3(256), 0, stream, x, act, stats, dact, dpool, s.part, npix, H, W, C);
     VPX_CHECK_HIP(vpx_hip_last_error());
-    VPX_LAUNCH(bn_bwd_finalize_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, stream, (const float*)part, (int)nblk, C, sums, dgamma, dbeta);
+    VPX_LAUNCH(bn_bwd_finalize_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, stream, (const float*)s.part, (int)s.nblk, C, s.sums, dgamma, dbeta);
     VPX_CHECK_HIP(vpx_hip_last_error());
-    VPX_LAUNCH(bn_bwd_apply_kernel, dim3((unsigned)((npix * C + 255) / 256)), dim3(256), 0, stream, x, act, stats, gamma, dact, dpool, (const float*)sums, dx,
+    VPX_LAUNCH(bn_bwd_apply_kernel, dim3((unsigned)((npix * C + 255) / 256)), dim3(256), 0, stream, x, act, stats, gamma, dact, dpool, (const float*)s.sums, dx,
                npix, H, W, C);
     VPX_CHECK_HIP(vpx_hip_last_error());
     return VPX_OK;
