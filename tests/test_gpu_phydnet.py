@@ -7,8 +7,6 @@ Bounds: forward values max|Δ|/max|ref| < 1e-4 (the north-star bar; the block an
 the elements kept: all of a small tensor, a strided slice of a large one) are held to the same 5e-5, the sum measured against the
 tensor's L1 norm; bf16x3 gradients of the whole model are held relative to a same-sized forward perturbation of the f32 model
 (see PERTURB), every figure recorded in the parity log."""
-import math
-
 import numpy as np
 import pytest
 import torch
@@ -16,6 +14,7 @@ import torch.nn.functional as F
 
 from golden_util import checksum, load_golden, name_seed, seeded_rand, seeded_randn
 from parity import relmax as _relmax
+from phydnet_ref import _moment_loss_fp64
 from test_phydnet_host import (PHY_CELL_CASES, PHY_DEFAULT_B, PHY_DEFAULT_CTX, PHY_DEFAULT_KW, PHY_DEFAULT_PRED,
                                PHY_TINY_AC_KW, PHY_TINY_B, PHY_TINY_CTX, PHY_TINY_KW, PHY_TINY_PRED, PHY_TRAIN_CTX, PHY_TRAIN_PRED,
                                grad_kept, phy_fill_)
@@ -110,18 +109,6 @@ def test_phydnet_ops_check_every_tensor(vpx):
 
 
 # ---- moment loss ----------------------------------------------------------------------------------------------------------------
-def _moment_loss_fp64(W, scale):
-    hid, cin, kh, kw = W.shape
-    def mmat(k):
-        return torch.tensor([[((u - (k - 1) // 2) ** i) / math.factorial(i) for u in range(k)] for i in range(k)], dtype=torch.float64)
-    M0, M1 = mmat(kh), mmat(kw)
-    C = torch.zeros(hid, kh, kw, dtype=torch.float64)
-    for o in range(min(hid, kh * kw)):
-        C[o, o // kw, o % kw] = 1.0
-    moment = torch.einsum("iu,obuv,jv->obij", M0, W, M1)
-    return scale * ((moment - C[:, None]) ** 2).mean(dim=(0, 2, 3)).sum()
-
-
 @pytest.mark.parametrize("shape", [(49, 64, 7, 7), (49, 16, 7, 7), (9, 5, 3, 3)])
 def test_phydnet_moment_loss_vs_fp64(vpx, shape):
     from vp_suite_amd import phy_ops

@@ -124,6 +124,15 @@ def test_phydnet_rejects_non_square_phycell_kernel(vpx):
             MODEL_CLASSES["phy"]("cpu", phycell_kernel_size=ks, **PHY_TINY_KW)
 
 
+def test_phycell_cell_rejects_non_square_or_even_kernel(vpx):
+    """The block's own check (the model's is above): the moment matrices and the 'same' padding are stated for square odd kernels."""
+    from vp_suite_amd.model_blocks.phydnet import PhyCell_Cell
+    for ks in ((3, 5), (4, 4)):
+        with pytest.raises(ValueError):
+            PhyCell_Cell(input_dim=16, action_conditional=False, action_size=0, hidden_dim=9, kernel_size=ks)
+    PhyCell_Cell(input_dim=16, action_conditional=False, action_size=0, hidden_dim=9, kernel_size=(3, 3))
+
+
 def test_phy_ops_refuse_cpu_tensors(vpx):
     """No CPU fallback: every op raises on host tensors before anything else."""
     from vp_suite_amd import phy_ops
@@ -225,3 +234,36 @@ def test_phydnet_conv_layers(L, det, prec):
         rc = L.vpx_conv2d_ex_bwd(ctypes.byref(d), _fake(1), _fake(2), _fake(4), _fake(5), _fake(6), _fake(7), _fake(8),
                                  ctypes.c_void_p(WS_BASE), nbw, None)
         assert rc == OK, (H, W, Ci, Co, k, s, tr, L.vpx_last_error())
+
+
+# ---- the plain-torch restatement (tests/phydnet_ref.py) against the reference's PhyCell fixtures, on the CPU -------------------------
+@pytest.mark.parametrize("tag", list(PHY_CELL_CASES))
+def test_phydnet_ref_matches_cell_fixtures_on_cpu(vpx, tag):
+    """phydnet_ref's PhyCell block, run in fp64 on the inputs of the recorded f32 fixture, must be the reference's block: every step's
+    output and the final state to 1e-5, the frame gradient and every parameter gradient to 5e-5 (max-normalised, the block's bars).
+    test_gpu_phydnet_kernels.py holds the library to this restatement at shapes no fixture has; this case is what entitles it to."""
+    import phydnet_ref
+    from golden_util import name_seed, seeded_randn
+    from vp_suite_amd.model_blocks import PhyCell
+    idim, hid, k, H, W, asz, B, steps = PHY_CELL_CASES[tag]
+    g = load_golden(f"phydnet_cell_{tag}")
+    blk = phy_fill_(PhyCell((H, W), idim, [hid], 1, (k, k), asz > 0, asz, "cpu"), name_seed("phydnet_cell." + tag))
+    sd = {key: v.detach().double().requires_grad_(True) for key, v in blk.state_dict().items()}
+    assert (asz > 0) == ("cell_list.0.frame_action_conv.weight" in sd)
+    frames = seeded_randn((B, steps, idim, H, W), name_seed(f"phydnet_cell.{tag}.frames")).double().requires_grad_(True)
+    actions = seeded_randn((B, steps, max(asz, 1)), name_seed(f"phydnet_cell.{tag}.actions"))[:, :, :asz].double()
+    outs, Hs = phydnet_ref.phycell_stack(sd, 1, frames, actions)
+
+    def err(got, ref):
+        return float(np.abs(got.detach().numpy() - ref).max()) / float(np.abs(ref).max())
+    loss = 0.0
+    for t, out in enumerate(outs):
+        assert err(out, g[f"out{t}"]) < 1e-5, t
+        loss = loss + (out * seeded_randn(out.shape, name_seed(f"phydnet_cell.{tag}.g{t}")).double()).sum()
+    assert err(Hs[0], g["H0"]) < 1e-5
+    loss.backward()
+    assert err(frames.grad, g["dframes"]) < 5e-5
+    names = [key for key, _ in blk.named_parameters()]
+    assert sorted("grad." + key for key in names) == sorted(key for key in g if key.startswith("grad."))
+    for key in names:
+        assert err(sd[key].grad, g["grad." + key]) < 5e-5, key
